@@ -26,21 +26,6 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 _T0 = time.perf_counter()
 
-
-def _one_rank_job():
-    gpus = [a.split("=", 1)[1] if "=" in a else (sys.argv[i + 1] if i + 1 < len(sys.argv) else "1") for i, a in enumerate(sys.argv) if a == "--gpus" or a.startswith("--gpus=")]
-    return int(os.environ.get("WORLD_SIZE", "1")) == 1 and os.environ.get("VIDC_DIST_WORLD1", "0") != "1" and (not gpus or gpus[-1] == "1")
-
-
-if "--train" in sys.argv and _one_rank_job():
-    # The training step runs on five HIP streams (main + up to four lanes); the runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware
-    # queues (default 4), so two lanes share a queue and their kernels serialise: 26.3-26.5 against 26.7-27.4 ms per step with 8 queues.
-    # ONE rank without a process group only: across ranks the step is two captured graphs with the decoder's all-reduce in between, and
-    # that form runs ~2x slower with more than 4 queues (50-57 against 27.3-28.3 ms; profiles/r4_train_side_stream_experiments.txt).
-    # (The inference stream mode, three lanes + the caller's stream, is FASTER with the default 4: 362 against 311 frames/s -- not set there.)
-    # Read by the runtime when it initialises, i.e. at the first device call of this process.
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 from vi_depth_completion_amd import sharding, synthetic as S   # noqa: E402
 
 FLOPS_PER_FRAME = {(240, 320): 293.88e9, (256, 320): 311.63e9}   # SURVEY.md §8d, reference formulation, 2 FLOP/MAC
@@ -103,7 +88,12 @@ def parse():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="no GPU work: every rank only joins the process group and gathers a fake record (tests/test_bench_launcher.py runs "
                          "`bench.py --gpus 2 --launcher-selftest` under gloo on the CPU: spawn, rendezvous, gather, the n_gpus check)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its LAST step as DIR/<name>.npy (float32; rank 0): "
+                         "depth_<leg>.npy per inference leg, train_loss.npy with --train.  Same arguments = same inputs, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.frames_per_launch <= 0:
         args.frames_per_launch = 4 if args.batch == 1 else 1
     return args
@@ -302,12 +292,15 @@ def measure(args, dev, rank, world, precision):
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run(args.steps)
+        last = run(args.steps)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         region_s.append(time.perf_counter() - t0)
+    # the last timed step's depth map, copied out before anything else runs on the pipeline (in the stream mode it is a view of a lane's
+    # output buffer, valid until the next item is requested)
+    last_output = last.detach().float().cpu().numpy() if args.dump_outputs else None
     elapsed = sorted(region_s)[len(region_s) // 2]      # this rank's median region (roofline bookkeeping below); the line uses max over ranks per region
 
     # ---- steady state of the stream mode (outside the timed regions): one long stream, a device time stamp behind every item's result;
@@ -460,7 +453,7 @@ def measure(args, dev, rank, world, precision):
                 for name, ops in ((("frame_program" if args.mode == "interleaved" else "surface_normal"), sn_ops), ("depth_completion", dc_ops)):
                     for n, t in ops:
                         f.write("%s\t%.2f\t%s\n" % (name, t * 1e3, n))
-    return {"elapsed": elapsed, "region_s": region_s, "steady": steady, "pipe": pipe, "lanes": lanes, "sn_sd": sn_sd, "dc_sd": dc_sd, "cc": cc, "det_sd": det_sd, "roofline": roofline, "extra": extra,
+    return {"last_output": last_output, "elapsed": elapsed, "region_s": region_s, "steady": steady, "pipe": pipe, "lanes": lanes, "sn_sd": sn_sd, "dc_sd": dc_sd, "cc": cc, "det_sd": det_sd, "roofline": roofline, "extra": extra,
             "frames": frames, "pre": pre}
 
 
@@ -490,6 +483,7 @@ def train_leg(args, dev, rank, world):
     for _ in range(args.steps):
         losses.append(tr.step(image, normal, depth_in, gt))
     torch.cuda.synchronize()
+    last_loss = losses[-1]
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -517,6 +511,8 @@ def train_leg(args, dev, rank, world):
                          "note": "whole step: 3 x forward conv FLOPs per frame / step time (fwd + dgrad + wgrad launches of the conv kernel; "
                                  "BatchNorm, pooling, loss and Adam are HBM-bound and inside the same time)"},
             "cpu_baseline": None, "losses": [round(float(x), 6) for x in losses[-min(len(losses), 6):]]}), flush=True)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"train_loss": np.asarray([float(last_loss)], dtype=np.float32)})
 
 
 def main():
@@ -743,10 +739,27 @@ def main():
                              "conv_stack": rm["extra"].get("conv_stack")}})
         if extra_legs is not None:
             line["extra_legs"] = extra_legs
+        if args.dump_outputs:
+            line["dumped_outputs"] = dump_outputs(args.dump_outputs, {"depth_" + m: res[m]["last_output"] for m in legs})
         print(json.dumps(line), flush=True)
     if world > 1 or os.environ.get("VIDC_DIST_WORLD1", "0") == "1":
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes every array as out_dir/<name>.npy in float32 (all of them together at most DUMP_LIMIT_BYTES); returns {name: shape}."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def run_extra_legs(args):

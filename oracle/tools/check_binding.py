@@ -1,7 +1,7 @@
 """Executes INTEGRATION.md §1's recipe against THE REFERENCE'S OWN HARNESS, in the build container (CPU): alias the package
 `networks` to vi_depth_completion_amd.networks, import the reference's unchanged main.py, and let its code -- not ours -- construct,
-load and switch the networks.  TEST INFRASTRUCTURE (tests/test_binding.py runs it as a child process; never on the GPU box: the
-reference is not there).
+load and switch the networks.  Run by hand next to a checkout of the reference (CPU only); not part of
+the suite, which needs nothing outside this repository.
 
 What the reference does with the classes, and what is checked here:
   * `RunDepthCompletion(args, None, None, ModifiedFPN, use_gravity=True)` (main.py:236-246): `DefaultImageNetwork.__init__` calls

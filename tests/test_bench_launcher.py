@@ -98,7 +98,11 @@ def test_bench_eight_gloo_ranks_with_real_pipelines_on_one_gpu():
     """Width-8 rehearsal: the command the driver's scaling run issues, `bench.py --gpus 8`, with eight REAL pipelines -- weights,
     frame programs, three lanes each -- sharing the one GPU of the box over gloo (8 x ~6 GB).  No scaling claim follows from it; it takes "never ran
     at width 8 with a pipeline" off the list of things the 8-GPU run can trip over: spawn before any HIP call, rank-staggered GPU start, barriers
-    around the timed regions of eight ranks, the gather, `n_gpus == 8`, one line, eight per-rank logs."""
+    around the timed regions of eight ranks, the gather, `n_gpus == 8`, one line, eight per-rank logs.  Rank r takes GPU r mod the GPU
+    count: at most six processes may hold one GPU, so the eight ranks need eight GPUs."""
+    n_dev = torch.cuda.device_count()
+    if n_dev < 8:
+        pytest.skip("needs 8 GPUs (one rank per GPU; at most 6 processes may hold one GPU), found %d" % n_dev)
     log_dir = os.path.join(ROOT, "gpurun_out", "rank_logs_eight_gloo_ranks")
     cmd = [sys.executable, BENCH, "--gpus", "8", "--steps", "2", "--warmup", "1", "--regions", "2", "--no-cpu-baseline", "--no-extra-legs", "--no-mixed-leg",
            "--no-sequential-leg"]
@@ -231,3 +235,25 @@ def test_items_per_launch_default_follows_the_item_size(monkeypatch):
                        (["bench.py", "--batch", "4", "--frames-per-launch", "2"], 2)):
         monkeypatch.setattr(sys, "argv", argv)
         assert bench.parse().frames_per_launch == want, argv
+
+
+def test_dump_outputs_writes_float32_arrays_within_the_limit(monkeypatch, tmp_path):
+    """`--dump-outputs DIR`: the last timed step's arrays as DIR/<name>.npy in float32, 64 MB at most in all; `--steps` below 1 is refused."""
+    import importlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--dump-outputs", str(tmp_path / "out")])
+    args = bench.parse()
+    assert args.steps == 3 and args.dump_outputs == str(tmp_path / "out")
+    depth = np.random.RandomState(0).rand(1, 1, 256, 320)
+    shapes = bench.dump_outputs(args.dump_outputs, {"depth_fp32": depth})
+    assert shapes == {"depth_fp32": [1, 1, 256, 320]}
+    back = np.load(str(tmp_path / "out" / "depth_fp32.npy"))
+    assert back.dtype == np.float32 and np.array_equal(back, depth.astype(np.float32))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"a": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)})
+    assert not (tmp_path / "big").exists()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCRIPT = os.path.join(ROOT, "tools", "stale_read", "stress_pipeline.py")
 _STRIP = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "VIDC_LANES", "VIDC_FRAMES_PER_LAUNCH", "VIDC_EXEC", "VIDC_FUSE_WARP",
-          "VIDC_DBG_STEM_LOADS", "GPU_MAX_HW_QUEUES", "VIDC_PRECISION")
+          "VIDC_DBG_STEM_LOADS", "VIDC_PRECISION")
 
 
 def _stress(env, items, runs=2, lanes=3, F=4, timeout=900):
@@ -40,12 +40,6 @@ def _stress(env, items, runs=2, lanes=3, F=4, timeout=900):
 def test_default_path_2000_items_three_lanes_graphs_vs_one_lane_eager(precision):
     """The timed configuration (3 lanes, 4 items per launch, captured graphs): 2000 items x 2 runs, every depth map bit-equal to lanes=1 eager."""
     bad, out = _stress({"VIDC_PRECISION": precision}, items=2000, runs=2)
-    assert bad == 0, out
-
-
-@pytest.mark.parametrize("precision", ["fp32", "mixed"])
-def test_default_path_with_eight_hardware_queues(precision):
-    bad, out = _stress({"VIDC_PRECISION": precision, "GPU_MAX_HW_QUEUES": "8"}, items=1000, runs=2)
     assert bad == 0, out
 
 

@@ -78,9 +78,9 @@ def main():
         bad = [i for i, (x, y) in enumerate(zip(ref, got)) if not torch.equal(x, y)]
         total_bad += len(bad)
         detail = ", ".join("%d(n=%d max=%.1e)" % (i, int((ref[i] != got[i]).sum()), float((ref[i] - got[i]).abs().max())) for i in bad[:6])
-        print("STRESS run %d: lanes=%d F=%d items=%d exec=%s fuse_warp=%s stem_loads=%s hwq=%s: %d differing items [%s] (%.1f items/s; reference %s, %.1f s)"
+        print("STRESS run %d: lanes=%d F=%d items=%d exec=%s fuse_warp=%s stem_loads=%s: %d differing items [%s] (%.1f items/s; reference %s, %.1f s)"
               % (run, a.lanes, a.F, a.items, want_exec, os.environ.get("VIDC_FUSE_WARP", "0"), os.environ.get("VIDC_DBG_STEM_LOADS", "0"),
-                 os.environ.get("GPU_MAX_HW_QUEUES", "default"), len(bad), detail, a.items / dt, a.ref_exec, t_ref), flush=True)
+                 len(bad), detail, a.items / dt, a.ref_exec, t_ref), flush=True)
     print("STRESS total differing items: %d" % total_bad)
     return 1 if total_bad else 0
 

@@ -179,7 +179,7 @@ class DepthCompletionTrainer:
         # 3258 / 42.0 ms, but as ONE dependency chain (27.3-27.5 ms per step) against 25.9 ms for the three lanes, whose launch latencies
         # hide under each other -- on this runtime kernels of different streams fill each other's gaps, they do not add throughput.
         # Across ranks the step is cut into two graphs around the decoder's all-reduce, and there the three-lane form falls into the
-        # runtime's slow regime above 4 hardware queues (50.4 against 27.4 ms at GPU_MAX_HW_QUEUES=8) while the single-stream grouped chain
+        # runtime's slow regime above 4 hardware queues (50.4 against 27.4 ms at 8 queues) while the single-stream grouped chain
         # does not care (27.8 / 28.4 ms at 4 / 8 queues): the multi-rank default must not depend on a queue count nobody controls.
         mode = os.environ.get("VIDC_TRAIN_GROUPED", "auto")
         want = self._distributed() if mode == "auto" else mode == "1"
