@@ -95,6 +95,10 @@ enum vidc_conv_flags {
     VIDC_NO_F32_OUT = 128, /* with SPLIT_OUT: skip the fp32 store (nobody reads it)              */
     VIDC_X_PLANAR_GROUPS = 512, /* group g's input is a plane of its own (B*H*W rows of ldx values at x + g*x_gs) instead of a channel slice of
                               rows shared by all groups: the grouped weight-gradient GEMMs of the training step (dY^T of the three pyramids) */
+    VIDC_MXFP8_OUT = 1024, /* also write the MXFP8 image of the final result (after BN, ReLU, residual and accumulate) to y_split, in the
+                              layout vidc_quant_mxfp8 writes for C = Cout (a dense image with rows of Cout channels, one plane per group);
+                              with NO_F32_OUT the fp32 store is skipped.  VIDC_PREC_MXFP8 convs only (the other precisions' producers
+                              are followed by vidc_quant_mxfp8). */
     VIDC_STATS_OUT = 256   /* training, VIDC_PREC_BF16 only, no second affine / residual / accumulate / split output (with `groups` > 1 the rows of
                               the partials hold groups * Cout doubles, group-major like the channels of y):
                               `y_split` points to ceil(M / 32) x 2 x Cout doubles and receives, per block of 32 output rows, the
@@ -130,7 +134,8 @@ typedef struct vidc_conv_desc {
                               hi|lo bf16 images made by vidc_split_bf16x3 /
                               vidc_pack_conv_weight_bf16x3 (same strides as fp32)     */
     int32_t dilation;      /* tap spacing of the kernel (nn.Conv2d dilation); 0 or 1 = dense                  */
-    void* y_split;         /* split-bf16 image of y (VIDC_SPLIT_OUT), the channel-sum partials (VIDC_STATS_OUT), or NULL */
+    void* y_split;         /* split-bf16 image of y (VIDC_SPLIT_OUT), the MXFP8 image of y (VIDC_MXFP8_OUT), the channel-sum partials
+                              (VIDC_STATS_OUT), or NULL */
 } vidc_conv_desc;
 
 /* Workgroup tilings (BM x BN output tile; _Kn = n k-slices reduced inside the workgroup through LDS). */
@@ -177,7 +182,25 @@ enum vidc_conv_tile { VIDC_TILE_AUTO = 0, VIDC_TILE_128x128 = 1, VIDC_TILE_128x6
  * BF16 (the arithmetic BASELINE configs[4] names for training): plain bf16 operands (vidc_cast_bf16 / pack kinds 4, 5), fp32
  * accumulation, fp32 output.  128 bytes of a row are 64 bf16 channels, so the descriptor counts TWO channels per element:
  * Cin, ldx, x_gs = bf16 channels / 2 (Cin a multiple of 32, i.e. 64 bf16 channels), w_gs = Cout*KH*KW*Cin.  2 MFMAs per 16 k. */
-enum vidc_conv_precision { VIDC_PREC_FP32 = 0, VIDC_PREC_BF16X3 = 1, VIDC_PREC_BF16 = 2 };
+/* MXFP8 (OCP MX, block-scaled FP8): inference only, v_mfma_scale_f32_32x32x64_f8f6f4 with fp32 accumulation.
+ *   Element: OCP e4m3fn (not the MI300 fnuz encoding).  Every block of 32 consecutive K values (32 channels of one pixel, or 32
+ *   consecutive K of a packed weight row) has one E8M0 scale byte E + 127, with E = max(-127, floor(log2 amax) - 8), amax the block's
+ *   largest |x| (8 = e4m3's emax).  An all-zero block has E = -127 (byte 0); byte 0xFF is never written.  Element = x * 2^-E rounded to
+ *   nearest even to e4m3, saturated to +-448.  Value = element * 2^E.  Products of two e4m3 values are exact in fp32.
+ *   Tensor: ONE dense allocation per group, the data plane [rows][C] bytes immediately followed by the scale plane [rows][C/32] bytes.
+ *   A grouped activation is one such plane pair per group, `x_gs` floats apart; packed weights are [Cout][K] bytes + [Cout][K/32] per group.
+ *   Descriptor: like VIDC_PREC_BF16 it counts 128-byte row units, here four channels per element: Cin, ldx = channels / 4 (Cin a multiple
+ *   of 32, i.e. 128 channels; ldx a multiple of 32), x_gs = group plane bytes / 4, w_gs = Cout*KH*KW*Cin*33/32.  `x` and `w` point at data
+ *   planes; the kernel finds a scale plane behind its data plane (x: B*H*W rows of 4*ldx bytes; w: Cout rows of 4*KH*KW*Cin bytes).
+ *   Refused (VIDC_ERR_SHAPE): STATS_OUT, SPLIT_OUT, X_PLANAR_GROUPS, and the tilings of the measured table only (loader-wave, pipelined,
+ *   streamed and Winograd tiles, and the 128x128 tile, whose registers spill): VIDC_TILE_AUTO or tiles 2 .. 13. */
+enum vidc_conv_precision { VIDC_PREC_FP32 = 0, VIDC_PREC_BF16X3 = 1, VIDC_PREC_BF16 = 2, VIDC_PREC_MXFP8 = 3 };
+/* fp32 NHWC rows [rows][ldx] whose first groups * C channels are `groups` slices of C channels -> the MXFP8 image: per group g, the data
+ * plane [rows][C] e4m3 bytes at y + g * rows * C * 33 / 32, followed by its scale plane [rows][C / 32] (format above).  C % 128 == 0. */
+int vidc_quant_mxfp8(const float* x, void* y, long long rows, int C, int ldx, int groups, vidc_stream_t stream);
+/* OIHW fp32 -> MXFP8 packed weights: data [Cout][Cin/128][KH][KW][128] e4m3 bytes (the conv kernel's K order, 128 channels per unit),
+ * followed by the scales [Cout][K/32] (one per 32 consecutive K of a row); Cout * K * 33 / 32 bytes.  One group per call, Cin % 128 == 0. */
+int vidc_pack_conv_weight_mxfp8(const float* w_oihw, void* w_packed, int Cout, int Cin, int KH, int KW, vidc_stream_t stream);
 /* fp32 NHWC rows [rows][ldx] (first C channels) -> dense bf16 rows [rows][C] (round to nearest even); C % 8 == 0. */
 int vidc_cast_bf16(const float* x, void* y, long long rows, int C, int ldx, vidc_stream_t stream);
 /* fp32 NHWC rows [rows][ldx] (first C channels) -> split image [rows][C/32][hi|lo]; C % 32 == 0. */
@@ -616,7 +639,8 @@ enum vidc_op_kind { VIDC_OP_CONV = 1, VIDC_OP_STEM = 2, VIDC_OP_MAXPOOL = 3, VID
                     VIDC_OP_AVGPOOL = 11, VIDC_OP_NORMALIZE = 12, VIDC_OP_DET_IM2COL = 13, VIDC_OP_NEAREST2X = 14,
                     /* 15: retired (persistent conv chain, removed in round 5) */ VIDC_OP_MASK = 16 /* vidc_mask_scale: p = x, image, y; i = B,h,w,C,ldx,ldy,H,W */,
                     VIDC_OP_WINO_IN = 17  /* vidc_winograd_input_transform: p = x, v; i = B,H,W,C,ldx,Cin,m,split,ldv */,
-                    VIDC_OP_WINO_OUT = 18 /* vidc_winograd_output_transform: p = mm, y, y_split, scale1, shift1, scale2, shift2; i = B,Ho,Wo,C,Cout,ldy,m,flags,ldm */ };
+                    VIDC_OP_WINO_OUT = 18 /* vidc_winograd_output_transform: p = mm, y, y_split, scale1, shift1, scale2, shift2; i = B,Ho,Wo,C,Cout,ldy,m,flags,ldm */,
+                    VIDC_OP_QUANT = 19    /* vidc_quant_mxfp8: p = x, y; i = rows (lo, hi), C, ldx, groups */ };
 
 typedef struct vidc_generic_args {   /* arguments of the non-conv launchers, in declaration order */
     const void* p[8];

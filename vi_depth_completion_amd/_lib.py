@@ -19,9 +19,9 @@ MAX_SEGMENTS = 4
 CLOCK_STAMP_WGS = 8      # VIDC_CLOCK_STAMP_WGS
 
 # vidc_conv_flags / vidc_up_flags / vidc_op_kind / vidc_conv_tile
-RELU1, AFFINE2, RELU2, RESIDUAL, RELU3, ACCUM, SPLIT_OUT, NO_F32_OUT, STATS_OUT, X_PLANAR_GROUPS = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
+RELU1, AFFINE2, RELU2, RESIDUAL, RELU3, ACCUM, SPLIT_OUT, NO_F32_OUT, STATS_OUT, X_PLANAR_GROUPS, MXFP8_OUT = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024
 UP_RELU, UP_ACCUM, UP_NO_F32_OUT = 1, 2, 4
-OP_CONV, OP_STEM, OP_MAXPOOL, OP_UPSAMPLE, OP_HEAD, OP_WARP_PARAMS, OP_WARP_FWD, OP_WARP_INV, OP_COPY, OP_SPLIT, OP_AVGPOOL, OP_NORMALIZE, OP_DET_IM2COL, OP_NEAREST2X, _OP_RETIRED_15, OP_MASK, OP_WINO_IN, OP_WINO_OUT = range(1, 19)
+OP_CONV, OP_STEM, OP_MAXPOOL, OP_UPSAMPLE, OP_HEAD, OP_WARP_PARAMS, OP_WARP_FWD, OP_WARP_INV, OP_COPY, OP_SPLIT, OP_AVGPOOL, OP_NORMALIZE, OP_DET_IM2COL, OP_NEAREST2X, _OP_RETIRED_15, OP_MASK, OP_WINO_IN, OP_WINO_OUT, OP_QUANT = range(1, 20)
 TILE_AUTO = 0
 TILE_NAMES = {0: "auto", 1: "128x128", 2: "128x64", 3: "64x128", 4: "64x64", 5: "64x64k2", 6: "32x64k2", 7: "32x32k4", 8: "32x128",
               9: "32x32k8", 10: "32x64k2d5", 11: "32x32k4d4", 12: "32x128d6", 13: "64x64k2d4", 14: "32x64k2L", 15: "32x64k2d5L", 16: "32x32k4d4L", 17: "64x64L", 18: "64x64k2d4L",
@@ -30,7 +30,8 @@ TILE_NAMES = {0: "auto", 1: "128x128", 2: "128x64", 3: "64x128", 4: "64x64", 5: 
               33: "128x128d4P", 34: "128x128d3P", 35: "64x64d4P", 36: "128x64d4P", 37: "64x64k2d4P", 38: "64x32k2d5P", 39: "32x64k2d5P", 40: "g96x32s", 41: "g96x64s3", 42: "wino4f"}
 TILE_COUNT = 43
 TILE_WINO4_FUSED = 42
-PREC_FP32, PREC_BF16X3, PREC_BF16 = 0, 1, 2
+PREC_FP32, PREC_BF16X3, PREC_BF16, PREC_MXFP8 = 0, 1, 2, 3
+MXFP8_TILES = range(2, 14)         # the tilings with an MXFP8 instance (include/vidc.h)
 SPLITK_COUNTERS = 16384            # VIDC_SPLITK_COUNTERS: ticket counters at the head of a split-K workspace
 
 _f32p = C.POINTER(C.c_float)
@@ -82,6 +83,8 @@ SIGNATURES = {
     "vidc_pack_conv_weight": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "vidc_split_bf16x3": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _vp]),
     "vidc_pack_conv_weight_bf16x3": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "vidc_quant_mxfp8": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _i, _vp]),
+    "vidc_pack_conv_weight_mxfp8": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "vidc_conv2d_bn_act": (C.c_int, [C.POINTER(ConvDesc), _vp]),
     "vidc_conv2d_workspace_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
     "vidc_conv2d_plan": (C.c_int, [C.POINTER(ConvDesc)]),

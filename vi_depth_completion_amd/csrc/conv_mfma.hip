@@ -57,11 +57,30 @@ using vidc::store_split;
 // Zero source for LDS-DMA lanes whose row is padding (conv halo, M tail, Cout tail, K tail).
 __device__ float g_zero_chunk[64] = {0};
 
+// ---- MXFP8 (include/vidc.h: OCP e4m3fn elements, one E8M0 scale per 32 values) ------------------------------------------------
+// Integer / ldexp / rint arithmetic only: exact, the same on host and device, and nothing hipcc's SLP vectoriser could pack into the
+// v_pk_*_f32 forms of DESIGN 4.5.
+// scale exponent E = max(-127, floor(log2 amax) - 8) of a block with largest magnitude amax >= 0 (fp32 subnormals and 0 give -127)
+__host__ __device__ inline int mx_scale_exp(float amax) {
+    const int e = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 0xFFu) - 127 - 8;
+    return e < -127 ? -127 : e;
+}
+// e4m3fn byte of v * 2^-E: round to nearest even, saturated to +-448 (0x7E); the sign of v is kept (-0 for negative underflow)
+__host__ __device__ inline unsigned mx_e4m3(float v, int E) {
+    const unsigned sgn = (__builtin_bit_cast(unsigned, v) >> 24) & 0x80u;
+    const float a = fminf(fabsf(ldexpf(v, -E)), 448.f);
+    if (a < 0.015625f) return sgn | (unsigned)rintf(ldexpf(a, 9));          // below 2^-6: the subnormal grid 2^-9 (8 -> 0x08 = 2^-6)
+    const int e = (int)((__builtin_bit_cast(unsigned, a) >> 23) & 0xFFu) - 127;   // -6 .. 8
+    return sgn | (((unsigned)(e + 7) << 3) + ((unsigned)rintf(ldexpf(a, 3 - e)) - 8u));   // mantissa 8..16: 16 carries into the exponent
+}
+
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -114,6 +133,11 @@ __device__ __forceinline__ f32x4 lds_read_b128(unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
     return v;
 }
+__device__ __forceinline__ unsigned lds_read_b32(unsigned addr) {
+    unsigned v;
+    asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr));
+    return v;
+}
 
 // Workgroup = WMW x WNW x WKW waves.  The (WMW x WNW) waves of one k-slice tile the BM x BN output; the WKW k-slices
 // split every pipeline stage's K range (32 floats each) and are summed through LDS at the end (deterministic order).
@@ -130,6 +154,14 @@ __device__ __forceinline__ f32x4 lds_read_b128(unsigned addr) {
 // PREC 2 ("bf16", the training mode BASELINE configs[4] names): plain bf16 operands, fp32 accumulate.  A 128-byte unit of a row holds
 // 64 bf16 channels, so the caller describes the tensors in units of two channels (Cin, ldx = bf16 channels / 2, weights packed per 64
 // channels) and everything up to the fragment reads is unchanged; a K unit is 2 x 2 v_mfma_f32_32x32x16_bf16.
+// PREC 3 ("MXFP8", include/vidc.h): e4m3 operands with one E8M0 scale per 32 K, v_mfma_scale_f32_32x32x64_f8f6f4.  A 128-byte unit of a row
+// holds 128 channels (the descriptor counts four channels per element), so DMA, ring, swizzle and split-K addressing are those of fp32; a K
+// unit is 2 scaled MFMAs of 64 k.  Lane map (checked with exact integer data, tests/test_mxfp8.py): lane l holds A[l & 31][16h + j] for
+// j < 16 and A[l & 31][32 + 16h + j - 16] for j >= 16 (h = l >> 5; B alike with its column), i.e. the 16-byte chunks 4t + h and 4t + 2 + h of
+// MFMA t; the scale VGPR of lane-half h scales k block h (k 32h .. 32h + 31) of the lane's row / column, byte `opsel`.  The four scale bytes
+// of a row's unit (one dword) travel with the stage: one 4-byte LDS-DMA per wave per operand, 64 rows each, into an area behind the
+// stage's operand rows (padding rows and taps read zeros: scale 2^-127 times zero data).  Lanes of the upper half shift that dword by 8 so
+// that opsel 2t selects block 2t + h.
 // SPEC 1 ("loader waves"): the workgroup has NW extra waves that do nothing but the LDS-DMA of the NW compute waves (loader l
 // issues exactly what compute wave l would) and the compute waves issue no DMA at all.  A wave can issue one 1 KiB DMA per ~64 clk
 // and stalls in-order behind it, so in the small-tile kernels (6 DMAs per wave per 192 clk of MFMA) the DMA issue used to sit on
@@ -149,10 +181,15 @@ template <int BM, int BN, int WMW, int WNW, int WKW, int NS, int PREC, int SPEC>
 __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const int tile_m, const int tile_n, const int kz, float* smem) {
     constexpr int NW = WMW * WNW * WKW, WPK = WMW * WNW;
     constexpr int TM = BM / (32 * WMW), TN = BN / (32 * WNW);
-    constexpr int A_J = (BM / 8) / WPK, B_J = (BN / 8) / WPK;      // DMA instructions per wave per stage
-    constexpr int LPS = A_J + B_J;
-    constexpr int STAGE = (BM + BN) * BK * WKW;                    // floats per ring slot
+    constexpr bool MX = PREC == 3;
+    constexpr int SJ = MX ? 1 : 0;                                 // MXFP8: one scale DMA per wave per operand and stage
+    constexpr int A_J = (BM / 8) / WPK, B_J = (BN / 8) / WPK;      // operand-row DMA instructions per wave per stage
+    constexpr int A_JW = A_J + SJ;                                 // ... and all DMA instructions of an A group
+    constexpr int LPS = A_J + B_J + 2 * SJ;
+    constexpr int SOFF = (BM + BN) * BK * WKW;                     // operand rows of a ring slot, then (MXFP8) per k-slice 64 * WPK A and B scale dwords
+    constexpr int STAGE = SOFF + (MX ? 2 * 64 * WPK * WKW : 0);    // floats per ring slot
     static_assert((BM / 8) % WPK == 0 && (BN / 8) % WPK == 0, "tile rows must split evenly over the waves");
+    static_assert(!MX || (BM <= 64 * WPK && BN <= 64 * WPK), "MXFP8: one scale DMA per wave covers the tile's rows");
     static_assert(NS >= 2 && (NS - 2) * LPS <= 63, "vmcnt is a 6-bit counter");
     static_assert((WKW - 1) * WPK * TM * TN * 1024 <= NS * STAGE, "K-reduction scratch must fit in the ring");
 #ifdef VIDC_CONV_TIMING
@@ -167,7 +204,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
 
     const int tid = threadIdx.x;
     const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    constexpr int SPEC_EFF = (SPEC == 2 && PREC == 0) ? 1 : SPEC;      // the pipelined loop exists for the 16-k bf16 MFMAs only
+    constexpr int SPEC_EFF = (SPEC == 2 && (PREC == 0 || PREC == 3)) ? 1 : SPEC;      // the pipelined loop exists for the 16-k bf16 MFMAs only
     const bool is_loader = SPEC && wave_all >= NW;              // wave-uniform
     const bool loads = !SPEC || is_loader;                      // this wave issues DMA
     const int wave = is_loader ? wave_all - NW : wave_all;      // role-local index: loader l feeds what compute wave l would load
@@ -195,10 +232,23 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
     };
     // (VIDC_X_PLANAR_GROUPS: every group's input is a plane of its own with B*H*W rows of ldx values, x_gs apart -- the training step's grouped
     //  weight-gradient GEMMs; else the groups are channel slices of shared rows and a later group sees fewer bytes behind its base)
-    const int x_bytes = __builtin_amdgcn_readfirstlane((int)(((long long)a.B * a.H * a.W * a.ldx - ((a.flags & VIDC_X_PLANAR_GROUPS) ? 0 : g * a.x_gs)) * 4));
+    // (MXFP8: every group is a plane pair of its own -- data rows, then their scales -- so the data plane is planar too)
+    const long long x_rows = (long long)a.B * a.H * a.W;
+    const int x_bytes = __builtin_amdgcn_readfirstlane((int)((x_rows * a.ldx - ((MX || (a.flags & VIDC_X_PLANAR_GROUPS)) ? 0 : g * a.x_gs)) * 4));
     const int w_bytes = __builtin_amdgcn_readfirstlane((int)((long long)a.Cout * a.K * 4));
     const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.x + g * a.x_gs), 0, x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.w + g * a.w_gs), 0, w_bytes, 0x00020000);
+    // MXFP8 scale planes, right behind the data planes: x_rows rows of ldx / 8 bytes (4 * ldx channels / 32), Cout rows of K / 8 bytes
+    // (PREC 3 only: in the other precisions' kernels none of this is computed)
+    const int srs = MX ? a.ldx >> 3 : 0;
+    __amdgpu_buffer_rsrc_t xs_rsrc = x_rsrc, ws_rsrc = w_rsrc;
+    if constexpr (MX) {
+        xs_rsrc = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.x + g * a.x_gs + x_rows * a.ldx), 0,
+                                                    __builtin_amdgcn_readfirstlane((int)(x_rows * srs)), 0x00020000);
+        ws_rsrc = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.w + g * a.w_gs + (long long)a.Cout * a.K), 0,
+                                                    __builtin_amdgcn_readfirstlane((int)((long long)a.Cout * (a.K >> 3))), 0x00020000);
+    }
+    const int srow = wq * 64 + lane;                     // MXFP8: the tile row whose scale dword this lane fetches (A and B)
     const int lrow = lane >> 3;
     // swizzled 16-byte chunk (in floats) this lane fetches for the j-th DMA of a stage: tile row = ... + (j * WPK + wq) * 8 + lrow, all
     // other terms multiples of 32, so (row >> 1) & 7 = ((j * WPK + wq) & 1) * 4 + (lrow >> 1)
@@ -211,6 +261,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
         const int n = n0 + (j * WPK + wq) * 8 + lrow;
         b_off[j] = n < a.Cout ? (unsigned)((n * a.K + csw_of(j)) * 4) : OOB;
     }
+    const unsigned bs_off = (MX && srow < BN && n0 + srow < a.Cout) ? (unsigned)((n0 + srow) * (a.K >> 3)) : OOB;
     // K order: unit u = cu * (KH*KW) + tap -- channel unit major, tap minor -- so the KH*KW taps of one 32-channel unit run
     // back to back and the shifted re-reads of the same pixels hit L2 (tap-major order re-read every pixel KH*KW times with
     // ~10 MB of other traffic per XCD in between: 23x over-fetch measured on the 3x3, K=6912 layer).  This wave's unit
@@ -232,6 +283,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
                 float* dst = smem + s * STAGE + (WKW * BM + kq * BN + (j * WPK + wq) * 8) * BK;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_void_t*)dst, 16, (int)(b_off[j] + uoff), 0, 0, 0);
             }
+            if constexpr (MX) {
+                float* dst = smem + s * STAGE + SOFF + (kq * 2 + 1) * 64 * WPK + wq * 64;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(ws_rsrc, (lds_void_t*)dst, 4, (int)(bs_off + (ub < unit_end ? (unsigned)(ub * 4) : OOB)), 0, 0, 0);
+            }
             ub += WKW;
         }
     }
@@ -242,18 +297,13 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
     const int HoWo = a.Ho * a.Wo;
     const float inv_howo = 1.0f / (float)HoWo, inv_wo = 1.0f / (float)a.Wo;
     const bool pointwise = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;    // input pixel index == output pixel index
-#pragma unroll
-    for (int j = 0; j < A_J; ++j) { a_off[j] = 0; a_taps[j] = 0u; }
-#pragma unroll
-    for (int j = 0; j < A_J; ++j) {
-        if (!loads) break;                               // compute waves of a SPEC kernel never issue DMA
-        const int m = m0 + (j * WPK + wq) * 8 + lrow;
-        const bool ok = m < a.M;
+    // output row m -> input pixel index of its tap (0, 0) (may be negative) and the bit set of its taps that read a real pixel
+    auto decode = [&](int m, bool ok, int& pix, unsigned& taps_out) {
         const int mm = ok ? m : 0;
         if (pointwise) {
-            a_taps[j] = ok ? 1u : 0u;
-            a_off[j] = (mm * a.ldx + csw_of(j)) * 4;
-            continue;
+            taps_out = ok ? 1u : 0u;
+            pix = mm;
+            return;
         }
         int b = (int)((float)mm * inv_howo);             // float reciprocal + fix-up: exact for M < 2^23
         int rem = mm - b * HoWo;
@@ -267,8 +317,25 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
         for (int tw = 0; tw < 3; ++tw) colm |= (tw < a.KW && (unsigned)(ix0 + tw * a.dil) < (unsigned)a.W) ? 1u << tw : 0u;
 #pragma unroll
         for (int th = 0; th < 3; ++th) taps |= (th < a.KH && (unsigned)(iy0 + th * a.dil) < (unsigned)a.H) ? colm << (th * a.KW) : 0u;
-        a_taps[j] = ok ? taps : 0u;
-        a_off[j] = (((b * a.H + iy0) * a.W + ix0) * a.ldx + csw_of(j)) * 4;
+        taps_out = ok ? taps : 0u;
+        pix = (b * a.H + iy0) * a.W + ix0;
+    };
+#pragma unroll
+    for (int j = 0; j < A_J; ++j) { a_off[j] = 0; a_taps[j] = 0u; }
+#pragma unroll
+    for (int j = 0; j < A_J; ++j) {
+        if (!loads) break;                               // compute waves of a SPEC kernel never issue DMA
+        const int m = m0 + (j * WPK + wq) * 8 + lrow;
+        int pix;
+        decode(m, m < a.M, pix, a_taps[j]);
+        a_off[j] = (pix * a.ldx + csw_of(j)) * 4;
+    }
+    int as_off = 0;                                      // MXFP8: byte offset of the scale dword of this lane's row (pixel, tap (0,0), unit 0)
+    unsigned as_taps = 0u;
+    if (MX && loads) {
+        int pix;
+        decode(m0 + srow, srow < BM && m0 + srow < a.M, pix, as_taps);
+        as_off = pix * srs;
     }
     VIDC_STAMP(10);     // activation rows decoded
     // One pipeline stage = A_J + B_J DMA instructions per wave, issued in two halves that the main loop places inside
@@ -284,6 +351,12 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
             float* dst = sbase + (kq * BM + (j * WPK + wq) * 8) * BK;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (lds_void_t*)dst, 16, (int)voff, 0, 0, 0);
         }
+        if constexpr (MX) {
+            const int stap_off = ((kh * a.W + kw) * a.dil) * srs + cc * 4;
+            const unsigned voff = (as_taps & tapbit) ? (unsigned)(as_off + stap_off) : OOB;
+            float* dst = sbase + SOFF + kq * 2 * 64 * WPK + wq * 64;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xs_rsrc, (lds_void_t*)dst, 4, (int)voff, 0, 0, 0);
+        }
     };
     auto issue_b = [&](int slot) {
         float* sbase = smem + slot * STAGE;
@@ -292,6 +365,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
         for (int j = 0; j < B_J; ++j) {
             float* dst = sbase + (WKW * BM + kq * BN + (j * WPK + wq) * 8) * BK;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_void_t*)dst, 16, (int)(b_off[j] + uoff), 0, 0, 0);
+        }
+        if constexpr (MX) {
+            float* dst = sbase + SOFF + (kq * 2 + 1) * 64 * WPK + wq * 64;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ws_rsrc, (lds_void_t*)dst, 4, (int)(bs_off + (unit < unit_end ? (unsigned)(unit * 4) : OOB)), 0, 0, 0);
         }
     };
     // K position after one stage (this wave's unit advances by WKW): branch-free, so it can sit between the MFMAs of the loop
@@ -364,8 +441,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
             for (int s = 0; s < PRO; ++s) { issue_a(s); advance(); }
             int slot = 0;
             for (int s = 0; s < nst; ++s) {
-                if constexpr (SPEC_EFF == 2) wait_landed<NS, A_J, LPS>(s + 1 < nst ? s + 1 : nst - 1, s, nst);      // ... and stage s + 1
-                else wait_stage<NS, A_J, LPS>(s, nst);
+                if constexpr (SPEC_EFF == 2) wait_landed<NS, A_JW, LPS>(s + 1 < nst ? s + 1 : nst - 1, s, nst);      // ... and stage s + 1
+                else wait_stage<NS, A_JW, LPS>(s, nst);
                 __builtin_amdgcn_s_barrier();     // stage s is in LDS (every loader waited for its pieces); stage s-1 has been read
                 int fill = slot + NS - 1; if (fill >= NS) fill -= NS;
                 if (s < n_main) { issue_a(fill); issue_b(fill); advance(); }
@@ -399,13 +476,61 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
         // DMA issue order: prologue B_0..B_{PRO-1}, A_0..A_{PRO-1}, then per iteration A, B.  Stage s < PRO has landed when
         // only the (PRO-1-s) younger prologue A groups and the s stages issued by the loop remain; from s = PRO on, when at
         // most NS-2 whole stages remain.
-        if constexpr (!SPEC) wait_stage<NS, A_J, LPS>(s, nst);      // SPEC: the loader waves wait for their DMA before this barrier
+        if constexpr (!SPEC) wait_stage<NS, A_JW, LPS>(s, nst);      // SPEC: the loader waves wait for their DMA before this barrier
         __builtin_amdgcn_s_barrier();     // every wave's pieces of stage s are in LDS; everyone finished stage s-1
         if (s == 0) VIDC_STAMP(2);      // first stage landed
         int fill = slot + NS - 1; if (fill >= NS) fill -= NS;     // the slot read in iteration s-1: free since the barrier
         const unsigned Ab = a_base + (unsigned)(slot * STAGE * 4);
         const unsigned Bb = b_base + (unsigned)(slot * STAGE * 4);
-        if constexpr (PREC != 0) {
+        if constexpr (MX) {
+            // the scale dwords of this lane's A rows / B columns, then per MFMA t the chunks 4t + lh and 4t + 2 + lh of every fragment
+            const unsigned As = lds0 + 4u * (unsigned)(slot * STAGE + SOFF + kq * 2 * 64 * WPK + wm * 32 * TM + li);
+            const unsigned Bs = As + 4u * (unsigned)(64 * WPK - wm * 32 * TM + wn * 32 * TN);
+            unsigned sa[TM], sb[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) sa[i] = lds_read_b32(As + i * 128);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) sb[j] = lds_read_b32(Bs + j * 128);
+            f32x4 a0[2][TM], a1[2][TM], b0[2][TN], b1[2][TN];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const unsigned c0 = (unsigned)(((4 * t + lh) ^ sw) * 16), c1 = (unsigned)(((4 * t + 2 + lh) ^ sw) * 16);
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+                    a0[t][i] = lds_read_b128<0>(Ab + c0 + i * 32 * BK * 4);
+                    a1[t][i] = lds_read_b128<0>(Ab + c1 + i * 32 * BK * 4);
+                }
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    b0[t][j] = lds_read_b128<0>(Bb + c0 + j * 32 * BK * 4);
+                    b1[t][j] = lds_read_b128<0>(Bb + c1 + j * 32 * BK * 4);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                if (t == 0) wait_lgkmcnt<2 * (TM + TN)>(); else wait_lgkmcnt<0>();
+                __builtin_amdgcn_sched_barrier(0);
+                if (t == 0) {
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) sa[i] >>= (unsigned)(lh << 3);      // opsel 2t then selects block 2t + lh
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) sb[j] >>= (unsigned)(lh << 3);
+                }
+#ifndef VIDC_DBG_SKIP_DMA
+                if constexpr (decltype(issue_tag)::value && !SPEC) { if (t == 0) issue_a(fill); else { issue_b(fill); advance(); } }   // among the MFMAs
+#endif
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        const i32x8 xa = __builtin_shufflevector(__builtin_bit_cast(i32x4, a0[t][i]), __builtin_bit_cast(i32x4, a1[t][i]), 0, 1, 2, 3, 4, 5, 6, 7);
+                        const i32x8 xb = __builtin_shufflevector(__builtin_bit_cast(i32x4, b0[t][j]), __builtin_bit_cast(i32x4, b1[t][j]), 0, 1, 2, 3, 4, 5, 6, 7);
+                        if (t == 0) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(xa, xb, acc[i][j], 0, 0, 0, (int)sa[i], 0, (int)sb[j]);
+                        else        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(xa, xb, acc[i][j], 0, 0, 2, (int)sa[i], 2, (int)sb[j]);
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else if constexpr (PREC != 0) {
             // logical 16-byte chunks of a row's unit: 0..3 = hi (k 0-7, 8-15, 16-23, 24-31), 4..7 = lo; MFMA t covers
             // k 16t..16t+15 with lanes 0-31 supplying the first and lanes 32-63 the second 8 k.
             f32x4 ah[2][TM], al[2][TM], bh[2][TN], bl[2][TN];
@@ -577,8 +702,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
     const float lo2 = (a.flags & VIDC_RELU2) ? 0.f : -INFINITY;
     const float lo3 = (a.flags & VIDC_RELU3) ? 0.f : -INFINITY;
     const bool aff2 = a.flags & VIDC_AFFINE2, has_res = a.flags & VIDC_RESIDUAL, accum = a.flags & VIDC_ACCUM;
-    const bool st_f32 = !(a.flags & VIDC_NO_F32_OUT), st_split = a.flags & VIDC_SPLIT_OUT;
+    const bool st_f32 = !(a.flags & VIDC_NO_F32_OUT), st_split = a.flags & VIDC_SPLIT_OUT, st_mx = MX && (a.flags & VIDC_MXFP8_OUT);
     unsigned short* ysp = st_split ? a.y_split + (size_t)g * a.y_gs * 2 : nullptr;
+    // VIDC_MXFP8_OUT: this group's plane pair of the image, data [M][Cout] bytes then scales [M][Cout / 32]
+    unsigned char* ymx = st_mx ? reinterpret_cast<unsigned char*>(a.y_split) + (size_t)g * a.M * a.Cout / 32 * 33 : nullptr;
     double* stats_out = (PREC == 2 && (a.flags & VIDC_STATS_OUT)) ? reinterpret_cast<double*>(a.y_split) : nullptr;
 #ifndef VIDC_CONV_TIMING
     // ---- split-K without a second launch: every k-slice workgroup stores its fp32 partial tile, takes a ticket on the tile's
@@ -716,6 +843,21 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
                     for (int r = 0; r < 16; ++r) {
                         const int dm = (r & 3) + 8 * (r >> 2);
                         if (FULL || mrow + dm < a.M) store_split(ysp, (size_t)(mrow + dm), a.ldy, n, v[r]);
+                    }
+                }
+                if constexpr (MX) if (st_mx) {
+                    // one register = one row's 32 channels nb .. nb + 31 on the 32 lanes of a half: the block's amax is a 5-step butterfly
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float am = fabsf(v[r]);
+#pragma unroll
+                        for (int o = 1; o < 32; o <<= 1) am = fmaxf(am, __shfl_xor(am, o));
+                        const int E = mx_scale_exp(am);
+                        const int m = mrow + (r & 3) + 8 * (r >> 2);
+                        if (FULL || m < a.M) {
+                            ymx[(size_t)m * a.Cout + n] = (unsigned char)mx_e4m3(v[r], E);
+                            if (li == 0) ymx[(size_t)a.M * a.Cout + (size_t)m * (a.Cout >> 5) + (nb >> 5)] = (unsigned char)(E + 127);
+                        }
                     }
                 }
             };
@@ -864,7 +1006,7 @@ constexpr int kFirstLoaderTile = VIDC_TILE_32x64_K2_L;
 template <int BM, int BN, int WMW, int WNW, int WKW, int NS, int PREC, int SPEC>
 int launch_tile_p(const ConvArgs& a, hipStream_t st) {
     constexpr int NT = 64 * WMW * WNW * WKW * (SPEC ? 2 : 1);
-    constexpr size_t lds = (size_t)NS * (BM + BN) * BK * WKW * sizeof(float);
+    constexpr size_t lds = (size_t)NS * ((BM + BN) * BK * WKW + (PREC == 3 ? 2 * 64 * WMW * WNW * WKW : 0)) * sizeof(float);
     static bool attr_set[64] = {};   // per device (the attribute is per device function); benign race: idempotent
     int dev = 0;
     VIDC_HIP(hipGetDevice(&dev));
@@ -879,8 +1021,13 @@ int launch_tile_p(const ConvArgs& a, hipStream_t st) {
     return VIDC_OK;
 }
 
-template <int BM, int BN, int WMW, int WNW, int WKW, int NS, int SPEC = 0>
+// MX: the tiling has an MXFP8 instance (validate() refuses precision 3 for the others)
+template <int BM, int BN, int WMW, int WNW, int WKW, int NS, int SPEC = 0, bool MX = false>
 int launch_tile(const ConvArgs& a, hipStream_t st, int precision) {
+    if constexpr (MX) {
+        if (precision == VIDC_PREC_MXFP8) return launch_tile_p<BM, BN, WMW, WNW, WKW, NS, 3, SPEC>(a, st);
+    }
+    VIDC_REQUIRE(precision != VIDC_PREC_MXFP8, VIDC_ERR_SHAPE, "conv: no MXFP8 instance of this tiling");
     return precision == VIDC_PREC_BF16X3 ? launch_tile_p<BM, BN, WMW, WNW, WKW, NS, 1, SPEC>(a, st)
            : precision == VIDC_PREC_BF16 ? launch_tile_p<BM, BN, WMW, WNW, WKW, NS, 2, SPEC>(a, st)
                                          : launch_tile_p<BM, BN, WMW, WNW, WKW, NS, 0, SPEC>(a, st);
@@ -906,13 +1053,23 @@ int validate(const vidc_conv_desc* d) {
     VIDC_REQUIRE(!(d->flags & VIDC_AFFINE2) || (d->scale2 && d->shift2), VIDC_ERR_NULL, "conv: AFFINE2 without scale2/shift2");
     VIDC_REQUIRE(!(d->flags & VIDC_RESIDUAL) || (d->residual && d->ldr >= d->Cout), VIDC_ERR_NULL, "conv: RESIDUAL without tensor");
     VIDC_REQUIRE(d->tile >= 0 && d->tile < VIDC_TILE_COUNT, VIDC_ERR_SHAPE, "conv: unknown tile id %d", d->tile);
-    VIDC_REQUIRE(d->precision == VIDC_PREC_FP32 || d->precision == VIDC_PREC_BF16X3 || d->precision == VIDC_PREC_BF16, VIDC_ERR_SHAPE,
-                 "conv: unknown precision %d", d->precision);
+    VIDC_REQUIRE(d->precision == VIDC_PREC_FP32 || d->precision == VIDC_PREC_BF16X3 || d->precision == VIDC_PREC_BF16 || d->precision == VIDC_PREC_MXFP8,
+                 VIDC_ERR_SHAPE, "conv: unknown precision %d", d->precision);
+    if (d->precision == VIDC_PREC_MXFP8) {      // (Cin, ldx count four channels: Cin % 32 above = 128 channels)
+        VIDC_REQUIRE(d->ldx % 32 == 0, VIDC_ERR_SHAPE, "conv: MXFP8 needs ldx = a multiple of 128 channels (ldx %% 32 == 0), got %d", d->ldx);
+        VIDC_REQUIRE(!(d->flags & (VIDC_STATS_OUT | VIDC_SPLIT_OUT | VIDC_X_PLANAR_GROUPS)), VIDC_ERR_SHAPE,
+                     "conv: MXFP8 does not support STATS_OUT, SPLIT_OUT or X_PLANAR_GROUPS");
+        VIDC_REQUIRE(d->tile == VIDC_TILE_AUTO || (d->tile > VIDC_TILE_128x128 && d->tile <= VIDC_TILE_64x64_K2_D4), VIDC_ERR_SHAPE,
+                     "conv: MXFP8 runs the tilings 2 .. 13 only (no loader-wave, pipelined, streamed or Winograd tile), got %d", d->tile);
+    }
+    VIDC_REQUIRE(!(d->flags & VIDC_MXFP8_OUT) || (d->precision == VIDC_PREC_MXFP8 && d->y_split), VIDC_ERR_SHAPE,
+                 "conv: MXFP8_OUT needs VIDC_PREC_MXFP8 and y_split");
     VIDC_REQUIRE(d->precision != VIDC_PREC_BF16 || !(d->flags & VIDC_SPLIT_OUT), VIDC_ERR_SHAPE, "conv: SPLIT_OUT writes the bf16x3 format, not plain bf16");
     VIDC_REQUIRE(d->splitk == 1 || d->workspace || d->tile == VIDC_TILE_G96x32_STREAM || d->tile == VIDC_TILE_G96x64_STREAM3, VIDC_ERR_NULL, "conv: split-K needs a workspace");
     VIDC_REQUIRE(!(d->flags & VIDC_SPLIT_OUT) || (d->y_split && d->Cout % 32 == 0 && d->ldy % 32 == 0), VIDC_ERR_NULL,
                  "conv: SPLIT_OUT needs y_split and Cout, ldy multiples of 32");
-    VIDC_REQUIRE(!(d->flags & VIDC_NO_F32_OUT) || (d->flags & VIDC_SPLIT_OUT), VIDC_ERR_SHAPE, "conv: NO_F32_OUT without SPLIT_OUT writes nothing");
+    VIDC_REQUIRE(!(d->flags & VIDC_NO_F32_OUT) || (d->flags & (VIDC_SPLIT_OUT | VIDC_MXFP8_OUT)), VIDC_ERR_SHAPE,
+                 "conv: NO_F32_OUT without SPLIT_OUT / MXFP8_OUT writes nothing");
     VIDC_REQUIRE(!(d->flags & VIDC_STATS_OUT) || (d->precision == VIDC_PREC_BF16 && d->y_split &&
                                                   !(d->flags & (VIDC_AFFINE2 | VIDC_RESIDUAL | VIDC_ACCUM | VIDC_SPLIT_OUT | VIDC_NO_F32_OUT))),
                  VIDC_ERR_SHAPE, "conv: STATS_OUT needs VIDC_PREC_BF16, y_split = the partials buffer and a plain epilogue");
@@ -966,6 +1123,7 @@ extern "C" int vidc_conv2d_plan(vidc_conv_desc* d) {
     double best = 1e30;
     int best_tile = VIDC_TILE_64x64, best_sk = 1;
     for (int t = 1; t < kFirstLoaderTile; ++t) {      // loader-wave variants are chosen by the measured table only
+        if (t == VIDC_TILE_128x128 && d->precision == VIDC_PREC_MXFP8) continue;      // (no MXFP8 instance: its registers spill)
         const TileInfo ti = kTiles[t];
         if (ti.bn > d->Cout && ti.bn > 64) continue;
         const long long tm = (M + ti.bm - 1) / ti.bm, tn = (d->Cout + ti.bn - 1) / ti.bn;
@@ -1006,19 +1164,19 @@ extern "C" int vidc_conv2d_bn_act(const vidc_conv_desc* d, vidc_stream_t stream)
     if (rc != VIDC_OK) return rc;
     hipStream_t st = vidc::as_stream(stream);
     switch (dd.tile) {
-        case VIDC_TILE_128x128:  rc = launch_tile<128, 128, 2, 2, 1, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_128x64:   rc = launch_tile<128, 64, 2, 2, 1, 3>(a, st, dd.precision); break;
-        case VIDC_TILE_64x128:   rc = launch_tile<64, 128, 2, 2, 1, 3>(a, st, dd.precision); break;
-        case VIDC_TILE_64x64:    rc = launch_tile<64, 64, 2, 2, 1, 4>(a, st, dd.precision); break;
-        case VIDC_TILE_64x64_K2: rc = launch_tile<64, 64, 2, 2, 2, 3>(a, st, dd.precision); break;
-        case VIDC_TILE_32x64_K2: rc = launch_tile<32, 64, 1, 2, 2, 3>(a, st, dd.precision); break;
-        case VIDC_TILE_32x32_K4: rc = launch_tile<32, 32, 1, 1, 4, 3>(a, st, dd.precision); break;
-        case VIDC_TILE_32x128:   rc = launch_tile<32, 128, 1, 4, 1, 4>(a, st, dd.precision); break;
-        case VIDC_TILE_32x32_K8: rc = launch_tile<32, 32, 1, 1, 8, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_32x64_K2_D5: rc = launch_tile<32, 64, 1, 2, 2, 5>(a, st, dd.precision); break;
-        case VIDC_TILE_32x32_K4_D4: rc = launch_tile<32, 32, 1, 1, 4, 4>(a, st, dd.precision); break;
-        case VIDC_TILE_32x128_D6:   rc = launch_tile<32, 128, 1, 4, 1, 6>(a, st, dd.precision); break;
-        case VIDC_TILE_64x64_K2_D4: rc = launch_tile<64, 64, 2, 2, 2, 4>(a, st, dd.precision); break;
+        case VIDC_TILE_128x128:  rc = launch_tile<128, 128, 2, 2, 1, 2>(a, st, dd.precision); break;      // (MXFP8: spills, no instance)
+        case VIDC_TILE_128x64:   rc = launch_tile<128, 64, 2, 2, 1, 3, 0, true>(a, st, dd.precision); break;
+        case VIDC_TILE_64x128:   rc = launch_tile<64, 128, 2, 2, 1, 3, 0, true>(a, st, dd.precision); break;
+        case VIDC_TILE_64x64:    rc = launch_tile<64, 64, 2, 2, 1, 4, 0, true>(a, st, dd.precision); break;
+        case VIDC_TILE_64x64_K2: rc = launch_tile<64, 64, 2, 2, 2, 3, 0, true>(a, st, dd.precision); break;
+        case VIDC_TILE_32x64_K2: rc = launch_tile<32, 64, 1, 2, 2, 3, 0, true>(a, st, dd.precision); break;
+        case VIDC_TILE_32x32_K4: rc = launch_tile<32, 32, 1, 1, 4, 3, 0, true>(a, st, dd.precision); break;
+        case VIDC_TILE_32x128:   rc = launch_tile<32, 128, 1, 4, 1, 4, 0, true>(a, st, dd.precision); break;
+        case VIDC_TILE_32x32_K8: rc = launch_tile<32, 32, 1, 1, 8, 2, 0, true>(a, st, dd.precision); break;
+        case VIDC_TILE_32x64_K2_D5: rc = launch_tile<32, 64, 1, 2, 2, 5, 0, true>(a, st, dd.precision); break;
+        case VIDC_TILE_32x32_K4_D4: rc = launch_tile<32, 32, 1, 1, 4, 4, 0, true>(a, st, dd.precision); break;
+        case VIDC_TILE_32x128_D6:   rc = launch_tile<32, 128, 1, 4, 1, 6, 0, true>(a, st, dd.precision); break;
+        case VIDC_TILE_64x64_K2_D4: rc = launch_tile<64, 64, 2, 2, 2, 4, 0, true>(a, st, dd.precision); break;
         case VIDC_TILE_32x64_K2_L:     rc = launch_tile<32, 64, 1, 2, 2, 3, 1>(a, st, dd.precision); break;
         case VIDC_TILE_32x64_K2_D5_L:  rc = launch_tile<32, 64, 1, 2, 2, 5, 1>(a, st, dd.precision); break;
         case VIDC_TILE_32x32_K4_D4_L:  rc = launch_tile<32, 32, 1, 1, 4, 4, 1>(a, st, dd.precision); break;
@@ -1081,5 +1239,69 @@ extern "C" int vidc_pack_conv_weight(const float* w_oihw, float* w_packed, int C
     hipLaunchKernelGGL(pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, vidc::as_stream(stream), w_oihw,
                        w_packed, Cout, Cin, KH, KW);
     VIDC_CHECK_LAUNCH("pack_weight_kernel");
+    return VIDC_OK;
+}
+
+// ---- MXFP8 operand preparation (format: include/vidc.h) -----------------------------------------------------------------------
+namespace {
+// one lane per value: a 32-lane half of a wave is one block (32 channels of one row of one group), its amax a 5-step butterfly
+__global__ void __launch_bounds__(256) quant_mxfp8_kernel(const float* __restrict__ x, unsigned char* __restrict__ y, long long rows, int C,
+                                                          int ldx, int groups) {
+    const long long per_row = (long long)C * groups;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= rows * per_row) return;      // whole waves: rows * per_row is a multiple of 128
+    const long long r = idx / per_row;
+    const int cg = (int)(idx - r * per_row), g = cg / C, c = cg - g * C;
+    const float v = x[r * ldx + cg];
+    float am = fabsf(v);
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) am = fmaxf(am, __shfl_xor(am, o));
+    const int E = mx_scale_exp(am);
+    unsigned char* plane = y + (size_t)g * rows * C / 32 * 33;
+    plane[r * C + c] = (unsigned char)mx_e4m3(v, E);
+    if ((c & 31) == 0) plane[rows * C + r * (C >> 5) + (c >> 5)] = (unsigned char)(E + 127);
+}
+
+// one thread per 32-value block of a packed row: wp[o][k] for k = ((c / 128) * taps + tap) * 128 + c % 128, then the scales [Cout][K / 32]
+__global__ void __launch_bounds__(256) pack_weight_mxfp8_kernel(const float* __restrict__ w, unsigned char* __restrict__ wp, int Cout, int Cin,
+                                                                int KH, int KW) {
+    const int K = Cin * KH * KW, nb = K / 32, taps = KH * KW;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)Cout * nb) return;
+    const int o = (int)(idx / nb), kb = (int)(idx - (long long)o * nb);
+    const int u = kb >> 2, cu = u / taps, tap = u - cu * taps, kh = tap / KW, kw = tap - kh * KW, c0 = cu * 128 + (kb & 3) * 32;
+    float v[32];
+    float am = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        v[i] = w[(((long long)o * Cin + c0 + i) * KH + kh) * KW + kw];
+        am = fmaxf(am, fabsf(v[i]));
+    }
+    const int E = mx_scale_exp(am);
+    unsigned char* row = wp + (long long)o * K + kb * 32;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) row[i] = (unsigned char)mx_e4m3(v[i], E);
+    wp[(long long)Cout * K + idx] = (unsigned char)(E + 127);
+}
+}  // namespace
+
+extern "C" int vidc_quant_mxfp8(const float* x, void* y, long long rows, int C, int ldx, int groups, vidc_stream_t stream) {
+    VIDC_REQUIRE(x && y, VIDC_ERR_NULL, "vidc_quant_mxfp8: null pointer");
+    VIDC_REQUIRE(rows > 0 && C > 0 && C % 128 == 0 && groups >= 1 && ldx >= C * groups, VIDC_ERR_SHAPE,
+                 "vidc_quant_mxfp8: C must be a multiple of 128 and ldx >= groups * C");
+    const long long n = rows * C * groups;
+    hipLaunchKernelGGL(quant_mxfp8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, vidc::as_stream(stream), x,
+                       reinterpret_cast<unsigned char*>(y), rows, C, ldx, groups);
+    VIDC_CHECK_LAUNCH("quant_mxfp8_kernel");
+    return VIDC_OK;
+}
+
+extern "C" int vidc_pack_conv_weight_mxfp8(const float* w_oihw, void* w_packed, int Cout, int Cin, int KH, int KW, vidc_stream_t stream) {
+    VIDC_REQUIRE(w_oihw && w_packed, VIDC_ERR_NULL, "vidc_pack_conv_weight_mxfp8: null pointer");
+    VIDC_REQUIRE(Cout > 0 && Cin > 0 && Cin % 128 == 0 && KH > 0 && KW > 0, VIDC_ERR_SHAPE, "vidc_pack_conv_weight_mxfp8: Cin must be a multiple of 128");
+    const long long blocks = (long long)Cout * (Cin * KH * KW / 32);
+    hipLaunchKernelGGL(pack_weight_mxfp8_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, vidc::as_stream(stream), w_oihw,
+                       reinterpret_cast<unsigned char*>(w_packed), Cout, Cin, KH, KW);
+    VIDC_CHECK_LAUNCH("pack_weight_mxfp8_kernel");
     return VIDC_OK;
 }

@@ -76,16 +76,18 @@ class WeightStore:
 
     def packed(self, keys, dry_run=False, precision=0):
         """[G][Cout][KH][KW][Cin] fp32 (precision 0) or the split-bf16 image of the same bytes (precision 1), packed by
-        the C kernels."""
+        the C kernels; precision 3: [G][Cout * K * 33 / 32 bytes], the MXFP8 images (include/vidc.h) in float32-typed storage."""
         ck = ("w", precision) + tuple(keys)
         if ck not in self._cache:
             ws = [self.sd()[k + ".weight"].contiguous() for k in keys]
             co, ci, kh, kw = ws[0].shape
-            out = torch.empty((len(ws), co, kh * kw * ci), dtype=torch.float32, device=ws[0].device)
+            per_group = kh * kw * ci if precision != L.PREC_MXFP8 else kh * kw * ci // 128 * 33
+            out = torch.empty((len(ws), co, per_group), dtype=torch.float32, device=ws[0].device)
             for g, w in enumerate(ws):
                 assert tuple(w.shape) == (co, ci, kh, kw)
                 if not dry_run:
-                    fn = L.lib().vidc_pack_conv_weight_bf16x3 if precision == L.PREC_BF16X3 else L.lib().vidc_pack_conv_weight
+                    fn = {L.PREC_BF16X3: L.lib().vidc_pack_conv_weight_bf16x3,
+                          L.PREC_MXFP8: L.lib().vidc_pack_conv_weight_mxfp8}.get(precision, L.lib().vidc_pack_conv_weight)
                     L.check(fn(L.ptr(w), L.ptr(out[g]), co, ci, kh, kw, L.current_stream()), "pack")
             if dry_run:
                 return out
@@ -193,12 +195,26 @@ def tuning_table():
 def precision_mode():
     """VIDC_PRECISION=fp32  : every conv on fp32 MFMA (exact fp32; the reference mode).
        VIDC_PRECISION=mixed : (default) compute-bound convs run split-bf16 3-pass MFMA (per-shape choice from the measured
-                              table, else by size); whole-path depth RMSE vs fp32 ~1.4e-5, bar 1e-3."""
+                              table, else by size); whole-path depth RMSE vs fp32 ~1.4e-5, bar 1e-3.
+       VIDC_PRECISION=mxfp8 : the direct convs that mxfp8_layer() selects run block-scaled FP8 (VIDC_PREC_MXFP8, include/vidc.h);
+                              every other layer makes exactly the choice of the mixed mode."""
     return os.environ.get("VIDC_PRECISION", "mixed")
 
 
 def default_precision(flops):
     return L.PREC_BF16X3 if flops >= 1.5e9 else L.PREC_FP32
+
+
+MXFP8_MIN_FLOPS = 1e8       # below this a layer is launch-bound: the FP8 rate buys nothing and the quantisation costs a launch
+# layers kept out of MXFP8 for accuracy (key substrings; DESIGN 4.6 lists the sets measured): ResNet-101 layer 1 and the FPN decoders
+# with the convs in front of the heads -- the pyramid's layers 2-4 run in MXFP8
+MXFP8_EXCLUDED = ("layer1.", "_upsamping.", "feature_concat.")
+
+
+def mxfp8_layer(key, co, ci, flops):
+    """Whether the direct conv `key` runs in MXFP8 in the mxfp8 mode: 128-channel K units (Cin % 128), whole 32-channel output tiles,
+    enough work (FLOPs of the launch, all groups), and not one of the layers MXFP8_EXCLUDED keeps out for accuracy."""
+    return ci % 128 == 0 and co % 32 == 0 and flops >= MXFP8_MIN_FLOPS and not any(e in key for e in MXFP8_EXCLUDED)
 
 
 # LDS bytes of the tilings (NS * (BM + BN) * 32 floats * WKW) and, for the co-residency experiment, the nearest tiling of at most 80 KB
@@ -219,11 +235,15 @@ def winograd_mode():
     return os.environ.get("VIDC_WINOGRAD", "auto")
 
 
-def winograd_choice(B, H, W, co, ci, kh, kw, stride, padding, dilation, G, mode=None, precision=None):
-    if (kh, kw, stride, padding, dilation) != (3, 3, 1, 1, 1) or ci % 32 or co % 32:
+def winograd_choice(B, H, W, co, ci, kh, kw, stride, padding, dilation, G, mode=None, precision=None, mxfp8=False):
+    """mxfp8: the caller runs this layer in MXFP8 (Program.conv, mxfp8_layer): no Winograd -- the transforms amplify the quantisation
+    error, and the direct form is what the FP8 rate pays for.  Every other layer of the mxfp8 mode takes the mixed mode's choice."""
+    if mxfp8 or (kh, kw, stride, padding, dilation) != (3, 3, 1, 1, 1) or ci % 32 or co % 32:
         return 0
     mode = mode if mode is not None else winograd_mode()
     precision = precision if precision is not None else precision_mode()
+    if precision == "mxfp8":
+        precision = "mixed"
     if mode in ("0", "2", "4"):
         m = int(mode)
     else:
@@ -260,7 +280,7 @@ class Program:
     """Records ops symbolically (buffers are integers), then `finalize()` plans memory and builds the C program."""
 
     def __init__(self, weights, device, batch, reuse_buffers=True, mode=None, winograd=None):
-        """mode: "fp32" | "mixed" (default: precision_mode()); winograd: "0" | "2" | "4" | "auto" (default: winograd_mode()) -- a program whose
+        """mode: "fp32" | "mixed" | "mxfp8" (default: precision_mode()); winograd: "0" | "2" | "4" | "auto" (default: winograd_mode()) -- a program whose
         results feed DECISIONS (the plane-mask detector: score / IoU / mask thresholds) is recorded with mode="fp32", winograd="0": exact
         fp32 direct-form sums, the arithmetic its oracle pins."""
         self.ws, self.device, self.B = weights, device, batch
@@ -277,6 +297,7 @@ class Program:
         self.ref_flops = 0       # the same layers in the reference's formulation (1x1 convs AFTER their upsample: SURVEY §8d)
         self._keep = []
         self._split_cache = {}   # (buf, ch_off, channels) -> buffer id of the split-bf16 image
+        self._quant_cache = {}   # (buf, ch_off, channels, groups) -> the MXFP8 image (T)
         self.cuts = []           # op indices where a new segment starts (see cut()); filled by finalize()
         self._cut_markers = []
         self.mode = mode if mode is not None else precision_mode()
@@ -315,6 +336,11 @@ class Program:
     def on_stream(self, sid, wait_mask=0):
         self.stream_id, self.wait_mask = sid, wait_mask
 
+    def _written(self, t):
+        """t's buffer is (re)written: its split / MXFP8 images are stale."""
+        self._split_cache = {k: v for k, v in self._split_cache.items() if k[0] != t.buf}
+        self._quant_cache = {k: v for k, v in self._quant_cache.items() if k[0] != t.buf}
+
     def _emit(self, kind, reads, writes, **kw):
         kw.update(stream_id=self.stream_id, wait_mask=self.wait_mask)
         self.wait_mask = 0
@@ -333,7 +359,7 @@ class Program:
         Wo = (x.W + 2 * padding - dilation * (kw - 1) - 1) // stride + 1
         y = out if out is not None else self.nhwc(Ho, Wo, co, G)
         assert (y.H, y.W, y.C, y.G) == (Ho, Wo, co, G)
-        self._split_cache = {k: v for k, v in self._split_cache.items() if k[0] != y.buf}     # y is (re)written
+        self._written(y)     # y is (re)written
         flags = (L.RELU1 if relu else 0) | (L.AFFINE2 if bn2 is not None else 0) | (L.RELU2 if relu2 else 0)
         if residual is not None:
             assert (residual.H, residual.W, residual.C, residual.G) == (Ho, Wo, co, G)
@@ -341,9 +367,10 @@ class Program:
         if accumulate:
             flags |= L.ACCUM
         flops = 2 * self.B * Ho * Wo * co * ci * kh * kw * G
+        mx = self.mode == "mxfp8" and mxfp8_layer(keys[0], co, ci, flops)
         wm = 0
         if residual is None and not accumulate:
-            wm = winograd_choice(self.B, x.H, x.W, co, ci, kh, kw, stride, padding, dilation, G, mode=self.winograd, precision=self.mode)
+            wm = winograd_choice(self.B, x.H, x.W, co, ci, kh, kw, stride, padding, dilation, G, mode=self.winograd, precision=self.mode, mxfp8=mx)
         if wm:
             self.ref_flops += int(round(flops * ref_flops_scale))
             self.direct_flops += flops
@@ -362,10 +389,12 @@ class Program:
         # precision: measured table entry if there is one, else by size
         sig = "M%d_N%d_K%d_k%ds%d_G%d" % (self.B * Ho * Wo, co, kh * kw * ci, kh, stride, G)
         prec = L.PREC_FP32
-        if self.mode == "mixed":
+        if mx:
+            prec = L.PREC_MXFP8
+        elif self.mode in ("mixed", "mxfp8"):
             ent = tuning_table().get(sig)
             prec = ent[2] if (ent is not None and len(ent) > 2) else default_precision(flops)
-        xin = self.split(x) if prec == L.PREC_BF16X3 else x
+        xin = self.split(x) if prec == L.PREC_BF16X3 else (self.quant(x) if prec == L.PREC_MXFP8 else x)
         self._emit("conv", [xin, residual, y if accumulate else None], [y], x=xin, y=y, keys=keys, precision=prec,
                    bn=_keys(bn) if bn is not None else None, bn2=_keys(bn2) if bn2 is not None else None,
                    residual=residual, flags=flags, stride=stride, pad=padding, geom=(co, ci, kh, kw, Ho, Wo), dilation=dilation)
@@ -382,7 +411,7 @@ class Program:
         self.flops += gflops
         sig = "M%d_N%d_K%d_k1s1_G%d" % (tiles, co, ci, a2 * G)
         prec = L.PREC_FP32
-        if self.mode == "mixed":
+        if self.mode in ("mixed", "mxfp8"):
             ent = tuning_table().get(sig)
             prec = ent[2] if (ent is not None and len(ent) > 2) else default_precision(gflops)
         V = T(self._new_buf(tiles * a2 * G * ci), 1, 1, tiles, ci, a2 * G)
@@ -421,6 +450,18 @@ class Program:
         # same storage, the caller's view of it (grouped and channel-concatenated views share one split image)
         sbuf, ld0 = self._split_cache[ck]
         return T(sbuf, x.B, x.H, x.W, x.C, x.G, ld=ld0)
+
+    def quant(self, x):
+        """MXFP8 image of an fp32 activation tensor (include/vidc.h: per group a data plane of rows of x.C e4m3 bytes, then its scale
+        plane), made once per tensor; as a program tensor its buffer holds G * rows * C * 33 / 32 bytes and `ld` = C."""
+        ck = (x.buf, x.ch_off, x.C, x.G)
+        if ck not in self._quant_cache:
+            assert not x.nchw and x.C % 128 == 0
+            rows = x.B * x.H * x.W
+            y = T(self._new_buf(-(-x.G * rows * x.C * 33 // 128)), x.B, x.H, x.W, x.C, x.G, ld=x.C)
+            self._emit("quant", [x], [y], x=x, y=y)
+            self._quant_cache[ck] = y
+        return self._quant_cache[ck]
 
     def linear(self, x, key, relu=False):
         """nn.Linear on `x.view(B, -1)` of the reference's NCHW tensor (surface_normal_dorn.py:23-24), as a 1x1 conv over the
@@ -499,13 +540,13 @@ class Program:
         groups are added up, group 0 first -- z2 + z3 + z4 of the decoders in one launch."""
         if sum_groups:
             assert into is not None and x.G > 1 and (into.H, into.W, into.C * into.G) == (size[0], size[1], x.C)
-            self._split_cache = {k: v for k, v in self._split_cache.items() if k[0] != into.buf}
+            self._written(into)
             self._emit("upsample", [x, into], [into], x=x, y=into, flags=(L.UP_RELU if relu else 0) | L.UP_ACCUM | (x.G << 8), sum_groups=x.G)
             return into
         y = into if into is not None else (out if out is not None else self.nhwc(size[0], size[1], x.C, x.G))
         assert (y.H, y.W, y.C * y.G) == (size[0], size[1], x.C * x.G)
         flags = (L.UP_RELU if relu else 0) | (L.UP_ACCUM if into is not None else 0)
-        self._split_cache = {k: v for k, v in self._split_cache.items() if k[0] != y.buf}
+        self._written(y)
         self._emit("upsample", [x, into], [y], x=x, y=y, flags=flags)
         return y
 
@@ -586,7 +627,8 @@ class Program:
             for t in writers:
                 yt = self.ops[t][3]["y"]
                 ok = ok and yt.ld == xs.ld and yt.ch_off % 32 == 0 and (yt.C * yt.G) % 32 == 0 and lo <= yt.ch_off and \
-                    yt.ch_off + yt.C * yt.G <= hi and self.ops[t][3].get("split_out") is None
+                    yt.ch_off + yt.C * yt.G <= hi and self.ops[t][3].get("split_out") is None and \
+                    self.ops[t][3].get("precision") != L.PREC_MXFP8          # (an MXFP8 conv writes no split image)
                 cover.append((yt.ch_off, yt.ch_off + yt.C * yt.G))
             cover.sort()
             ok = ok and cover[0][0] == lo and cover[-1][1] == hi and all(cover[k][1] == cover[k + 1][0] for k in range(len(cover) - 1))
@@ -614,6 +656,38 @@ class Program:
                     else:
                         kw["no_f32"] = True
         self.n_fused_splits = len(drop)
+        self.ops = [op for i, op in enumerate(self.ops) if i not in drop]
+
+    def _fuse_quants(self):
+        """A quant op whose input is the whole output of one MXFP8 conv is folded into that conv (VIDC_MXFP8_OUT: its epilogue writes
+        the image); when nothing else reads the fp32 result the conv does not store it (VIDC_NO_F32_OUT).  Every other producer -- the
+        max-pool, an upsample, Winograd outputs, the stem, a conv of another precision, several producers of one tensor, a channel
+        slice -- is followed by the stand-alone quant launch."""
+        n = len(self.ops)
+        drop = set()
+        for i, (kind, _r, _w, kw) in enumerate(self.ops):
+            if kind != "quant":
+                continue
+            xs = kw["x"]
+            writers = [t for t in range(i) if xs.buf in self.ops[t][2]]
+            if len(writers) != 1 or self.ops[writers[0]][0] != "conv":
+                continue
+            j = writers[0]
+            pk = self.ops[j][3]
+            y = pk["y"]
+            if pk["precision"] != L.PREC_MXFP8 or pk.get("mx_out") is not None or y.buf != xs.buf or \
+                    (y.ch_off, y.C, y.G, y.ld) != (xs.ch_off, xs.C, xs.G, xs.ld) or y.ch_off != 0 or y.ld != y.C * y.G:
+                continue
+            pk["mx_out"] = kw["y"]
+            pk["flags"] |= L.MXFP8_OUT
+            self.ops[j][2].append(kw["y"].buf)
+            drop.add(i)
+        for j, (kind, _r, _w, kw) in enumerate(self.ops):
+            if kind == "conv" and kw.get("mx_out") is not None and kw["y"].buf not in self.pinned:
+                yb = kw["y"].buf
+                if not any(t not in drop and yb in self.ops[t][1] for t in range(j + 1, n)):
+                    kw["flags"] |= L.NO_F32_OUT
+        self.n_fused_quants = len(drop)
         self.ops = [op for i, op in enumerate(self.ops) if i not in drop]
 
     def _fuse_warp_into_stem(self):
@@ -674,6 +748,8 @@ class Program:
         d.flags, d.groups = kw["flags"], len(keys)
         if kw.get("split_out") is not None:
             d.y_split = addr(kw["split_out"])
+        if kw.get("mx_out") is not None:
+            d.y_split = addr(kw["mx_out"])
         d.x_gs, d.w_gs, d.y_gs, d.p_gs = x.C, co * kh * kwid * ci, y.C, co
         if wm:          # (m+2)^2 transform-domain GEMMs per group of the layer, identity epilogue shared by all of them
             d.groups, d.p_gs = len(keys) * (wm + 2) * (wm + 2), 0
@@ -683,6 +759,19 @@ class Program:
             d.w_gs, d.tile = 36 * co * ci, L.TILE_WINO4_FUSED
             self._keep += [wp, s1, b1]
             return "conv:%s@wino4f:%s:sk1:fp32 M%d_N%d_K%d_k1s1_G%d flags=0x%x" % (keys[0], L.TILE_NAMES[d.tile], wf, co, ci, 36 * len(keys), d.flags)
+        if prec == L.PREC_MXFP8:
+            # four channels per descriptor element, every group a plane pair of its own (include/vidc.h); no measured MXFP8 entries yet:
+            # the planner's tiling (VIDC_FORCE_TILE where it names an MXFP8 tiling)
+            assert x.ch_off == 0 and x.ld == ci
+            d.Cin, d.ldx = ci // 4, ci // 4
+            d.x_gs, d.w_gs = x.B * x.H * x.W * ci // 128 * 33, co * kh * kwid * ci // 128 * 33
+            forced = int(os.environ.get("VIDC_FORCE_TILE", "0"))
+            if forced in L.MXFP8_TILES:
+                d.tile, d.splitk = forced, 1
+            else:
+                L.check(lib.vidc_conv2d_plan(C.byref(d)), "conv plan")
+            self._keep += [wp, s1, b1]
+            return "conv:%s:%s:sk%d:mxfp8 %s flags=0x%x" % (keys[0], L.TILE_NAMES[d.tile], d.splitk, sig, d.flags)
         if os.environ.get("VIDC_FORCE_TILE"):           # (tests / A-B runs: one tiling for every conv)
             d.tile, d.splitk = int(os.environ["VIDC_FORCE_TILE"]), 1
         else:
@@ -750,6 +839,7 @@ class Program:
             self.n_fused_warps = 0
         if os.environ.get("VIDC_FUSE_SPLIT", "1") == "1":
             self._fuse_splits()
+            self._fuse_quants()
         self.cuts = [next(i for i, op in enumerate(self.ops) if op is mk) + 1 for mk in self._cut_markers]
         assert len(self.cuts) < L.MAX_SEGMENTS and self.cuts == sorted(set(self.cuts))
         storage = self._plan_buffers()
@@ -848,6 +938,13 @@ class Program:
                 g.p[0], g.p[1] = addr(x), addr(y)
                 g.i[0], g.i[1], g.i[2], g.i[3] = rows & 0xFFFFFFFF, rows >> 32, x.C * x.G, x.ld
                 self.op_names.append("split:%dx%d" % (rows, x.C * x.G))
+            elif kind == "quant":
+                x, y = kw["x"], kw["y"]
+                rows = x.B * x.H * x.W
+                op.kind = L.OP_QUANT
+                g.p[0], g.p[1] = addr(x), addr(y)
+                g.i[0], g.i[1], g.i[2], g.i[3], g.i[4] = rows & 0xFFFFFFFF, rows >> 32, x.C, x.ld, x.G
+                self.op_names.append("quant:%dx%dx%d" % (rows, x.C, x.G))
             elif kind == "avgpool":
                 x, y = kw["x"], kw["y"]
                 op.kind = L.OP_AVGPOOL
@@ -993,7 +1090,7 @@ class Program:
                 continue
             grouped = (kind in ("conv", "wino_out") and len(kw["keys"]) == groups) or (kind in ("maxpool", "wino_in") and kw["x"].G == groups)
             # (a split launch of its own -- VIDC_FUSE_SPLIT=0 -- over a grouped tensor has no row stride for its image: it runs whole in every variant)
-            if grouped or keep_ungrouped or (kind == "split" and kw["x"].G == groups):
+            if grouped or keep_ungrouped or (kind in ("split", "quant") and kw["x"].G == groups):
                 picked.append(i)
         ops = (L.Op * len(picked))()
         for j, i in enumerate(picked):
@@ -1005,6 +1102,8 @@ class Program:
                 for field, gs in (("x", d.x_gs), ("w", d.w_gs), ("y", d.y_gs), ("scale1", d.p_gs), ("shift1", d.p_gs), ("scale2", d.p_gs),
                                   ("shift2", d.p_gs), ("residual", d.r_gs), ("y_split", d.y_gs)):     # every operand is 4 bytes per element
                     v = getattr(d, field)                                                              # (a split-bf16 unit = 32 x (hi, lo))
+                    if field == "y_split" and d.flags & L.MXFP8_OUT:                                  # (MXFP8 image: one plane pair per group)
+                        gs = d.B * d.Ho * d.Wo * d.Cout * 33 // 128
                     if v:
                         setattr(d, field, v + 4 * g_lo * gs * a2)
                 d.groups = (g_hi - g_lo) * a2

@@ -47,22 +47,52 @@ def split_bf16x3(x_nhwc):
     return out
 
 
+def pack_conv_weight_mxfp8(w_oihw):
+    """OIHW fp32 -> MXFP8 packed weights (include/vidc.h): uint8 (Cout * K * 33 / 32,), the e4m3 rows then their scale bytes."""
+    _dev(w_oihw)
+    w = w_oihw.contiguous().float()
+    co, ci, kh, kw = w.shape
+    out = torch.empty(co * kh * kw * ci // 32 * 33, dtype=torch.uint8, device=w.device)
+    L.check(L.lib().vidc_pack_conv_weight_mxfp8(L.ptr(w), L.ptr(out), co, ci, kh, kw, L.current_stream()), "pack_conv_weight_mxfp8")
+    return out
+
+
+def quant_mxfp8(x_nhwc, groups=1):
+    """fp32 NHWC (..., G*C) -> MXFP8 image (include/vidc.h): uint8 (G * rows * C * 33 / 32,), per group the e4m3 rows then their scales."""
+    _dev(x_nhwc)
+    x = x_nhwc.contiguous().float()
+    ld = x.shape[-1]
+    rows = x.numel() // ld
+    out = torch.empty(rows * ld // 32 * 33, dtype=torch.uint8, device=x.device)
+    L.check(L.lib().vidc_quant_mxfp8(L.ptr(x), L.ptr(out), rows, ld // groups, ld, groups, L.current_stream()), "quant_mxfp8")
+    return out
+
+
 def conv2d_bn_act(x, w_packed, scale1, shift1, kh, kw, stride=1, pad=0, relu1=False, scale2=None, shift2=None, relu2=False,
                   residual=None, relu3=False, accumulate_into=None, tile=0, splitk=1, groups=1, precision=0, split_out=None,
-                  no_f32_out=False, workspace=None):
+                  no_f32_out=False, workspace=None, dilation=1, mx_out=None):
     """x: NHWC (B,H,W,G*Cin) contiguous; w_packed: (G,Cout,kh*kw*Cin) or (Cout,K); returns NHWC (B,Ho,Wo,G*Cout).
     precision=1 (bf16x3): x is split here; w_packed must come from pack_conv_weight_bf16x3.
+    precision=3 (MXFP8): x is quantised here; w_packed: the pack_conv_weight_mxfp8 images of the G groups, concatenated.
+    mx_out: uint8 tensor of G * B*Ho*Wo * Cout * 33 / 32 bytes receiving the MXFP8 image of the result (VIDC_MXFP8_OUT).
     workspace: optional persistent split-K scratch (float32, zero-initialised once by the caller; include/vidc.h)."""
     _dev(x, w_packed, scale1, shift1)
     x = x.contiguous()
-    if precision == L.PREC_BF16X3:
-        x = split_bf16x3(x)
     B, H, W, ld = x.shape
     G = groups
     cin = ld // G
-    wp = w_packed.contiguous().view(G, -1, kh * kw * cin)
-    cout = wp.shape[1]
-    Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+    if precision == L.PREC_BF16X3:
+        x = split_bf16x3(x)
+    elif precision == L.PREC_MXFP8:
+        x = quant_mxfp8(x, G)
+    if precision == L.PREC_MXFP8:
+        wp = w_packed.contiguous()
+        cout = wp.numel() // G // (kh * kw * cin // 32 * 33)
+        assert wp.numel() == G * cout * kh * kw * cin // 32 * 33
+    else:
+        wp = w_packed.contiguous().view(G, -1, kh * kw * cin)
+        cout = wp.shape[1]
+    Ho, Wo = (H + 2 * pad - dilation * (kh - 1) - 1) // stride + 1, (W + 2 * pad - dilation * (kw - 1) - 1) // stride + 1
     y = accumulate_into if accumulate_into is not None else torch.empty((B, Ho, Wo, G * cout), dtype=torch.float32, device=x.device)
     d = L.ConvDesc()
     d.x, d.w, d.y = L.ptr(x), L.ptr(wp), L.ptr(y)
@@ -84,10 +114,18 @@ def conv2d_bn_act(x, w_packed, scale1, shift1, kh, kw, stride=1, pad=0, relu1=Fa
     if split_out is not None:       # float32-typed tensor of y's shape receiving the split-bf16 image of the result
         d.y_split = L.ptr(split_out)
         flags |= L.SPLIT_OUT | (L.NO_F32_OUT if no_f32_out else 0)
+    if mx_out is not None:
+        assert mx_out.dtype == torch.uint8 and mx_out.numel() >= G * B * Ho * Wo * cout // 32 * 33
+        d.y_split = L.ptr(mx_out)
+        flags |= L.MXFP8_OUT | (L.NO_F32_OUT if no_f32_out else 0)
     d.B, d.H, d.W, d.Cin, d.ldx = B, H, W, cin, ld
     d.Ho, d.Wo, d.Cout, d.ldy = Ho, Wo, cout, G * cout
     d.KH, d.KW, d.stride, d.pad, d.flags, d.groups = kh, kw, stride, pad, flags, G
+    d.dilation = dilation
     d.x_gs, d.w_gs, d.y_gs, d.p_gs = cin, cout * kh * kw * cin, cout, (cout if s1.numel() >= G * cout else 0)      # (one affine for all groups: p_gs = 0)
+    if precision == L.PREC_MXFP8:       # four channels per descriptor element; every group a plane pair of its own (include/vidc.h)
+        d.Cin, d.ldx = cin // 4, cin // 4
+        d.x_gs, d.w_gs = B * H * W * cin // 128 * 33, cout * kh * kw * cin // 128 * 33
     d.tile, d.splitk, d.precision = tile, splitk, precision
     if tile == 0:
         L.check(L.lib().vidc_conv2d_plan(C.byref(d)), "conv2d_plan")

@@ -69,8 +69,9 @@ def _(x, gravity, aligned, fx, fy, cx, cy, align_corners, normalize):
 def conv2d_bn_act(x_nhwc: torch.Tensor, w_oihw: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, stride: int, pad: int,
                   relu: bool, precision: int) -> torch.Tensor:
     """relu?(conv(x, w) * scale + shift) on NHWC activations; scale/shift = the folded bias + eval-mode BatchNorm
-    (engine.fold_bn); precision 0 = exact fp32 MFMA, 1 = bf16x3 (vidc_conv_precision)."""
-    pack = _ops.pack_conv_weight_bf16x3 if precision == 1 else _ops.pack_conv_weight
+    (engine.fold_bn); precision 0 = exact fp32 MFMA, 1 = bf16x3, 3 = MXFP8: the fp32 input is quantised and the weights packed
+    block-scaled, the output is fp32 (vidc_conv_precision)."""
+    pack = {1: _ops.pack_conv_weight_bf16x3, 3: _ops.pack_conv_weight_mxfp8}.get(precision, _ops.pack_conv_weight)
     return _ops.conv2d_bn_act(x_nhwc, pack(w_oihw), scale, shift, w_oihw.shape[2], w_oihw.shape[3], stride=stride, pad=pad,
                               relu1=relu, precision=precision)
 
