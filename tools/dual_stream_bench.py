@@ -2,7 +2,7 @@
 """Experiment: TWO software-pipelined frame streams (pipeline.run_interleaved) on two HIP streams of one GPU, even / odd frames, so that
 the fixed cost of one stream's launches (dispatch, prologue, split-K epilogue, drain: ~9 of the ~14 us of a small-layer launch) can
 hide under the other stream's main loops.  Workgroups of the default tilings reserve 96-128 KB of LDS, so two kernels rarely share a
-CU; VIDC_LDS_CAP_KB=80 swaps in <= 80 KB tilings.
+CU (VIDC_TUNING_OVERRIDE can put smaller tilings in for an A/B run).
 
     python tools/dual_stream_bench.py --frames 200 [--streams 2]
 """
@@ -67,8 +67,7 @@ def main():
     t0 = time.perf_counter()
     n = run(a.frames)
     dt = time.perf_counter() - t0
-    print(json.dumps({"streams": a.streams, "frames": n, "fps": round(n / dt, 1), "ms_per_frame": round(1e3 * dt / n, 3),
-                      "lds_cap_kb": os.environ.get("VIDC_LDS_CAP_KB")}))
+    print(json.dumps({"streams": a.streams, "frames": n, "fps": round(n / dt, 1), "ms_per_frame": round(1e3 * dt / n, 3)}))
 
 
 if __name__ == "__main__":

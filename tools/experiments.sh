@@ -10,58 +10,17 @@ python -m pytest tests/test_hip_parity.py -x -q -k "lanes_are_bit_identical or f
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > gpurun_out/r3/expb/bench20.json
 python -c "import json; d=json.load(open('gpurun_out/r3/expb/bench20.json')); print('20 steps:', d['value'], d['value_fp32'], d['sequential_call_cnn'], d['fp32_leg']['sequential_call_cnn'])"
 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-sequential-leg 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('200 steps:', d['value'], d['value_fp32'])"
-R2="6:28,10:28,4:29,7:30,11:30,21:32,22:32"
-for remap in "25:1,24:1" "25:1,24:1,$R2" "25:1,24:1,2:29,20:29,17:29,19:31,3:31,$R2"; do
-  for lanes in 2 3; do
-    VIDC_TILE_REMAP=$remap python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-sequential-leg --no-fp32-leg --lanes $lanes 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('mixed remap=$remap lanes $lanes:', d['value'], d['program_ms'])"
-  done
-done
 VIDC_TRAIN_PRECISION=bf16 python bench.py --train --batch 8 --steps 5 --warmup 3 2>/dev/null | tail -1 | cut -c1-600
 python tools/dump_config2_detections.py gpurun_out/r3/config2_det.npz 2>&1 | tail -1
 }
 
 r3_c() {
-mkdir -p gpurun_out/r3/expc; O=$PWD/gpurun_out/r3/expc; R=$PWD
 python -m pytest tests/test_training.py -x -q -m gpu 2>&1 | tail -3
 for w in 1 0 1 0; do
   VIDC_TRAIN_WGRAD_STREAM=$w VIDC_TRAIN_PRECISION=bf16 python bench.py --train --batch 8 --steps 10 --warmup 3 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('bf16 wgrad side stream $w:', d['ms_per_step'], d['value'], d['losses'][-2:])"
 done
 for w in 1 0; do
   VIDC_TRAIN_WGRAD_STREAM=$w VIDC_TRAIN_PRECISION=fp32 python bench.py --train --batch 8 --steps 5 --warmup 3 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('fp32 wgrad side stream $w:', d['ms_per_step'], d['value'], d['losses'][-2:])"
-done
-cd /tmp; export TMPDIR=/tmp
-for remap in "" "25:33"; do
-  tag=$(echo "x$remap" | tr ':' '_')
-  VIDC_TILE_REMAP=$remap VIDC_EXEC=eager rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $O/pmc_$tag -o f --output-format csv -- python3 $R/tools/frame_replay.py 20 > $O/pmc_$tag.log 2>&1
-  python3 - <<PY
-import csv, collections
-per=collections.defaultdict(lambda: [0.0,0.0,0.0,0])
-for r in csv.DictReader(open("$O/pmc_$tag/f_counter_collection.csv")):
-    n=r["Kernel_Name"]
-    if "128, 128" not in n: continue
-    k=n.split("(")[0].replace("(anonymous namespace)::","").replace("void ","")
-    c=r["Counter_Name"]; v=float(r["Counter_Value"])
-    if c=="SQ_VALU_MFMA_BUSY_CYCLES": per[k][0]+=v
-    if c=="GRBM_GUI_ACTIVE": per[k][1]+=v; per[k][2]+=(int(r["End_Timestamp"])-int(r["Start_Timestamp"]))/1e3; per[k][3]+=1
-for k,(b,g,us,n) in per.items():
-    print("remap '$remap':", k, "launches", n, "avg us %.1f" % (us/max(n,1)), "MFMA busy %.1f %%" % (100*b/(g/8*1024)))
-PY
-done
-}
-
-r3_d2() {
-# round 3 experiment: 2-deep-ring tiles (32-48 KB of LDS, >= 3 workgroups per CU) swapped in for the table's choices, one to three lanes
-python -m pytest tests/test_hip_parity.py -q -x -k "conv_tiles and (28- or 29- or 30- or 31- or 32-)" 2>&1 | tail -2
-run() { python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-sequential-leg --no-fp32-leg --lanes $1 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$VIDC_PRECISION remap=$VIDC_TILE_REMAP lanes $1:', d['value'], d['program_ms'])"; }
-R1="6:28,10:28"
-R2="6:28,10:28,4:29,7:30,11:30,21:32,22:32"
-R3="6:28,10:28,4:29,7:30,11:30,21:32,22:32,3:31"
-for prec in fp32 mixed; do
-  export VIDC_PRECISION=$prec
-  for remap in "" "$R1" "$R2" "$R3"; do
-    export VIDC_TILE_REMAP=$remap
-    for lanes in 1 2 3; do run $lanes; done
-  done
 done
 }
 
@@ -71,17 +30,6 @@ python -m pytest tests/test_hip_parity.py tests/test_configs.py tests/test_dorn.
 run() { python bench.py --steps $1 --warmup 5 --no-cpu-baseline --no-sequential-leg 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('early=$VIDC_EARLY_SECOND_FRAME steps $1:', d['value'], d['value_fp32'])"; }
 for rep in 1 2 3 4; do for e in 0 1; do export VIDC_EARLY_SECOND_FRAME=$e; run 20; done; done
 for e in 0 1; do export VIDC_EARLY_SECOND_FRAME=$e; run 200; done
-}
-
-r3_lds_cap() {
-mkdir -p gpurun_out/r3/exp1
-export VIDC_PRECISION=fp32
-for lanes in 2 3; do
-  python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-sequential-leg --lanes $lanes 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('cap none lanes $lanes', d['value'], d['program_ms'])"
-  for cap in 80 64; do
-    VIDC_LDS_CAP_KB=$cap python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-sequential-leg --lanes $lanes 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('cap $cap lanes $lanes', d['value'], d['program_ms'])"
-  done
-done
 }
 
 r3_pipelined() {
@@ -515,6 +463,6 @@ done; done
 }
 
 case "$1" in
-  list|"") echo "experiments: r4_hw_queues r4_rccl_group r4_items_and_lanes r4_four_items r4_schedulers_f1 r4_waves3 r3_b r3_c r3_d2 r3_early r3_lds_cap r3_pipelined r3_plane_side r3_prefetch r3_train_add r3_train_bnadd r3_train_dyt r3_train_pack r3_train_retune r3_train_skip r3_train_tail r3_train_tickets r3_train_timeline r3_train_xt r3_train_xt3 r3_tune_b2 r3_tune_b8 r3_tune_b8_lanes r3_tune_detector r3_tune_fp32 r3_tune_fp32_again r3_tune_mixed r3_variants r3_xb r4_bnfold r4_lanes r4_newtests r4_pairing r4_perop r4_stagger r4_timeline" ;;
+  list|"") echo "experiments: r4_hw_queues r4_rccl_group r4_items_and_lanes r4_four_items r4_schedulers_f1 r4_waves3 r3_b r3_c r3_early r3_pipelined r3_plane_side r3_prefetch r3_train_add r3_train_bnadd r3_train_dyt r3_train_pack r3_train_retune r3_train_skip r3_train_tail r3_train_tickets r3_train_timeline r3_train_xt r3_train_xt3 r3_tune_b2 r3_tune_b8 r3_tune_b8_lanes r3_tune_detector r3_tune_fp32 r3_tune_fp32_again r3_tune_mixed r3_variants r3_xb r4_bnfold r4_lanes r4_newtests r4_pairing r4_perop r4_stagger r4_timeline" ;;
   *) name="$1"; shift; if declare -F "$name" > /dev/null; then "$name" "$@"; else echo "unknown experiment $name (bash tools/experiments.sh list)"; exit 2; fi ;;
 esac

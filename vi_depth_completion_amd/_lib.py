@@ -58,6 +58,73 @@ class ConvDesc(C.Structure):
     ]
 
 
+# ---- descriptor builder: the conventions of vidc_conv_desc (include/vidc.h) are written here and nowhere else ---------------
+def conv_desc(B, H, W, Cin, Cout, KH=1, KW=1, stride=1, pad=0, dilation=1, groups=1, Ho=None, Wo=None, ldx=None, ldy=None,
+              precision=PREC_FP32, x=None, w=None, y=None, scale1=None, shift1=None, shared_affine=False, scale2=None, shift2=None,
+              relu1=False, relu2=False, residual=None, ldr=None, relu3=False, accumulate=False, split_out=None, mx_out=None,
+              stats_out=None, no_f32_out=False, wino_fused=False):
+    """The vidc_conv_desc of a direct conv (include/vidc.h:110-139), or with wino_fused of the same 3x3 / stride 1 / pad 1 conv as the
+    one-launch Winograd F(4x4, 3x3) (VIDC_TILE_WINO4_FUSED, vidc.h:169-174).  Without pointers it describes the geometry only.
+
+    Geometry in channels, whatever the precision: Cin / Cout per group, ldx / ldy the row strides of x and y (default: groups * Cin /
+    Cout; an MXFP8 x is `groups` planes of Cin channels), ldr the residual's (default ldy).  Pointers are ints or None.  The epilogue:
+    scale1 / shift1 [groups][Cout], or one [Cout] pair for every group (shared_affine); scale2 / shift2 with relu2 (AFFINE2, RELU2);
+    residual with relu3; accumulate; one image of the result in y_split: split_out (split bf16), mx_out (MXFP8) or stats_out (the
+    channel-sum partials of VIDC_STATS_OUT).  no_f32_out skips the fp32 store behind split_out / mx_out.
+    tile = AUTO, splitk = 1 (plan() chooses them), except the fused Winograd form's own tile."""
+    assert sum(p is not None for p in (split_out, mx_out, stats_out)) <= 1
+    dil = max(dilation, 1)
+    Ho = (H + 2 * pad - dil * (KH - 1) - 1) // stride + 1 if Ho is None else Ho
+    Wo = (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1 if Wo is None else Wo
+    ldx = (Cin if precision == PREC_MXFP8 else groups * Cin) if ldx is None else ldx
+    ldy = groups * Cout if ldy is None else ldy
+    flags = ((RELU1 if relu1 else 0) | (AFFINE2 | (RELU2 if relu2 else 0) if scale2 is not None else 0) |
+             (RESIDUAL | (RELU3 if relu3 else 0) if residual is not None else 0) | (ACCUM if accumulate else 0) |
+             (SPLIT_OUT if split_out is not None else 0) | (MXFP8_OUT if mx_out is not None else 0) | (STATS_OUT if stats_out is not None else 0) |
+             (NO_F32_OUT if no_f32_out and (split_out is not None or mx_out is not None) else 0))
+    # group g reads x + g*x_gs, w + g*w_gs, writes y + g*y_gs (vidc.h:110-111): the groups are channel slices of x, y and the residual
+    x_gs, w_gs = Cin, Cout * KH * KW * Cin
+    if precision == PREC_BF16:          # vidc.h:182-184: two bf16 channels per element in Cin, ldx, x_gs (and so in w_gs)
+        Cin, ldx = Cin // 2, ldx // 2
+        x_gs, w_gs = Cin, Cout * KH * KW * Cin
+    elif precision == PREC_MXFP8:       # vidc.h:192-194: four channels per element; a group is a data + scale plane pair (33 bytes per 32)
+        assert ldx == Cin, "an MXFP8 activation is one dense plane of Cin channels per group"
+        x_gs, w_gs = B * H * W * Cin // 128 * 33, Cout * KH * KW * Cin // 128 * 33
+        Cin, ldx = Cin // 4, Cin // 4
+    if wino_fused:                      # vidc.h:169-174: w holds U of 36 positions per group, re-ordered by vidc_winograd_weight_pack_fused
+        w_gs = 36 * Cout * Cin
+    return ConvDesc(x=x, w=w, y=y, scale1=scale1, shift1=shift1, scale2=scale2, shift2=shift2, residual=residual,
+                    B=B, H=H, W=W, Cin=Cin, ldx=ldx, Ho=Ho, Wo=Wo, Cout=Cout, ldy=ldy, ldr=(0 if residual is None else ldr or ldy),
+                    KH=KH, KW=KW, stride=stride, pad=pad, flags=flags, groups=groups,
+                    x_gs=x_gs, w_gs=w_gs, y_gs=Cout, r_gs=(0 if residual is None else Cout),
+                    p_gs=(0 if shared_affine and groups > 1 else Cout),      # (with one group p_gs is never read)
+                    tile=(TILE_WINO4_FUSED if wino_fused else TILE_AUTO), splitk=1, precision=precision, dilation=dil,
+                    y_split=next((p for p in (split_out, mx_out, stats_out) if p is not None), None))
+
+
+def gemm_desc(rows, K, N, groups=1, ldx=None, ldy=None, precision=PREC_FP32, planar=False, x=None, w=None, y=None, scale1=None,
+              shift1=None, shared_affine=True):
+    """y[g] = x[g] w[g]^T as the 1x1 conv of vidc_conv2d_bn_act over B = H = 1, W = rows (the "rows as W" GEMM): K and N in channels
+    per group, epilogue scale1 / shift1 only.  The Winograd products (vidc.h:223-224: rows = tiles, groups = G * (m+2)^2, an identity
+    affine shared by the groups) and the weight-gradient GEMMs of the training step (rows of dY^T times rows of the transposed im2col).
+    planar: group g's rows of x and of y are planes of their own (X_PLANAR_GROUPS, vidc.h:96-97) instead of channel slices."""
+    d = conv_desc(1, 1, rows, K, N, groups=groups, ldx=ldx, ldy=ldy, precision=precision, x=x, w=w, y=y, scale1=scale1, shift1=shift1,
+                  shared_affine=shared_affine)
+    if planar:
+        d.flags |= X_PLANAR_GROUPS
+        d.x_gs, d.y_gs = rows * d.ldx, rows * d.ldy
+    return d
+
+
+def plan(d, tiling=None):
+    """d.tile, d.splitk = `tiling` (a measured (tile, splitk)), or without one the planner's choice (vidc_conv2d_plan)."""
+    if tiling is not None:
+        d.tile, d.splitk = tiling
+    else:
+        check(lib().vidc_conv2d_plan(C.byref(d)), "conv plan")
+    return d
+
+
 class GenericArgs(C.Structure):
     _fields_ = [("p", C.c_void_p * 8), ("i", C.c_int32 * 16), ("f", C.c_float * 8)]
 

@@ -217,16 +217,6 @@ def mxfp8_layer(key, co, ci, flops):
     return ci % 128 == 0 and co % 32 == 0 and flops >= MXFP8_MIN_FLOPS and not any(e in key for e in MXFP8_EXCLUDED)
 
 
-# LDS bytes of the tilings (NS * (BM + BN) * 32 floats * WKW) and, for the co-residency experiment, the nearest tiling of at most 80 KB
-_TILE_LDS_KB = {33: 128, 34: 96, 35: 64, 36: 96, 37: 128, 38: 120, 39: 120, 28: 48, 29: 32, 30: 64, 31: 48, 32: 48, 1: 64, 2: 72, 3: 72, 4: 64, 5: 96, 6: 72, 7: 96, 8: 80, 9: 128, 10: 120, 11: 128, 12: 120, 13: 128, 14: 72, 15: 120, 16: 128, 17: 64,
-                18: 128, 19: 72, 20: 72, 21: 72, 22: 120, 23: 120, 24: 96, 25: 96, 26: 144, 27: 144}
-_TILE_SMALL = {5: 4, 13: 4, 18: 4, 7: 6, 9: 6, 10: 6, 11: 6, 15: 6, 16: 6, 12: 8, 22: 21, 23: 21, 24: 1, 25: 1, 26: 1, 27: 1}
-
-
-def _capped_tile(tile, cap_kb):
-    return _TILE_SMALL.get(tile, tile) if _TILE_LDS_KB.get(tile, 0) > cap_kb else tile
-
-
 def winograd_mode():
     """VIDC_WINOGRAD=auto : (default) 3x3 / stride 1 / pad 1 convs with >= 128 input channels run as Winograd F(m x m, 3x3) GEMMs
                              (csrc/winograd.hip): the entry "W:<direct signature>" of the measured table picks m in {0, 2, 4} (5 = m 4 in ONE launch, fp32 only), else (fp32 mode
@@ -249,7 +239,7 @@ def winograd_choice(B, H, W, co, ci, kh, kw, stride, padding, dilation, G, mode=
     else:
         ent = None                                # [m in the fp32 mode, m in the mixed mode]; measured on the frame program (4 pyramid groups):
         for gg in (G, 4, 3, 1, 2):                # the stand-alone programs run the same layers with 1 / 3 groups and take that verdict
-            ent = tuning_table().get("W:M%d_N%d_K%d_k3s1_G%d" % (B * H * W, co, 9 * ci, gg))
+            ent = tuning_table().get("W:" + conv_signature(L.conv_desc(B, H, W, ci, co, 3, 3, 1, 1, groups=gg)))
             if ent is not None:
                 break
         if ent is not None:
@@ -273,6 +263,8 @@ def winograd_choice(B, H, W, co, ci, kh, kw, stride, padding, dilation, G, mode=
 
 
 def conv_signature(d):
+    """Key of a launch in the measured tables (conv_tuning.json, train_tuning.json): GEMM rows, Cout, K, kernel height, stride and
+    groups of its descriptor -- L.conv_desc / L.gemm_desc without pointers give the key of a launch before it is built."""
     return "M%d_N%d_K%d_k%ds%d_G%d" % (d.B * d.Ho * d.Wo, d.Cout, d.KH * d.KW * d.Cin, d.KH, d.stride, d.groups)
 
 
@@ -387,7 +379,7 @@ class Program:
         self.direct_flops += flops
         self.ref_flops += int(round(flops * ref_flops_scale))
         # precision: measured table entry if there is one, else by size
-        sig = "M%d_N%d_K%d_k%ds%d_G%d" % (self.B * Ho * Wo, co, kh * kw * ci, kh, stride, G)
+        sig = conv_signature(L.conv_desc(self.B, x.H, x.W, ci, co, kh, kw, stride, padding, dilation, G))
         prec = L.PREC_FP32
         if mx:
             prec = L.PREC_MXFP8
@@ -397,7 +389,7 @@ class Program:
         xin = self.split(x) if prec == L.PREC_BF16X3 else (self.quant(x) if prec == L.PREC_MXFP8 else x)
         self._emit("conv", [xin, residual, y if accumulate else None], [y], x=xin, y=y, keys=keys, precision=prec,
                    bn=_keys(bn) if bn is not None else None, bn2=_keys(bn2) if bn2 is not None else None,
-                   residual=residual, flags=flags, stride=stride, pad=padding, geom=(co, ci, kh, kw, Ho, Wo), dilation=dilation)
+                   residual=residual, flags=flags, stride=stride, pad=padding, geom=(co, ci, kh, kw, Ho, Wo), dilation=dilation, sig=sig)
         return y
 
     def _conv_winograd(self, x, y, keys, bn, bn2, flags, m, geom):
@@ -409,7 +401,7 @@ class Program:
         tiles = self.B * (-(-Ho // m)) * (-(-Wo // m))
         gflops = 2 * tiles * a2 * G * co * ci
         self.flops += gflops
-        sig = "M%d_N%d_K%d_k1s1_G%d" % (tiles, co, ci, a2 * G)
+        sig = conv_signature(L.gemm_desc(tiles, ci, co, groups=a2 * G))
         prec = L.PREC_FP32
         if self.mode in ("mixed", "mxfp8"):
             ent = tuning_table().get(sig)
@@ -418,7 +410,7 @@ class Program:
         Mm = T(self._new_buf(tiles * a2 * G * co), 1, 1, tiles, co, a2 * G)
         self._emit("wino_in", [x], [V], x=x, v=V, m=m, cin=ci, split=int(prec == L.PREC_BF16X3))
         self._emit("conv", [V], [Mm], x=V, y=Mm, keys=keys, precision=prec, bn=None, bn2=None, residual=None, flags=0, stride=1, pad=0,
-                   geom=(co, ci, 1, 1, 1, tiles), dilation=1, wino=m)
+                   geom=(co, ci, 1, 1, 1, tiles), dilation=1, wino=m, sig=sig)
         self._emit("wino_out", [Mm], [y], mm=Mm, y=y, keys=keys, bn=_keys(bn) if bn is not None else None,
                    bn2=_keys(bn2) if bn2 is not None else None, flags=flags, m=m, cout=co)
         return y
@@ -431,7 +423,7 @@ class Program:
         self.flops += 2 * tiles * 36 * len(keys) * co * ci
         self._emit("conv", [x], [y], x=x, y=y, keys=keys, precision=L.PREC_FP32, bn=_keys(bn) if bn is not None else None,
                    bn2=_keys(bn2) if bn2 is not None else None, residual=None, flags=flags, stride=1, pad=1, geom=(co, ci, 3, 3, Ho, Wo), dilation=1,
-                   wino_fused=tiles)
+                   wino_fused=tiles, sig=conv_signature(L.gemm_desc(tiles, ci, co, groups=36 * len(keys))))      # (named by the products it executes)
         return y
 
     def split(self, x):
@@ -715,80 +707,39 @@ class Program:
             self.ops = [op for t, op in enumerate(self.ops) if t not in drop]
         self.n_fused_warps = len(drop)
 
-    def _fill_conv_desc(self, d, kw, addr, dry_run):
-        """Fills one vidc_conv_desc from a recorded conv; returns the op's display name."""
-        lib = L.lib()
-        x, y, keys = kw["x"], kw["y"], kw["keys"]
+    def _conv_desc(self, kw, addr, dry_run):
+        """The vidc_conv_desc of a recorded conv (L.conv_desc / L.gemm_desc) with its tiling, and the op's display name."""
+        x, y, keys, f = kw["x"], kw["y"], kw["keys"], kw["flags"]
         co, ci, kh, kwid, Ho, Wo = kw["geom"]
-        prec = kw["precision"]
-        wm = kw.get("wino", 0)
-        wf = kw.get("wino_fused", 0)
-        if wm:
-            wp = self.ws.packed_winograd([k for k in keys], wm, dry_run, prec)
-            s1, b1 = self.ws.identity_affine(co, wp.device)
-        elif wf:
-            wp = self.ws.packed_winograd_fused([k for k in keys], dry_run)
-            s1, b1 = self.ws.affine(list(keys), list(kw["bn"]) if kw["bn"] is not None else None)
-        else:
-            wp = self.ws.packed([k for k in keys], dry_run, prec)
-            s1, b1 = self.ws.affine(list(keys), list(kw["bn"]) if kw["bn"] is not None else None)
-        d.x, d.w, d.y = addr(x), wp.data_ptr(), addr(y)
-        d.scale1, d.shift1 = s1.data_ptr(), b1.data_ptr()
-        if kw["bn2"] is not None:
-            s2, b2 = self.ws.affine([None] * len(keys), list(kw["bn2"]))
-            d.scale2, d.shift2 = s2.data_ptr(), b2.data_ptr()
-            self._keep += [s2, b2]
-        r = kw["residual"]
-        if r is not None:
-            d.residual, d.ldr, d.r_gs = addr(r), r.ld, r.C
-        d.B, d.H, d.W, d.Cin, d.ldx = x.B, x.H, x.W, ci, x.ld
-        d.Ho, d.Wo, d.Cout, d.ldy = Ho, Wo, co, y.ld
-        d.KH, d.KW, d.stride, d.pad = kh, kwid, kw["stride"], kw["pad"]
-        d.dilation = kw.get("dilation", 1)
-        d.flags, d.groups = kw["flags"], len(keys)
-        if kw.get("split_out") is not None:
-            d.y_split = addr(kw["split_out"])
-        if kw.get("mx_out") is not None:
-            d.y_split = addr(kw["mx_out"])
-        d.x_gs, d.w_gs, d.y_gs, d.p_gs = x.C, co * kh * kwid * ci, y.C, co
+        prec, wm, wf, sig = kw["precision"], kw.get("wino", 0), kw.get("wino_fused", 0), kw["sig"]
         if wm:          # (m+2)^2 transform-domain GEMMs per group of the layer, identity epilogue shared by all of them
-            d.groups, d.p_gs = len(keys) * (wm + 2) * (wm + 2), 0
-        d.tile, d.splitk, d.precision = 0, 1, prec
-        sig = conv_signature(d)
-        if wf:          # one launch: the transformed weights of a group are 36 Cout Cin floats; shown with the signature of the products it executes
-            d.w_gs, d.tile = 36 * co * ci, L.TILE_WINO4_FUSED
-            self._keep += [wp, s1, b1]
-            return "conv:%s@wino4f:%s:sk1:fp32 M%d_N%d_K%d_k1s1_G%d flags=0x%x" % (keys[0], L.TILE_NAMES[d.tile], wf, co, ci, 36 * len(keys), d.flags)
-        if prec == L.PREC_MXFP8:
-            # four channels per descriptor element, every group a plane pair of its own (include/vidc.h); no measured MXFP8 entries yet:
-            # the planner's tiling (VIDC_FORCE_TILE where it names an MXFP8 tiling)
-            assert x.ch_off == 0 and x.ld == ci
-            d.Cin, d.ldx = ci // 4, ci // 4
-            d.x_gs, d.w_gs = x.B * x.H * x.W * ci // 128 * 33, co * kh * kwid * ci // 128 * 33
-            forced = int(os.environ.get("VIDC_FORCE_TILE", "0"))
-            if forced in L.MXFP8_TILES:
-                d.tile, d.splitk = forced, 1
-            else:
-                L.check(lib.vidc_conv2d_plan(C.byref(d)), "conv plan")
-            self._keep += [wp, s1, b1]
-            return "conv:%s:%s:sk%d:mxfp8 %s flags=0x%x" % (keys[0], L.TILE_NAMES[d.tile], d.splitk, sig, d.flags)
-        if os.environ.get("VIDC_FORCE_TILE"):           # (tests / A-B runs: one tiling for every conv)
-            d.tile, d.splitk = int(os.environ["VIDC_FORCE_TILE"]), 1
+            wp = self.ws.packed_winograd(list(keys), wm, dry_run, prec)
+            s1, b1 = self.ws.identity_affine(co, wp.device)
+            s2 = b2 = None
+            d = L.gemm_desc(x.W, ci, co, groups=len(keys) * (wm + 2) * (wm + 2), ldx=x.ld, ldy=y.ld, precision=prec, x=addr(x),
+                            w=wp.data_ptr(), y=addr(y), scale1=s1.data_ptr(), shift1=b1.data_ptr())
         else:
+            wp = self.ws.packed_winograd_fused(list(keys), dry_run) if wf else self.ws.packed(list(keys), dry_run, prec)
+            s1, b1 = self.ws.affine(list(keys), list(kw["bn"]) if kw["bn"] is not None else None)
+            s2, b2 = self.ws.affine([None] * len(keys), list(kw["bn2"])) if kw["bn2"] is not None else (None, None)
+            r, so, mo = kw["residual"], kw.get("split_out"), kw.get("mx_out")
+            d = L.conv_desc(x.B, x.H, x.W, ci, co, kh, kwid, kw["stride"], kw["pad"], kw["dilation"], len(keys), Ho, Wo, x.ld, y.ld, prec,
+                            x=addr(x), w=wp.data_ptr(), y=addr(y), scale1=s1.data_ptr(), shift1=b1.data_ptr(),
+                            scale2=s2.data_ptr() if s2 is not None else None, shift2=b2.data_ptr() if b2 is not None else None,
+                            relu1=f & L.RELU1, relu2=f & L.RELU2, residual=addr(r) if r is not None else None, ldr=r.ld if r is not None else None,
+                            relu3=f & L.RELU3, accumulate=f & L.ACCUM, split_out=addr(so) if so is not None else None,
+                            mx_out=addr(mo) if mo is not None else None, no_f32_out=f & L.NO_F32_OUT, wino_fused=bool(wf))
+        self._keep += [t for t in (wp, s1, b1, s2, b2) if t is not None]
+        if prec == L.PREC_MXFP8:        # no measured MXFP8 entries: the planner's tiling
+            L.plan(d)
+        elif not wf:                    # the fused Winograd form has its own tile
+            # the measured entry: [tile, splitk, precision] or [t, sk, prec, t32, sk32] with the best fp32 tiling as well; a 3-element entry
+            # of the mixed mode sets the tiling of an fp32 conv of that signature too
             ent = tuning_table().get(sig)
-            if ent is not None and (len(ent) < 5 or prec == ent[2]):
-                d.tile, d.splitk = ent[0], ent[1]
-            elif ent is not None and len(ent) >= 5:          # table holds the best fp32 config as well: [t, sk, prec, t32, sk32]
-                d.tile, d.splitk = ent[3], ent[4]
-            else:
-                L.check(lib.vidc_conv2d_plan(C.byref(d)), "conv plan")
-        if os.environ.get("VIDC_TILE_REMAP"):          # experiment knob: "6:28,10:28" replaces tile 6 and 10 by 28 wherever the table picked them
-            remap = dict((int(a), int(b)) for a, b in (kv.split(":") for kv in os.environ["VIDC_TILE_REMAP"].split(",") if kv))
-            d.tile = remap.get(d.tile, d.tile)
-        if os.environ.get("VIDC_LDS_CAP_KB"):          # experiment knob (tools/dual_stream_bench.py): tilings that leave room for a second
-            d.tile = _capped_tile(d.tile, int(os.environ["VIDC_LDS_CAP_KB"]))      # workgroup of another stream on the CU
-        self._keep += [wp, s1, b1]
-        return "conv:%s%s:%s:sk%d:%s %s flags=0x%x" % (keys[0], "@wino%d" % wm if wm else "", L.TILE_NAMES[d.tile], d.splitk, "bf16x3" if prec else "fp32", sig, d.flags)
+            L.plan(d, None if ent is None else (ent[0], ent[1]) if len(ent) < 5 or prec == ent[2] else (ent[3], ent[4]))
+        form = "@wino4f" if wf else ("@wino%d" % wm if wm else "")
+        pname = {L.PREC_FP32: "fp32", L.PREC_BF16X3: "bf16x3", L.PREC_MXFP8: "mxfp8"}[prec]
+        return d, "conv:%s%s:%s:sk%d:%s %s flags=0x%x" % (keys[0], form, L.TILE_NAMES[d.tile], d.splitk, pname, sig, d.flags)
 
     def _plan_buffers(self):
         n = len(self.buf_elems)
@@ -851,7 +802,7 @@ class Program:
 
         ops = (L.Op * sum(1 for _ in self.ops))()
         ws_need = {}
-        conv_ops = []
+        ws_ops = []              # the convs that need a split-K workspace
         self.op_names = []
         for i, (kind, _r, _w, kw) in enumerate(self.ops):
             op = ops[i]
@@ -859,11 +810,11 @@ class Program:
             g = op.u.g
             if kind == "conv":
                 op.kind = L.OP_CONV
-                name = self._fill_conv_desc(op.u.conv, kw, addr, dry_run)
+                op.u.conv, name = self._conv_desc(kw, addr, dry_run)
                 need = lib.vidc_conv2d_workspace_bytes(C.byref(op.u.conv))
                 if need:
                     ws_need[op.stream_id] = max(ws_need.get(op.stream_id, 0), need)
-                conv_ops.append(op)
+                    ws_ops.append(op)
                 self.op_names.append(name)
             elif kind == "stem":
                 x, y = kw["x"], kw["y"]
@@ -1015,9 +966,8 @@ class Program:
         # split-K workspaces (one per stream id so concurrent convs never share partials); zeroed once: their heads hold the
         # per-tile ticket counters of the fused split-K reduction, which every launch leaves at zero (include/vidc.h)
         self.workspaces = {sid: torch.zeros(nb // 4 + 4, dtype=torch.float32, device=self.device) for sid, nb in ws_need.items()}
-        for op in conv_ops:
-            if op.u.conv.splitk > 1:
-                op.u.conv.workspace = self.workspaces[op.stream_id].data_ptr()
+        for op in ws_ops:
+            op.u.conv.workspace = self.workspaces[op.stream_id].data_ptr()
         self.c_ops = ops
         self.captured = False
         if dry_run:

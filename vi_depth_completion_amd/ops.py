@@ -94,43 +94,25 @@ def conv2d_bn_act(x, w_packed, scale1, shift1, kh, kw, stride=1, pad=0, relu1=Fa
         cout = wp.shape[1]
     Ho, Wo = (H + 2 * pad - dilation * (kh - 1) - 1) // stride + 1, (W + 2 * pad - dilation * (kw - 1) - 1) // stride + 1
     y = accumulate_into if accumulate_into is not None else torch.empty((B, Ho, Wo, G * cout), dtype=torch.float32, device=x.device)
-    d = L.ConvDesc()
-    d.x, d.w, d.y = L.ptr(x), L.ptr(wp), L.ptr(y)
     s1, b1 = scale1.contiguous().float(), shift1.contiguous().float()
-    d.scale1, d.shift1 = L.ptr(s1), L.ptr(b1)
-    flags = (L.RELU1 if relu1 else 0)
-    keep = [s1, b1]
-    if scale2 is not None:
-        s2, b2 = scale2.contiguous().float(), shift2.contiguous().float()
-        d.scale2, d.shift2 = L.ptr(s2), L.ptr(b2)
-        keep += [s2, b2]
-        flags |= L.AFFINE2 | (L.RELU2 if relu2 else 0)
-    if residual is not None:
-        residual = residual.contiguous()
-        d.residual, d.ldr, d.r_gs = L.ptr(residual), residual.shape[-1], cout
-        flags |= L.RESIDUAL | (L.RELU3 if relu3 else 0)
-    if accumulate_into is not None:
-        flags |= L.ACCUM
-    if split_out is not None:       # float32-typed tensor of y's shape receiving the split-bf16 image of the result
-        d.y_split = L.ptr(split_out)
-        flags |= L.SPLIT_OUT | (L.NO_F32_OUT if no_f32_out else 0)
+    s2, b2 = (scale2.contiguous().float(), shift2.contiguous().float()) if scale2 is not None else (None, None)
+    residual = residual.contiguous() if residual is not None else None
     if mx_out is not None:
         assert mx_out.dtype == torch.uint8 and mx_out.numel() >= G * B * Ho * Wo * cout // 32 * 33
-        d.y_split = L.ptr(mx_out)
-        flags |= L.MXFP8_OUT | (L.NO_F32_OUT if no_f32_out else 0)
-    d.B, d.H, d.W, d.Cin, d.ldx = B, H, W, cin, ld
-    d.Ho, d.Wo, d.Cout, d.ldy = Ho, Wo, cout, G * cout
-    d.KH, d.KW, d.stride, d.pad, d.flags, d.groups = kh, kw, stride, pad, flags, G
-    d.dilation = dilation
-    d.x_gs, d.w_gs, d.y_gs, d.p_gs = cin, cout * kh * kw * cin, cout, (cout if s1.numel() >= G * cout else 0)      # (one affine for all groups: p_gs = 0)
-    if precision == L.PREC_MXFP8:       # four channels per descriptor element; every group a plane pair of its own (include/vidc.h)
-        d.Cin, d.ldx = cin // 4, cin // 4
-        d.x_gs, d.w_gs = B * H * W * cin // 128 * 33, cout * kh * kw * cin // 128 * 33
-    d.tile, d.splitk, d.precision = tile, splitk, precision
-    if tile == 0:
-        L.check(L.lib().vidc_conv2d_plan(C.byref(d)), "conv2d_plan")
-        if splitk > 1:
-            d.splitk = splitk
+    d = L.conv_desc(B, H, W, cin, cout, kh, kw, stride, pad, dilation, G, Ho, Wo, precision=precision, x=L.ptr(x), w=L.ptr(wp), y=L.ptr(y),
+                    scale1=L.ptr(s1), shift1=L.ptr(b1), shared_affine=s1.numel() < G * cout, scale2=L.ptr(s2), shift2=L.ptr(b2),
+                    relu1=relu1, relu2=relu2, residual=L.ptr(residual), ldr=residual.shape[-1] if residual is not None else None, relu3=relu3,
+                    accumulate=accumulate_into is not None, split_out=L.ptr(split_out), mx_out=L.ptr(mx_out), no_f32_out=no_f32_out)
+    _launch(d, x.device, tile, splitk, workspace, "conv2d_bn_act")
+    return y
+
+
+def _launch(d, device, tile, splitk, workspace, what):
+    """Tiles `d` -- (tile, splitk), or for tile 0 the planner's tile, with `splitk` kept where it is > 1 -- and launches it, with the
+    caller's split-K workspace or a fresh zeroed one where it needs one."""
+    L.plan(d, (tile, splitk) if tile else None)
+    if not tile and splitk > 1:
+        d.splitk = splitk
     ws = None
     nbytes = L.lib().vidc_conv2d_workspace_bytes(C.byref(d))
     if nbytes and workspace is not None:
@@ -138,10 +120,9 @@ def conv2d_bn_act(x, w_packed, scale1, shift1, kh, kw, stride=1, pad=0, relu1=Fa
             raise RuntimeError("split-K workspace too small: %d < %d bytes" % (workspace.numel() * 4, nbytes))
         d.workspace = L.ptr(workspace)
     elif nbytes:
-        ws = torch.zeros(nbytes // 4, dtype=torch.float32, device=x.device)     # zeroed: ticket counters at its head
+        ws = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)     # zeroed: ticket counters at its head
         d.workspace = L.ptr(ws)
-    L.check(L.lib().vidc_conv2d_bn_act(C.byref(d), L.current_stream()), "conv2d_bn_act")
-    return y
+    L.check(L.lib().vidc_conv2d_bn_act(C.byref(d), L.current_stream()), what)
 
 
 def stem_conv3x3s2(x_nchw, w_oihw, relu=True, split_out=None):
@@ -280,25 +261,10 @@ def conv3x3_winograd(x, w_oihw_groups, scale1, shift1, m, relu1=False, scale2=No
         u = img
     v = winograd_input_transform(x, cin, m, split=precision == L.PREC_BF16X3)
     tiles = v.shape[0]
-    d = L.ConvDesc()
     mm = torch.empty((tiles, a2 * G * cout), dtype=torch.float32, device=x.device)
     one, zero = torch.ones(cout, dtype=torch.float32, device=x.device), torch.zeros(cout, dtype=torch.float32, device=x.device)
-    d.x, d.w, d.y, d.scale1, d.shift1 = L.ptr(v), L.ptr(u), L.ptr(mm), L.ptr(one), L.ptr(zero)
-    d.B, d.H, d.W, d.Cin, d.ldx = 1, 1, tiles, cin, a2 * G * cin
-    d.Ho, d.Wo, d.Cout, d.ldy = 1, tiles, cout, a2 * G * cout
-    d.KH, d.KW, d.stride, d.pad, d.flags, d.groups = 1, 1, 1, 0, 0, a2 * G
-    d.x_gs, d.w_gs, d.y_gs, d.p_gs = cin, cout * cin, cout, 0
-    d.tile, d.splitk, d.precision = tile, splitk, precision
-    if tile == 0:
-        L.check(L.lib().vidc_conv2d_plan(C.byref(d)), "conv2d_plan")
-        if splitk > 1:
-            d.splitk = splitk
-    ws = None
-    nbytes = L.lib().vidc_conv2d_workspace_bytes(C.byref(d))
-    if nbytes:
-        ws = torch.zeros(nbytes // 4, dtype=torch.float32, device=x.device)
-        d.workspace = L.ptr(ws)
-    L.check(L.lib().vidc_conv2d_bn_act(C.byref(d), L.current_stream()), "conv2d_bn_act (winograd GEMMs)")
+    d = L.gemm_desc(tiles, cin, cout, groups=a2 * G, precision=precision, x=L.ptr(v), w=L.ptr(u), y=L.ptr(mm), scale1=L.ptr(one), shift1=L.ptr(zero))
+    _launch(d, x.device, tile, splitk, None, "conv2d_bn_act (winograd GEMMs)")
     return winograd_output_transform(mm, B, H, W, cout, m, scale1, shift1, relu1, scale2, shift2, relu2, split_out, no_f32_out)
 
 
@@ -326,21 +292,10 @@ def conv3x3_winograd_fused(x, w_oihw_groups, scale1, shift1, relu1=False, scale2
         u = torch.cat([winograd_weight_pack_fused(winograd_weight_transform(w, 4)) for w in w_oihw_groups], 0)      # (G*36, cout, cin) floats, fragment order
     cout = u.shape[1]
     y = torch.empty((B, H, W, G * cout), dtype=torch.float32, device=x.device)
-    d = L.ConvDesc()
     s1, b1 = scale1.contiguous().float().view(-1), shift1.contiguous().float().view(-1)
-    d.x, d.w, d.y, d.scale1, d.shift1 = L.ptr(x), L.ptr(u), L.ptr(y), L.ptr(s1), L.ptr(b1)
-    flags = (L.RELU1 if relu1 else 0)
-    keep = [s1, b1]
-    if scale2 is not None:
-        s2, b2 = scale2.contiguous().float().view(-1), shift2.contiguous().float().view(-1)
-        d.scale2, d.shift2 = L.ptr(s2), L.ptr(b2)
-        keep += [s2, b2]
-        flags |= L.AFFINE2 | (L.RELU2 if relu2 else 0)
-    d.B, d.H, d.W, d.Cin, d.ldx = B, H, W, cin, Cc
-    d.Ho, d.Wo, d.Cout, d.ldy = H, W, cout, G * cout
-    d.KH, d.KW, d.stride, d.pad, d.flags, d.groups = 3, 3, 1, 1, flags, G
-    d.x_gs, d.w_gs, d.y_gs, d.p_gs = cin, 36 * cout * cin, cout, (cout if s1.numel() >= G * cout else 0)
-    d.tile, d.splitk, d.precision = L.TILE_WINO4_FUSED, 1, L.PREC_FP32
+    s2, b2 = (scale2.contiguous().float().view(-1), shift2.contiguous().float().view(-1)) if scale2 is not None else (None, None)
+    d = L.conv_desc(B, H, W, cin, cout, 3, 3, 1, 1, groups=G, x=L.ptr(x), w=L.ptr(u), y=L.ptr(y), scale1=L.ptr(s1), shift1=L.ptr(b1),
+                    shared_affine=s1.numel() < G * cout, scale2=L.ptr(s2), shift2=L.ptr(b2), relu1=relu1, relu2=relu2, wino_fused=True)
     L.check(L.lib().vidc_conv2d_bn_act(C.byref(d), L.current_stream()), "conv2d_bn_act (fused Winograd)")
     return y
 

@@ -362,21 +362,10 @@ class DepthCompletionTrainer:
             if xs is None:
                 xs = self._empty(B, H, W, cin // 2)
                 L.check(L.lib().vidc_cast_bf16(L.ptr(x_t), L.ptr(xs), B * H * W, cin, ldx, L.current_stream()), "cast")
-            x_t, cin = xs, cin // 2
-            ldx = cin
-        cin, cout = cin // G, cout // G           # per group (cin in the descriptor's units: two bf16 channels per element in the bf16 mode)
-        d = L.ConvDesc()
-        d.x, d.w, d.y = L.ptr(x_t), L.ptr(w_packed), L.ptr(y_t)
-        d.scale1, d.shift1 = L.ptr(self._const(self._ones, cout, 1.0)), L.ptr(shift)
-        d.B, d.H, d.W, d.Cin, d.ldx = B, H, W, cin, ldx
-        d.Ho, d.Wo, d.Cout, d.ldy = Ho, Wo, cout, _ld(y_t)
-        d.KH, d.KW, d.stride, d.pad = kh, kw, stride, pad
-        d.flags = (L.RELU1 if relu else 0) | (L.ACCUM if accumulate else 0)
-        if stats is not None:                 # (the descriptor's y_split field carries the partials buffer: include/vidc.h VIDC_STATS_OUT)
-            d.flags |= L.STATS_OUT
-            d.y_split = L.ptr(stats)
-        d.groups, d.splitk, d.precision, d.tile = G, 1, self.precision, 0
-        d.x_gs, d.w_gs, d.y_gs, d.p_gs = cin, cout * kh * kw * cin, cout, (cout if G == 1 else 0)
+            x_t, ldx = xs, cin                    # (dense rows of cin channels)
+        d = L.conv_desc(B, H, W, cin // G, cout // G, kh, kw, stride, pad, groups=G, Ho=Ho, Wo=Wo, ldx=ldx, ldy=_ld(y_t), precision=self.precision,
+                        x=L.ptr(x_t), w=L.ptr(w_packed), y=L.ptr(y_t), scale1=L.ptr(self._const(self._ones, cout // G, 1.0)), shift1=L.ptr(shift),
+                        shared_affine=True, relu1=relu, accumulate=accumulate, stats_out=L.ptr(stats))
         self._plan(d, "conv")
         L.check(L.lib().vidc_conv2d_bn_act(C.byref(d), L.current_stream()), "conv")
 
@@ -385,15 +374,11 @@ class DepthCompletionTrainer:
         [tile, splitk] per arithmetic mode), else the planner's cost model.  Split-K partial sums go through one persistent workspace
         (ticket counters at its head, zeroed once; the last workgroup of a tile resets its ticket)."""
         lib = L.lib()
-        fixed = self.tune_hook(d, role) if self.tune_hook is not None else None      # (a hook that returns True has set tile / splitk itself)
-        ent = training_table().get(engine.conv_signature(d))
-        if fixed:
-            pass
-        elif ent is not None and len(ent) > 2 * d.precision + 1 and ent[2 * d.precision]:
-            d.tile, d.splitk = ent[2 * d.precision], ent[2 * d.precision + 1]
-        else:
-            L.check(lib.vidc_conv2d_plan(C.byref(d)), "conv plan")
-            if role == "conv":
+        if not (self.tune_hook is not None and self.tune_hook(d, role)):      # (a hook that returns True has set tile / splitk itself)
+            ent, p = training_table().get(engine.conv_signature(d)), 2 * d.precision
+            tiling = (ent[p], ent[p + 1]) if ent is not None and len(ent) > p + 1 and ent[p] else None
+            L.plan(d, tiling)
+            if tiling is None and role == "conv":
                 d.splitk = 1
         need = lib.vidc_conv2d_workspace_bytes(C.byref(d))
         if need:
@@ -531,18 +516,11 @@ class DepthCompletionTrainer:
             L.check(lib.vidc_im2col_transposed_bf16(L.ptr(x.bf), L.ptr(xt), B, H, W, G * ci, Ho, Wo, kh, kw, stride, pad, Mp, st), "im2col^T (bf16)")
         else:
             L.check(lib.vidc_im2col_transposed(L.ptr(x.t), L.ptr(xt), B, H, W, G * ci, x.ld, Ho, Wo, kh, kw, stride, pad, Mp, split | (4 if inplace else 0), st), "im2col^T")
-        Mp //= e
         n_out = taps * ci
         gw = self._adjacent_base(self.grad, keys, ".weight")      # grouped: the G gradients are one contiguous run, group g at + g * co * n_out
         tmp = gw if inplace else self._empty(co, n_out)
-        d = L.ConvDesc()
-        d.x, d.w, d.y = L.ptr(gt), L.ptr(xt), L.ptr(tmp)
-        d.scale1, d.shift1 = L.ptr(self._const(self._ones, n_out, 1.0)), L.ptr(self._const(self._zeros, n_out, 0.0))
-        d.B, d.H, d.W, d.Cin, d.ldx = 1, 1, co, Mp, Mp
-        d.Ho, d.Wo, d.Cout, d.ldy = 1, co, n_out, n_out
-        d.KH, d.KW, d.stride, d.pad, d.flags = 1, 1, 1, 0, (L.X_PLANAR_GROUPS if G > 1 else 0)
-        d.groups, d.splitk, d.precision, d.tile = G, 1, self.precision, 0
-        d.x_gs, d.w_gs, d.y_gs, d.p_gs = (co * Mp if G > 1 else Mp), n_out * Mp, (co * n_out if G > 1 else n_out), (0 if G > 1 else n_out)
+        d = L.gemm_desc(co, Mp, n_out, groups=G, ldx=Mp, ldy=n_out, precision=self.precision, planar=G > 1, x=L.ptr(gt), w=L.ptr(xt), y=L.ptr(tmp),
+                        scale1=L.ptr(self._const(self._ones, n_out, 1.0)), shift1=L.ptr(self._const(self._zeros, n_out, 0.0)))
         self._plan(d, "gemm")
         L.check(lib.vidc_conv2d_bn_act(C.byref(d), st), "wgrad gemm")
         if not inplace:
