@@ -11,6 +11,10 @@ one "step" = one frame through warp -> surface-normal net -> plane block + enric
 (RunDepthCompletion._call_cnn, main.py:261-298), inputs resident in HBM, seeded random-init weights.
 Frames shard over ranks with no data-path collective (weak scaling: every rank runs K frames); RCCL only gathers
 4 doubles per rank at the end.  Rank 0 prints ONE JSON line.
+
+A plain run measures the headline alone: set-up, W warm-up steps, the timed regions of K steps, --dump-outputs, the line.
+Everything else (the mixed-precision leg, steady-state rate, first-item latency, back-to-back _call_cnn, per-kernel roofline,
+parity against the CPU oracle, CPU baseline, the extra configurations) runs with --full.
 """
 import argparse
 import json
@@ -42,9 +46,14 @@ def parse():
     ap.add_argument("--width", type=int, default=320)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--pool", type=int, default=4, help="distinct synthetic frames cycled through")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline leg: the mixed-precision leg, the steady-state rate, the "
+                         "first-item latency, back-to-back _call_cnn, the per-kernel roofline, parity against the CPU oracle, the CPU baseline "
+                         "and the extra configurations (`extra_legs`).  --no-cpu-baseline, --no-sequential-leg, --no-extra-legs and "
+                         "--steady-frames only shape a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=4)
-    ap.add_argument("--per-op", type=str, default="", help="write the per-op timing table to this file")
+    ap.add_argument("--per-op", type=str, default="", help="write the per-op timing table to this file (needs --full: the roofline pass measures it)")
     ap.add_argument("--source", default="", help="WxH of a raw camera stream (e.g. 640x480, 1280x720: BASELINE configs[2], [3]); every step "
                                                   "then starts from uint8 frames resident in HBM and includes the device-side pre-processing "
                                                   "(PIL-exact resize + ToTensor, sparse-point rasterisation) of SURVEY 8f-2")
@@ -68,7 +77,8 @@ def parse():
                          "frames/s in fp32 at 20 steps with the first item complete after 26 ms, 2 measures 361-364 with 15 ms (DESIGN 5.1)")
     ap.add_argument("--no-fp32-leg", action="store_true", help="only the mixed-mode leg (bf16x3 MFMA on the layers the measured table selects): it becomes "
                                                                "the headline, with its dtype in the line")
-    ap.add_argument("--no-mixed-leg", action="store_true", help="only the headline leg (every conv in exact fp32 MFMA arithmetic)")
+    ap.add_argument("--no-mixed-leg", action="store_true", help="only the headline leg (every conv in exact fp32 MFMA arithmetic); a plain run "
+                                                                "reports the headline leg alone and runs the mixed leg only to write its --dump-outputs array")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the short child-process runs of BASELINE configs[4] (training step, bf16) and "
                                                                  "configs[2] (640x480 stream, batch 8, plane head) that the default N=1 run appends as `extra_legs`")
     ap.add_argument("--extra-legs-budget", type=float, default=130.0, help="seconds of wall clock since the start of this process after which no further extra leg is started")
@@ -94,6 +104,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.per_op and not args.full:
+        ap.error("--per-op needs --full")
     if args.frames_per_launch <= 0:
         args.frames_per_launch = 4 if args.batch == 1 else 1
     return args
@@ -239,7 +251,8 @@ def winograd_summary(prog, ops, fpt, frames_per_s, peak_tflops, ref_flops_per_ti
 
 def measure(args, dev, rank, world, precision):
     """One leg: builds the pipeline in `precision` mode ("mixed" | "fp32": engine.precision_mode reads VIDC_PRECISION when a program is
-    recorded), runs W untimed + K timed steps bracketed by barrier + synchronize, then (rank 0) the live roofline of what was timed."""
+    recorded), runs W untimed + K timed steps bracketed by barrier + synchronize, then (rank 0, --full only) the steady-state stream, the
+    first-item latency, back-to-back _call_cnn and the live roofline of what was timed."""
     import torch.distributed as dist
     os.environ["VIDC_PRECISION"] = precision
     H, W, B = args.height, args.width, args.batch
@@ -306,7 +319,7 @@ def measure(args, dev, rank, world, precision):
     # ---- steady state of the stream mode (outside the timed regions): one long stream, a device time stamp behind every item's result;
     #      rate between two group boundaries well inside it, i.e. without the fill and the drain a K-step region contains ------------------
     steady = None
-    if rank == 0 and args.mode == "interleaved" and args.steady_frames >= 0:
+    if rank == 0 and args.full and args.mode == "interleaved" and args.steady_frames >= 0:
         grp = lanes * args.frames_per_launch
         n_long = args.steady_frames if args.steady_frames > 0 else 16 * grp
         n_long = max(6 * grp, n_long // grp * grp)
@@ -329,7 +342,7 @@ def measure(args, dev, rank, world, precision):
     # ---- latency of the first item of a stream in the mode that was timed (outside the timed region): host time from the first request to
     #      the first depth map being complete on the device; with --frames-per-launch F the first F items finish together ------------------
     first_item_ms = None
-    if rank == 0 and args.mode == "interleaved":
+    if rank == 0 and args.full and args.mode == "interleaved":
         lat = []
         for _ in range(3):
             torch.cuda.synchronize()
@@ -346,7 +359,7 @@ def measure(args, dev, rank, world, precision):
     # ---- the operator the reference's harness calls, frame after frame (network_run.py:294-296: one _call_cnn per batch, its output
     #      consumed before the next call): per-frame latency and the rate with ONE frame in flight.  Outside the timed region. ----------
     sequential = None
-    if rank == 0 and not args.no_sequential_leg and args.sequential_frames > 0:
+    if rank == 0 and args.full and not args.no_sequential_leg and args.sequential_frames > 0:
         it = frames(args.sequential_frames + 3)
         for _ in range(3):
             pipe._call_cnn(next(it))
@@ -366,7 +379,7 @@ def measure(args, dev, rank, world, precision):
     #      CPU baseline, whose OpenMP workers keep spinning and would slow the launching thread ---------------------
     roofline = None
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         fpt = B * (args.frames_per_launch if args.mode == "interleaved" else 1)      # frames per execution of the program measured below
         if args.mode == "interleaved":     # the program that was timed: one tick = both networks, 4-group pyramid launches, F items per launch
             fp = pipe.frame_program(fpt, H, W)
@@ -585,7 +598,7 @@ def main():
     # Two legs over the same steps, both inside this process (no re-exec).  The HEADLINE leg runs every conv in the reference's own
     # arithmetic (fp32 MFMA: exact fp32 products and sums) -- value, ms_per_step, dtype "f32", rmse_vs_oracle and roofline describe it.
     # The mixed mode (bf16x3 MFMA on the layers the measured table selects; narrower products, RMSE ~1e-5 against the 1e-3 bar) is
-    # reported beside it as value_mixed / dtype_mixed / roofline_mixed / mixed_leg.
+    # reported beside it as value_mixed / dtype_mixed / roofline_mixed / mixed_leg by a --full run.
     if os.environ.get("VIDC_PRECISION") in ("fp32", "mixed"):
         legs = [os.environ["VIDC_PRECISION"]]                  # an explicit mode: that leg alone
     else:
@@ -593,8 +606,13 @@ def main():
         if not legs:
             raise SystemExit("bench.py: --no-fp32-leg and --no-mixed-leg leave nothing to run")
     main_mode = legs[0]
+    # a plain run reports the headline leg alone; the other leg still runs its set-up, warm-up and timed steps when --dump-outputs asks for
+    # what its last step returned (the same steps draw the same numbers: the arrays a --full run writes)
+    run_legs = legs if (args.full or args.dump_outputs) else legs[:1]
+    if not args.full:
+        legs = legs[:1]
     res = {}
-    for mode in legs:
+    for mode in run_legs:
         res[mode] = measure(args, dev, rank, world, mode)      # (both pipelines stay resident: ~6 GB of 288)
     lead = res[main_mode]
     cc = lead["cc"]
@@ -605,7 +623,7 @@ def main():
         recs[m][0], recs[m][1] = args.steps * B, res[m]["elapsed"]
     n_reg = len(lead["region_s"])
     cpu_baseline = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         from oracle import vidc_oracle as O
         intr = O.Intrinsics(202.0, 202.0, cc[0], cc[1])
         cpu_sn = {k: v.cpu() for k, v in lead["sn_sd"].items()}
@@ -672,7 +690,7 @@ def main():
             fps.append((jr["frames"] / jr["seconds"], jr["seconds"]))
         region_fps[m] = fps
     extra_legs = None
-    if rank == 0 and world == 1 and not args.no_extra_legs and not args.source and not args.plane_head and B == 1 and args.mode == "interleaved":
+    if rank == 0 and world == 1 and args.full and not args.no_extra_legs and not args.source and not args.plane_head and B == 1 and args.mode == "interleaved":
         torch.cuda.synchronize()
         extra_legs = run_extra_legs(args)
     if rank == 0:
@@ -703,7 +721,7 @@ def main():
                        "frames_in_flight": (2 * lead["lanes"] * F if args.mode == "interleaved" else args.in_flight if args.mode == "streams" else 1),
                        "latency_note": ("`value` is a stream rate: %d batch-%d items share every launch on %d lanes (%d frames in flight; first depth map of a stream "
                                         "after first_item_latency_ms).  The reference's operator called one frame at a time is `sequential_call_cnn`; the "
-                                        "one- and two-items-per-launch stream rates are in `extra_legs`." % (F, B, lead["lanes"], 2 * lead["lanes"] * F)) if F > 1 else None,
+                                        "one- and two-items-per-launch stream rates are in `extra_legs` (both in a --full line)." % (F, B, lead["lanes"], 2 * lead["lanes"] * F)) if F > 1 else None,
                        "sharding": "frames round-robin over %d rank(s), no data-path collective" % world},
             "rmse_vs_oracle": (round(job["rmse"], 8) if job["rmse"] is not None else None),
             "roofline": lead["roofline"], "cpu_baseline": cpu_baseline,
@@ -740,7 +758,7 @@ def main():
         if extra_legs is not None:
             line["extra_legs"] = extra_legs
         if args.dump_outputs:
-            line["dumped_outputs"] = dump_outputs(args.dump_outputs, {"depth_" + m: res[m]["last_output"] for m in legs})
+            line["dumped_outputs"] = dump_outputs(args.dump_outputs, {"depth_" + m: res[m]["last_output"] for m in run_legs})
         print(json.dumps(line), flush=True)
     if world > 1 or os.environ.get("VIDC_DIST_WORLD1", "0") == "1":
         dist.barrier()
@@ -764,8 +782,9 @@ def dump_outputs(out_dir, arrays):
 
 def run_extra_legs(args):
     """Driver-visible numbers for BASELINE configs[4] and configs[2] and for the stream mode's two-items-per-launch setting: each one is THIS script started as a child process
-    (its own GPU context, its own environment; a crash or a hang there cannot take the headline down) after both main legs have been
-    measured and before the line is printed.  Skipped once the wall clock of this run passes --extra-legs-budget."""
+    (its own GPU context, its own environment; a crash or a hang there cannot take the headline down) after both main legs of a --full run
+    have been measured and before the line is printed; every inference child is a --full run itself.  Skipped once the wall clock of this
+    run passes --extra-legs-budget."""
     import subprocess
     t_start = _T0
     out = {}
@@ -773,18 +792,18 @@ def run_extra_legs(args):
               ["--train", "--batch", "8", "--steps", "5", "--warmup", "3"]),
              ("configs[2] 640x480 stream, batch 8, Mask R-CNN plane head every frame", {},
               ["--batch", "8", "--source", "640x480", "--height", "240", "--plane-head", "--steps", "20", "--warmup", "4", "--frames-per-launch", "1",
-               "--no-cpu-baseline", "--no-sequential-leg", "--no-extra-legs"]),
+               "--no-cpu-baseline", "--no-sequential-leg", "--no-extra-legs", "--full"]),
              ("configs[3] 1280x720 stream, one GPU's share of batch 32 = 4 frames per item (plane mask fixed)", {},
               ["--batch", "4", "--source", "1280x720", "--height", "240", "--steps", "20", "--warmup", "4", "--frames-per-launch", "1",
-               "--no-cpu-baseline", "--no-sequential-leg", "--no-extra-legs"]),
+               "--no-cpu-baseline", "--no-sequential-leg", "--no-extra-legs", "--full"]),
              # the headline runs four items per launch (first depth map of a stream after ~26 ms); this is the same workload at the
              # lower-latency setting of the knob (two items per launch, ~15 ms), in the headline's arithmetic
              ("configs[1] with two items per launch (lower first-item latency), fp32", {},
-              ["--steps", "20", "--warmup", "5", "--frames-per-launch", "2", "--no-mixed-leg", "--no-cpu-baseline", "--no-sequential-leg", "--no-extra-legs"]),
+              ["--steps", "20", "--warmup", "5", "--frames-per-launch", "2", "--no-mixed-leg", "--no-cpu-baseline", "--no-sequential-leg", "--no-extra-legs", "--full"]),
              ("configs[1] with eight items per launch (the throughput end of the knob: 48 frames in flight), fp32", {},
-              ["--steps", "40", "--warmup", "8", "--frames-per-launch", "8", "--no-mixed-leg", "--no-cpu-baseline", "--no-sequential-leg", "--no-extra-legs"]),
+              ["--steps", "40", "--warmup", "8", "--frames-per-launch", "8", "--no-mixed-leg", "--no-cpu-baseline", "--no-sequential-leg", "--no-extra-legs", "--full"]),
              ("configs[1] with one item per launch (every launch is one batch-1 frame), fp32", {},
-              ["--steps", "20", "--warmup", "5", "--frames-per-launch", "1", "--no-mixed-leg", "--no-cpu-baseline", "--no-sequential-leg", "--no-extra-legs"])]
+              ["--steps", "20", "--warmup", "5", "--frames-per-launch", "1", "--no-mixed-leg", "--no-cpu-baseline", "--no-sequential-leg", "--no-extra-legs", "--full"])]
     for name, env_add, flags in specs:
         if time.perf_counter() - t_start > args.extra_legs_budget:
             out[name] = {"skipped": "wall-clock budget of the run (%.0f s) used up" % args.extra_legs_budget}

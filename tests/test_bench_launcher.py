@@ -81,8 +81,8 @@ def test_bench_refuses_a_world_that_is_not_gpus():
 
 @pytest.mark.gpu
 def test_bench_two_gloo_ranks_on_one_gpu():
-    """The whole bench (timed region between barriers, parity check, gather) with two ranks sharing the one GPU over gloo."""
-    cmd = [sys.executable, BENCH, "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-fp32-leg", "--no-sequential-leg"]
+    """The whole bench (--full: timed region between barriers, parity check, gather) with two ranks sharing the one GPU over gloo."""
+    cmd = [sys.executable, BENCH, "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-fp32-leg", "--no-sequential-leg", "--full"]
     # No second try (round 4 retried once around "a rank gone within seconds of starting" seen one time on a fresh box): the launcher now
     # keeps every rank's output in a file of its own and replays it on failure, so a death shows its cause here -- and fails the test.
     log_dir = os.path.join(ROOT, "gpurun_out", "rank_logs_two_gloo_ranks")
@@ -211,6 +211,7 @@ def test_extra_legs_can_never_take_the_headline_down(monkeypatch):
     assert "TimeoutExpired" in out[names[1]]["error"]
     assert all(kw.get("timeout") and kw.get("capture_output") for _c, kw in calls)
     assert all("--no-extra-legs" in c or "--train" in c for c, _kw in calls), "a child must not start grandchildren"
+    assert all("--full" in c or "--train" in c for c, _kw in calls), "an inference child reports what a --full line holds"
     for env in (kw["env"] for _c, kw in calls):
         assert "RANK" not in env and "VIDC_PRECISION" not in env
         assert not any(k in env for k in ("VIDC_DIST_WORLD1", "MASTER_PORT", "MASTER_ADDR", "GROUP_RANK")) and not any(k.startswith("TORCHELASTIC_") for k in env)
@@ -255,5 +256,20 @@ def test_dump_outputs_writes_float32_arrays_within_the_limit(monkeypatch, tmp_pa
         bench.dump_outputs(str(tmp_path / "big"), {"a": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)})
     assert not (tmp_path / "big").exists()
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_plain_run_is_lean_and_full_is_opt_in(monkeypatch):
+    """A plain `bench.py` measures the headline alone; `--full` adds everything else, and `--per-op` (measured by the roofline pass) needs it."""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--per-op", "t.tsv"])
+    args = bench.parse()
+    assert args.full and args.per_op == "t.tsv"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--per-op", "t.tsv"])
     with pytest.raises(SystemExit):
         bench.parse()

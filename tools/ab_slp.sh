@@ -4,9 +4,9 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/ab_slp; mkdir -p $O
 run() {
   tag=$1
-  for rep in 1 2; do python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs --no-sequential-leg 2>/dev/null | grep '^{' | tail -1 > $O/line_${tag}_$rep.json; done
-  python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg --lanes 1 --per-op $O/per_op_$tag.tsv 2>/dev/null | grep '^{' | tail -1 > $O/line_${tag}_lanes1.json
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg --frames-per-launch 1 2>/dev/null | grep '^{' | tail -1 > $O/line_${tag}_F1.json
+  for rep in 1 2; do python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs --no-sequential-leg 2>/dev/null | grep '^{' | tail -1 > $O/line_${tag}_$rep.json; done
+  python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg --lanes 1 --per-op $O/per_op_$tag.tsv 2>/dev/null | grep '^{' | tail -1 > $O/line_${tag}_lanes1.json
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg --frames-per-launch 1 2>/dev/null | grep '^{' | tail -1 > $O/line_${tag}_F1.json
 }
 run noslp
 sed -i 's/ -fno-slp-vectorize//' vi_depth_completion_amd/csrc/Makefile

@@ -4,8 +4,8 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/ab_spread; mkdir -p $O
 run() {
   tag=$1
-  for rep in 1 2; do python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg 2>/dev/null | grep '^{' | tail -1 > $O/line_${tag}_$rep.json; done
-  python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg --lanes 1 --per-op $O/per_op_$tag.tsv 2>/dev/null | grep '^{' | tail -1 > $O/line_${tag}_lanes1.json
+  for rep in 1 2; do python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg 2>/dev/null | grep '^{' | tail -1 > $O/line_${tag}_$rep.json; done
+  python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg --lanes 1 --per-op $O/per_op_$tag.tsv 2>/dev/null | grep '^{' | tail -1 > $O/line_${tag}_lanes1.json
 }
 run base
 ( cd vi_depth_completion_amd/csrc && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function -DVIDC_CONV_SPREAD_DMA -c conv_mfma.hip -o conv_mfma.o > /dev/null 2>&1 && make > /dev/null 2>&1 )

@@ -5,8 +5,8 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/ab_wfused; mkdir -p $O
 run() {
   tag=$1; knob=$2
-  for rep in 1 2; do VIDC_WINO_FUSED=$knob python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg 2>$O/err_${tag}_$rep.txt | grep '^{' | tail -1 > $O/line_${tag}_$rep.json; done
-  VIDC_WINO_FUSED=$knob python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg --lanes 1 --per-op $O/per_op_$tag.tsv 2>$O/err_${tag}_l1.txt | grep '^{' | tail -1 > $O/line_${tag}_lanes1.json
+  for rep in 1 2; do VIDC_WINO_FUSED=$knob python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg 2>$O/err_${tag}_$rep.txt | grep '^{' | tail -1 > $O/line_${tag}_$rep.json; done
+  VIDC_WINO_FUSED=$knob python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg --lanes 1 --per-op $O/per_op_$tag.tsv 2>$O/err_${tag}_l1.txt | grep '^{' | tail -1 > $O/line_${tag}_lanes1.json
 }
 run base 0
 run f80 80

@@ -9,8 +9,8 @@ OV41=${OV40//\[40,/[41,}
 OVL3='{"M80_N256_K256_k1s1_G144":[40,64]}'
 run() {
   tag=$1; ov=$2
-  for rep in 1 2; do VIDC_TUNING_OVERRIDE="$ov" python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg 2>$O/err_${tag}_$rep.txt | grep '^{' | tail -1 > $O/line_${tag}_$rep.json; done
-  VIDC_TUNING_OVERRIDE="$ov" python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg --lanes 1 --per-op $O/per_op_$tag.tsv 2>/dev/null | grep '^{' | tail -1 > $O/line_${tag}_lanes1.json
+  for rep in 1 2; do VIDC_TUNING_OVERRIDE="$ov" python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg 2>$O/err_${tag}_$rep.txt | grep '^{' | tail -1 > $O/line_${tag}_$rep.json; done
+  VIDC_TUNING_OVERRIDE="$ov" python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-extra-legs --no-sequential-leg --no-mixed-leg --lanes 1 --per-op $O/per_op_$tag.tsv 2>/dev/null | grep '^{' | tail -1 > $O/line_${tag}_lanes1.json
 }
 run base '{}'
 run s40 "$OV40"

@@ -2,10 +2,10 @@
 # process group of one rank (the stream mode must not depend on it), and the training lines.  One box.   bash tools/evidence_r4_final.sh
 R=$PWD; O=$R/gpurun_out/r4/final; mkdir -p $O
 python -m pytest tests/ -x -q -m gpu > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
-python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > $O/bench_line.json
-python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_second_run.json
-python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extra-legs 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_200.json
-VIDC_DIST_WORLD1=1 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_rccl_world1.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > $O/bench_line.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_second_run.json
+python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-extra-legs 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_200.json
+VIDC_DIST_WORLD1=1 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_rccl_world1.json
 VIDC_TRAIN_PRECISION=bf16 python bench.py --train --batch 8 --steps 20 --warmup 3 2>/dev/null | grep '^{' | tail -1 > $O/train_line_bf16_b8.json
 VIDC_TRAIN_PRECISION=fp32 python bench.py --train --batch 8 --steps 10 --warmup 3 2>/dev/null | grep '^{' | tail -1 > $O/train_line_fp32_b8.json
 VIDC_DIST_WORLD1=1 VIDC_TRAIN_PRECISION=bf16 python bench.py --train --batch 8 --steps 10 --warmup 3 2>/dev/null | grep '^{' | tail -1 > $O/train_line_bf16_b8_rccl_world1_f32_buckets.json

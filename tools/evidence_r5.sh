@@ -2,18 +2,18 @@
 # batch 4, the per-op table and the bench lines, one box.   bash tools/evidence_r5_f4.sh
 R=$PWD; O=$R/gpurun_out/r5/f4; mkdir -p $O
 python -m pytest tests/test_frames_per_launch.py tests/test_configs.py -x -q -m gpu > $O/pytest_stream_mode.log 2>&1; tail -2 $O/pytest_stream_mode.log
-python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > $O/bench_line.json
-python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_second_run.json
-python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extra-legs 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_200.json
-python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extra-legs --lanes 1 --per-op $O/per_op.tsv 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_200_lanes1.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs --frames-per-launch 2 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_two_items_per_launch.json
-VIDC_DIST_WORLD1=1 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_rccl_world1.json
-VIDC_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --no-sequential-leg 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_2ranks_gloo_1gpu.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > $O/bench_line.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_second_run.json
+python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-extra-legs 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_200.json
+python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-extra-legs --lanes 1 --per-op $O/per_op.tsv 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_200_lanes1.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs --frames-per-launch 2 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_two_items_per_launch.json
+VIDC_DIST_WORLD1=1 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-legs 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_rccl_world1.json
+VIDC_DIST_BACKEND=gloo python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --no-sequential-leg 2>/dev/null | grep '^{' | tail -1 > $O/bench_line_2ranks_gloo_1gpu.json
 VIDC_PRECISION=fp32 python tools/group_timeline.py 20 3 4 > $O/timeline_fp32_F4_L3.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-VIDC_PRECISION=fp32 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_fp32 -o r5 -- python3 $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-sequential-leg --no-extra-legs --lanes 1 > $O/bench_line_fp32_profiled_lanes1.json 2> $O/prof_fp32.err
-VIDC_PRECISION=mixed rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_mixed -o r5 -- python3 $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-sequential-leg --no-extra-legs --lanes 1 > $O/bench_line_mixed_profiled_lanes1.json 2> $O/prof_mixed.err
-VIDC_PRECISION=fp32 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_fp32_3 -o r5 -- python3 $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-sequential-leg --no-extra-legs > $O/bench_line_fp32_profiled.json 2> $O/prof_fp32_3.err
+VIDC_PRECISION=fp32 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_fp32 -o r5 -- python3 $R/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-sequential-leg --no-extra-legs --lanes 1 > $O/bench_line_fp32_profiled_lanes1.json 2> $O/prof_fp32.err
+VIDC_PRECISION=mixed rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_mixed -o r5 -- python3 $R/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-sequential-leg --no-extra-legs --lanes 1 > $O/bench_line_mixed_profiled_lanes1.json 2> $O/prof_mixed.err
+VIDC_PRECISION=fp32 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_fp32_3 -o r5 -- python3 $R/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-sequential-leg --no-extra-legs > $O/bench_line_fp32_profiled.json 2> $O/prof_fp32_3.err
 cd $R
 for d in prof_fp32 prof_mixed prof_fp32_3; do python tools/kernel_breakdown.py $(find $O/$d -name 'r5_kernel_trace.csv') 25 warp_fwd_kernel 12 > $O/frame_breakdown_$d.txt 2>&1; cp $(find $O/$d -name 'r5_kernel_stats.csv') $O/kernel_stats_$d.csv; rm -rf $O/$d; done
 cd /tmp

@@ -11,7 +11,7 @@ done
 cp vi_depth_completion_amd/conv_tuning.json $OUT/conv_tuning_gemms.json
 FPL=$B
 for w in 0 2 4; do
-  VIDC_WINOGRAD=$w python bench.py --height $H --frames-per-launch $FPL --steps 24 --warmup 12 --no-cpu-baseline --no-extra-legs --no-sequential-leg --per-op $OUT/per_op_w${w}_b${B}_h${H}.tsv > $OUT/bench_w${w}_b${B}_h${H}.json 2> $OUT/bench_w${w}_b${B}_h${H}.err
+  VIDC_WINOGRAD=$w python bench.py --full --height $H --frames-per-launch $FPL --steps 24 --warmup 12 --no-cpu-baseline --no-extra-legs --no-sequential-leg --per-op $OUT/per_op_w${w}_b${B}_h${H}.tsv > $OUT/bench_w${w}_b${B}_h${H}.json 2> $OUT/bench_w${w}_b${B}_h${H}.err
 done
 python tools/winograd_select.py --fp32 $OUT/per_op_w{0,2,4}_b${B}_h${H}.tsv.fp32 --mixed $OUT/per_op_w{0,2,4}_b${B}_h${H}.tsv > $OUT/select_b${B}_h${H}.log 2>&1
 tail -40 $OUT/select_b${B}_h${H}.log

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Chooses, per 3x3 / stride-1 layer, between the direct MFMA conv and the Winograd forms F(2x2,3x3) / F(4x4,3x3) from per-op timing
-tables of the SAME program recorded three times (bench.py --per-op under VIDC_WINOGRAD=0, 2, 4; HIP events between ops, rescaled to
+tables of the SAME program recorded three times (bench.py --full --per-op under VIDC_WINOGRAD=0, 2, 4; HIP events between ops, rescaled to
 the graph replay time), and writes the choice into conv_tuning.json as "W:<direct signature>": [m_fp32, m_mixed] (m = 0, 2 or 4).
 A Winograd layer's time = wino_in + the grouped GEMM launch + wino_out.  CPU only.
 
