@@ -75,6 +75,18 @@ int vidc_warp2dof_fwd(const float* x, const float* params, float* y, int B, int 
 int vidc_warp2dof_inv_rot_norm(const float* x, const float* params, float* z, int B, int H, int W, float cx, float cy,
                                int align_corners, int normalize, vidc_stream_t stream);
 
+/* dx of vidc_warp2dof_fwd (warping_2dof_alignment.py:108-156 differentiated w.r.t. the image): the transposed bilinear gather,
+ * dx[b,c,p] = sum over the output pixels q whose four taps include p of w(q,p) * dy[b,c,q].  Gather form -- a thread owns a source
+ * pixel and walks the window of output pixels its 2x2-pixel support maps to, re-deriving their taps with the forward's own
+ * functions -- so the result is bit-identical from run to run.  `params`: the record of vidc_warp2dof_params. */
+int vidc_warp2dof_fwd_backward(const float* dy, const float* params, float* dx, int B, int C, int H, int W, float cx, float cy,
+                               int align_corners, vidc_stream_t stream);
+/* dx of vidc_warp2dof_inv_rot_norm (warping_2dof_alignment.py:216-255 + surface_normal.py:170) through its three stages in one
+ * kernel: F.normalize (z = R^T y recomputed from x; skipped when normalize == 0), the rotation and the transposed gather.  Gather
+ * form, bit-identical from run to run.  x: the forward's input (B,3,H,W), dz: the gradient of its output. */
+int vidc_warp2dof_inv_rot_norm_backward(const float* x, const float* dz, const float* params, float* dx, int B, int H, int W,
+                                        float cx, float cy, int align_corners, int normalize, vidc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * conv + BN + ReLU stacks           (networks/surface_normal.py:10-145, networks/depth_completion.py:16-147)
  * ---------------------------------------------------------------------------------------------- */
@@ -630,6 +642,18 @@ int vidc_im2col_transposed_bf16(const void* x_bf16, void* xt_bf16, int B, int H,
                                 int Mp, vidc_stream_t stream);
 int vidc_wgrad_permute(const float* tmp, float* dw_oihw, int Cout, int Cin, int taps, vidc_stream_t stream);
 /* wgrad of the 3x3 / stride-2 stem conv on the NCHW network input (Cin = 1 or 3). */
+/* The epilogue of vidc_conv2d_bn_act, y = relu?(c * scale + shift) on NHWC rows, transposed in one pass (Conv2d + eval BatchNorm2d + ReLU
+ * differentiated behind the raw conv output c): dc = mask(dy) * scale, dshift[ch] = sum mask(dy), dscale[ch] = sum mask(dy) * c with
+ * c = (y - shift) / scale; channels with scale == 0 read c from c_raw (row stride |ldc|; may be NULL when there is no such channel),
+ * and with ldc < 0 every channel does (for a forward whose y is not an fp32-accurate image of c: bf16x3, Winograd).
+ * Sums: fp64 chunk partials reduced in a fixed order.  scratch: vidc_train_scratch_bytes(M, C).  dy, y, dc 16-byte aligned. */
+int vidc_affine_act_backward(const float* dy, const float* y, const float* c_raw, const float* scale, const float* shift, float* dc,
+                             float* dscale, float* dshift, long long M, int C, int lddy, int ldy, int ldc, int lddc, int relu, void* scratch,
+                             vidc_stream_t stream);
+/* dx (NCHW, Cin <= 4) of vidc_stem_conv3x3s2 (surface_normal.py:36 differentiated w.r.t. its input); y_relu: the forward output when the
+ * ReLU was applied (its mask is applied to dy), else NULL.  Gather form, bit-identical from run to run. */
+int vidc_stem_conv3x3s2_backward_data(const float* dy, const float* y_relu, const float* w_oihw, float* dx_nchw, int B, int Cin, int H, int W,
+                                      int Cout, int lddy, int ldy, vidc_stream_t stream);
 size_t vidc_stem_wgrad_scratch_bytes(int B, int Cin, int H, int W, int Cout);
 int vidc_stem_wgrad(const float* dy, const float* x_nchw, float* dw_oihw, int B, int Cin, int H, int W, int Cout, int lddy, void* scratch,
                     vidc_stream_t stream);

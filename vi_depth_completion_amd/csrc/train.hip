@@ -1642,3 +1642,139 @@ extern "C" size_t vidc_stem_wgrad_scratch_bytes(int B, int Cin, int H, int W, in
     const long long M = (long long)B * Ho * Wo;
     return (size_t)((M + kStemRows - 1) / kStemRows) * (size_t)Cout * Cin * 9 * sizeof(double);
 }
+
+// ---- backward of the per-op surface (torch.ops.vidc.*, torch_ops.py) ------------------------------------------------------------------------
+namespace {
+
+// The epilogue of vidc_conv2d_bn_act, y = relu?(c * scale + shift), transposed in one pass over the NHWC rows: dc = mask(dy) * scale (the operand
+// of dgrad and wgrad) and the chunk sums of mask(dy) and mask(dy) * c in fp64, c = (y - shift) / scale -- where the mask is open y determines c,
+// where it is closed the term is zero.  A channel with scale == 0 reads c from `craw` (the conv re-run with an identity epilogue; the caller
+// passes it only when such a channel exists), with all_raw every channel does (a forward whose y is not an fp32-accurate image of c).
+// Block / grid / summation order: chan_partial_kernel's.
+__global__ void __launch_bounds__(TT)
+affine_act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ craw, const float* __restrict__ scale,
+                      const float* __restrict__ shift, float* __restrict__ dc, long long M, int C, int lddy, int ldy, int ldc, int lddc, int relu,
+                      int all_raw, int rows_per_chunk, double* __restrict__ partial) {
+    __shared__ double red[2][16][64];
+    const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    const int c = blockIdx.x * 64 + cq * 4;
+    const long long r0 = (long long)blockIdx.y * rows_per_chunk, r1 = min(M, r0 + rows_per_chunk);
+    double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
+    if (c < C) {
+        float sc[4], sh[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { sc[k] = scale[c + k]; sh[k] = shift[c + k]; }
+        for (long long r = r0 + rl; r < r1; r += 16) {
+            const float4 gv = *reinterpret_cast<const float4*>(dy + r * lddy + c);
+            const float4 yv4 = *reinterpret_cast<const float4*>(y + r * ldy + c);
+            float g[4] = {gv.x, gv.y, gv.z, gv.w};
+            const float yv[4] = {yv4.x, yv4.y, yv4.z, yv4.w};
+            float o[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (relu && !(yv[k] > 0.f)) g[k] = 0.f;
+                float cv;
+                if (sc[k] != 0.f && !all_raw) cv = (yv[k] - sh[k]) / sc[k];
+                else cv = craw ? craw[r * ldc + c + k] : 0.f;
+                s0[k] += (double)g[k];
+                s1[k] += (double)g[k] * (double)cv;
+                o[k] = g[k] * sc[k];
+            }
+            *reinterpret_cast<float4*>(dc + r * lddc + c) = make_float4(o[0], o[1], o[2], o[3]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { red[0][rl][cq * 4 + k] = s0[k]; red[1][rl][cq * 4 + k] = s1[k]; }
+    __syncthreads();
+    if (threadIdx.x < 128) {                       // 64 channels x 2 sums; row-lanes added in order 0..15
+        const int q = threadIdx.x >> 6, l = threadIdx.x & 63, cc = blockIdx.x * 64 + l;
+        if (cc < C) {
+            double t = 0.0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) t += red[q][j][l];
+            partial[((size_t)blockIdx.y * 2 + q) * C + cc] = t;
+        }
+    }
+}
+
+// dx (NCHW) of the 3x3 / stride-2 / pad-1 stem conv, gather form: one thread per input pixel and all Cin channels; the up to 2 x 2 output pixels
+// whose window holds it are read as NHWC rows (ReLU mask from y), the weights from LDS as [tap][ci][co].  Fixed order (ky, kx, co): reproducible.
+__global__ void __launch_bounds__(256)
+stem_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ w_oihw, float* __restrict__ dx, int B, int Cin,
+                  int H, int W, int Ho, int Wo, int Cout, int lddy, int ldy) {
+    extern __shared__ float ws[];
+    for (int i = threadIdx.x; i < Cout * Cin * 9; i += blockDim.x) {
+        const int co = i / (Cin * 9), r = i - co * (Cin * 9), ci = r / 9, t = r - ci * 9;
+        ws[(t * Cin + ci) * Cout + co] = w_oihw[i];
+    }
+    __syncthreads();
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)B * H * W) return;
+    const int ix = (int)(idx % W), iy = (int)((idx / W) % H), b = (int)(idx / ((long long)W * H));
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int ky = 0; ky < 3; ++ky) {
+        const int ty = iy + 1 - ky;
+        if (ty < 0 || (ty & 1) || (ty >> 1) >= Ho) continue;
+        for (int kx = 0; kx < 3; ++kx) {
+            const int tx = ix + 1 - kx;
+            if (tx < 0 || (tx & 1) || (tx >> 1) >= Wo) continue;
+            const size_t row = ((size_t)b * Ho + (ty >> 1)) * Wo + (tx >> 1);
+            const float* g = dy + row * lddy;
+            const float* yy = y ? y + row * ldy : nullptr;
+            const float* wt = ws + (size_t)(ky * 3 + kx) * Cin * Cout;
+            for (int co = 0; co < Cout; co += 4) {
+                float4 gv = *reinterpret_cast<const float4*>(g + co);
+                if (yy) {
+                    const float4 yv = *reinterpret_cast<const float4*>(yy + co);
+                    if (!(yv.x > 0.f)) gv.x = 0.f;
+                    if (!(yv.y > 0.f)) gv.y = 0.f;
+                    if (!(yv.z > 0.f)) gv.z = 0.f;
+                    if (!(yv.w > 0.f)) gv.w = 0.f;
+                }
+                for (int ci = 0; ci < Cin; ++ci) {
+                    const float* wc = wt + ci * Cout + co;
+                    acc[ci] = fmaf(gv.w, wc[3], fmaf(gv.z, wc[2], fmaf(gv.y, wc[1], fmaf(gv.x, wc[0], acc[ci]))));
+                }
+            }
+        }
+    }
+    const size_t plane = (size_t)H * W;
+    float* o = dx + (size_t)b * Cin * plane + (size_t)iy * W + ix;
+    for (int ci = 0; ci < Cin; ++ci) o[ci * plane] = acc[ci];
+}
+
+}  // namespace
+
+extern "C" int vidc_affine_act_backward(const float* dy, const float* y, const float* c_raw, const float* scale, const float* shift, float* dc,
+                                        float* dscale, float* dshift, long long M, int C, int lddy, int ldy, int ldc, int lddc, int relu, void* scratch,
+                                        vidc_stream_t stream) {
+    VIDC_REQUIRE(dy && y && scale && shift && dc && dscale && dshift && scratch, VIDC_ERR_NULL, "vidc_affine_act_backward: null pointer");
+    VIDC_REQUIRE(M > 0 && C > 0 && C % 4 == 0 && lddy >= C && ldy >= C && lddc >= C && lddy % 4 == 0 && ldy % 4 == 0 && lddc % 4 == 0 &&
+                 (!c_raw || ldc >= C || -ldc >= C), VIDC_ERR_SHAPE, "vidc_affine_act_backward: bad shape (C and the row strides multiples of 4)");
+    VIDC_REQUIRE(((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dc)) & 15) == 0, VIDC_ERR_SHAPE,
+                 "vidc_affine_act_backward: dy, y and dc must be 16-byte aligned");
+    hipStream_t st = vidc::as_stream(stream);
+    const int nch = chunks_for(M, C);
+    double* partial = reinterpret_cast<double*>(scratch);
+    double* sums = partial + (size_t)nch * 2 * C;
+    hipLaunchKernelGGL(affine_act_bwd_kernel, dim3((C + 63) / 64, nch), dim3(TT), 0, st, dy, y, c_raw, scale, shift, dc, M, C, lddy, ldy,
+                       ldc < 0 ? -ldc : ldc, lddc, relu, (c_raw && ldc < 0) ? 1 : 0, rows_for(M, C), partial);
+    hipLaunchKernelGGL(chan_final_kernel<FinalParamGrad>, dim3((C + 7) / 8), dim3(TT), 0, st, partial, nch, C, sums, FinalParamGrad{dscale, dshift});
+    VIDC_CHECK_LAUNCH("affine_act_backward");
+    return VIDC_OK;
+}
+
+extern "C" int vidc_stem_conv3x3s2_backward_data(const float* dy, const float* y_relu, const float* w_oihw, float* dx_nchw, int B, int Cin, int H, int W,
+                                                 int Cout, int lddy, int ldy, vidc_stream_t stream) {
+    VIDC_REQUIRE(dy && w_oihw && dx_nchw, VIDC_ERR_NULL, "vidc_stem_conv3x3s2_backward_data: null pointer");
+    VIDC_REQUIRE(B > 0 && Cin > 0 && Cin <= 4 && H > 0 && W > 0 && Cout > 0 && Cout % 4 == 0 && lddy >= Cout && lddy % 4 == 0 &&
+                 (!y_relu || (ldy >= Cout && ldy % 4 == 0)) && (size_t)Cout * Cin * 9 * sizeof(float) <= 48 * 1024, VIDC_ERR_SHAPE,
+                 "vidc_stem_conv3x3s2_backward_data: bad shape (Cin <= 4, Cout and the row strides multiples of 4, weights within 48 KiB of LDS)");
+    VIDC_REQUIRE(((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(y_relu)) & 15) == 0, VIDC_ERR_SHAPE,
+                 "vidc_stem_conv3x3s2_backward_data: dy and y must be 16-byte aligned");
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    hipLaunchKernelGGL(stem_dgrad_kernel, dim3(blocks((long long)B * H * W)), dim3(256), (size_t)Cout * Cin * 9 * sizeof(float), vidc::as_stream(stream), dy,
+                       y_relu, w_oihw, dx_nchw, B, Cin, H, W, Ho, Wo, Cout, lddy, ldy);
+    VIDC_CHECK_LAUNCH("stem_dgrad_kernel");
+    return VIDC_OK;
+}

@@ -320,3 +320,188 @@ def shader_clock_ghz(stamps, a, b):
     sb = {int(r[0]): (int(r[1]), int(r[2])) for r in h[b] if int(r[3]) == 1}
     ghz = sorted((sb[x][0] - sa[x][0]) / (sb[x][1] - sa[x][1]) * 0.1 for x in sa if x in sb and sb[x][1] > sa[x][1] and sb[x][0] > sa[x][0])
     return ghz[len(ghz) // 2] if ghz else None
+
+
+# ---- backward of the per-op surface (torch_ops.py registers these as the autograd formulas of torch.ops.vidc.*) ------------------------
+def _scratch(nbytes, device):
+    return torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
+
+
+def warp2dof_fwd_backward(dy, params, cx, cy, align_corners):
+    """dx of vidc_warp2dof_fwd: dy (B,C,H,W), params the (B,32) record of vidc_warp2dof_params."""
+    _dev(dy, params)
+    dy = dy.contiguous().float()
+    B, Cc, H, W = dy.shape
+    dx = torch.empty_like(dy)
+    L.check(L.lib().vidc_warp2dof_fwd_backward(L.ptr(dy), L.ptr(params), L.ptr(dx), B, Cc, H, W, float(cx), float(cy), int(align_corners),
+                                               L.current_stream()), "warp2dof_fwd_backward")
+    return dx
+
+
+def warp2dof_inv_rot_norm_backward(x, dz, params, cx, cy, align_corners, normalize):
+    """dx of vidc_warp2dof_inv_rot_norm: x the forward's input (B,3,H,W), dz the gradient of its output."""
+    _dev(x, dz, params)
+    x, dz = x.contiguous().float(), dz.contiguous().float()
+    B, _c, H, W = x.shape
+    dx = torch.empty_like(x)
+    L.check(L.lib().vidc_warp2dof_inv_rot_norm_backward(L.ptr(x), L.ptr(dz), L.ptr(params), L.ptr(dx), B, H, W, float(cx), float(cy),
+                                                        int(align_corners), int(normalize), L.current_stream()), "warp2dof_inv_rot_norm_backward")
+    return dx
+
+
+def affine_act_backward(dy, y, scale, shift, relu, c_raw=None, all_from_raw=False):
+    """The conv epilogue y = relu?(c * scale + shift) transposed: (dc, dscale, dshift) from NHWC dy, y (vidc_affine_act_backward).  c_raw: the raw
+    conv output, read for the channels whose scale is 0 -- or, with all_from_raw, for every channel (ldc < 0 in the C call)."""
+    _dev(dy, y, scale, shift, c_raw)
+    dy, y = dy.contiguous().float(), y.contiguous()
+    Cc = y.shape[-1]
+    M = y.numel() // Cc
+    s, b = scale.contiguous().float(), shift.contiguous().float()
+    c_raw = c_raw.contiguous() if c_raw is not None else None
+    dc = torch.empty_like(y)
+    dscale, dshift = torch.empty_like(s), torch.empty_like(b)
+    sc = _scratch(L.lib().vidc_train_scratch_bytes(M, Cc), y.device)
+    L.check(L.lib().vidc_affine_act_backward(L.ptr(dy), L.ptr(y), L.ptr(c_raw), L.ptr(s), L.ptr(b), L.ptr(dc), L.ptr(dscale), L.ptr(dshift), M, Cc,
+                                             Cc, Cc, -Cc if (all_from_raw and c_raw is not None) else Cc, Cc, int(relu), L.ptr(sc), L.current_stream()),
+            "affine_act_backward")
+    return dc, dscale, dshift
+
+
+def pack_conv_weight_dgrad(w_oihw, precision=0):
+    """OIHW -> the weights of the data-gradient conv (kernel flipped, channels transposed) in the format of `precision` (0 fp32, 1 bf16x3)."""
+    _dev(w_oihw)
+    w = w_oihw.contiguous().float()
+    co, ci, kh, kw = w.shape
+    out = torch.empty((ci, kh * kw * co), dtype=torch.float32, device=w.device)
+    if precision == L.PREC_FP32:
+        L.check(L.lib().vidc_pack_conv_weight_dgrad(L.ptr(w), L.ptr(out), co, ci, kh, kw, L.current_stream()), "pack_conv_weight_dgrad")
+        return out
+    if precision != L.PREC_BF16X3:
+        raise RuntimeError("pack_conv_weight_dgrad: precision %d has no data-gradient form" % precision)
+    kind = 3
+    nb = L.lib().vidc_pack_item_blocks(co, ci, kh, kw, kind)
+    if nb <= 0:
+        raise RuntimeError("conv weight %dx%dx%dx%d cannot be packed for the bf16x3 data gradient (Cout a multiple of 32, kernels up to 3x3)" % (co, ci, kh, kw))
+    item = (L.PackItem * 1)()
+    item[0].w, item[0].packed, item[0].Cout, item[0].Cin, item[0].KH, item[0].KW, item[0].kind, item[0].block_begin = L.ptr(w), L.ptr(out), co, ci, kh, kw, kind, 0
+    dev = torch.frombuffer(bytearray(bytes(item)), dtype=torch.uint8).to(w.device)
+    L.check(L.lib().vidc_pack_conv_weights_batched(L.ptr(dev), 1, nb, L.current_stream()), "pack_conv_weights_batched")
+    return out
+
+
+def conv_backward_data(dc, w_oihw, H, W, stride, pad, precision=0):
+    """dx NHWC (B,H,W,Cin) of a conv from the gradient dc of its raw output: vidc_zero_stuff (stride > 1) + the conv kernel on the
+    data-gradient weights, in the arithmetic of `precision` (the sequence DepthCompletionTrainer.conv records)."""
+    _dev(dc, w_oihw)
+    dc = dc.contiguous()
+    co, ci, kh, kw = w_oihw.shape
+    B, Ho, Wo, _c = dc.shape
+    if kh != kw or kh - 1 - pad < 0 or (stride > 1 and 2 * pad > kh - 1):
+        raise RuntimeError("conv data gradient: unsupported geometry %dx%d stride %d pad %d (square kernels, pad <= k-1, and pad <= (k-1)/2 when strided)"
+                           % (kh, kw, stride, pad))
+    wd = pack_conv_weight_dgrad(w_oihw, precision)
+    g = dc
+    if stride > 1:
+        g = torch.empty((B, H, W, co), dtype=torch.float32, device=dc.device)
+        L.check(L.lib().vidc_zero_stuff(L.ptr(dc), L.ptr(g), B, Ho, Wo, co, co, stride, H, W, L.current_stream()), "zero_stuff")
+    one, zero = torch.ones(ci, dtype=torch.float32, device=dc.device), torch.zeros(ci, dtype=torch.float32, device=dc.device)
+    dx = conv2d_bn_act(g, wd, one, zero, kh, kw, stride=1, pad=kh - 1 - pad, precision=precision)
+    if dx.shape[1] != H or dx.shape[2] != W:        # a strided conv whose padding is below "same": the rows / columns past the input are not its gradient
+        dx = dx[:, :H, :W].contiguous()
+    return dx
+
+
+def conv_backward_weight(dc, x, w_shape, stride, pad):
+    """dw OIHW (fp32) from the gradient dc of the raw conv output and the conv's NHWC input (vidc_conv_wgrad)."""
+    _dev(dc, x)
+    dc, x = dc.contiguous(), x.contiguous()
+    co, ci, kh, kw = w_shape
+    B, H, W, _c = x.shape
+    _b, Ho, Wo, _co = dc.shape
+    dw = torch.empty((co, ci, kh, kw), dtype=torch.float32, device=x.device)
+    sc = _scratch(L.lib().vidc_conv_wgrad_scratch_bytes(B, Ho, Wo, co, ci, kh, kw), x.device)
+    L.check(L.lib().vidc_conv_wgrad(L.ptr(dc), L.ptr(x), L.ptr(dw), B, H, W, ci, ci, Ho, Wo, co, co, kh, kw, stride, pad, L.ptr(sc), L.current_stream()),
+            "conv_wgrad")
+    return dw
+
+
+def relu_backward(dy, y):
+    """dy * (y > 0) for tensors of any shape (the kernel works on rows of four)."""
+    _dev(dy, y)
+    dy, y = dy.contiguous().float(), y.contiguous()
+    n = dy.numel()
+    if n % 4:
+        pad = 4 - n % 4
+        dy, y = torch.nn.functional.pad(dy.reshape(-1), (0, pad)), torch.nn.functional.pad(y.reshape(-1), (0, pad))
+    out = torch.empty_like(dy)
+    L.check(L.lib().vidc_relu_backward(L.ptr(dy), L.ptr(y), L.ptr(out), dy.numel() // 4, 4, 4, 4, 4, 0, L.current_stream()), "relu_backward")
+    return out.reshape(-1)[:n].reshape(y.shape) if n % 4 else out
+
+
+def stem_conv3x3s2_backward_data(dy, y, w_oihw, H, W, relu=True):
+    """dx NCHW of stem_conv3x3s2; y: the forward output (read for the ReLU mask when relu)."""
+    _dev(dy, y, w_oihw)
+    dy, w = dy.contiguous().float(), w_oihw.contiguous().float()
+    B, _ho, _wo, co = dy.shape
+    cin = w.shape[1]
+    y = y.contiguous() if relu else None
+    dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dy.device)
+    L.check(L.lib().vidc_stem_conv3x3s2_backward_data(L.ptr(dy), L.ptr(y), L.ptr(w), L.ptr(dx), B, cin, H, W, co, co, co, L.current_stream()),
+            "stem_conv3x3s2_backward_data")
+    return dx
+
+
+def stem_conv3x3s2_backward_weight(dy, y, x_nchw, w_shape, relu=True):
+    _dev(dy, y, x_nchw)
+    x = x_nchw.contiguous().float()
+    B, cin, H, W = x.shape
+    co = w_shape[0]
+    g = relu_backward(dy, y) if relu else dy.contiguous().float()
+    dw = torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
+    sc = _scratch(L.lib().vidc_stem_wgrad_scratch_bytes(B, cin, H, W, co), x.device)
+    L.check(L.lib().vidc_stem_wgrad(L.ptr(g), L.ptr(x), L.ptr(dw), B, cin, H, W, co, co, L.ptr(sc), L.current_stream()), "stem_wgrad")
+    return dw
+
+
+def maxpool3x3s2_backward(dy, x):
+    _dev(dy, x)
+    dy, x = dy.contiguous().float(), x.contiguous()
+    B, H, W, Cc = x.shape
+    dx = torch.empty_like(x)
+    L.check(L.lib().vidc_maxpool3x3s2_backward(L.ptr(x), L.ptr(dy), L.ptr(dx), B, H, W, Cc, Cc, Cc, Cc, L.current_stream()), "maxpool3x3s2_backward")
+    return dx
+
+
+def upsample_bilinear_ac_backward(dy, size_in, y=None):
+    """dx NHWC (B,h,w,C) of upsample_bilinear_ac; y: the forward output when its ReLU was applied."""
+    _dev(dy, y)
+    dy = dy.contiguous().float()
+    B, H, W, Cc = dy.shape
+    if y is not None:
+        dy = relu_backward(dy, y)
+    dx = torch.empty((B, size_in[0], size_in[1], Cc), dtype=torch.float32, device=dy.device)
+    L.check(L.lib().vidc_upsample_bilinear_ac_backward(L.ptr(dy), L.ptr(dx), B, size_in[0], size_in[1], Cc, Cc, Cc, H, W, L.current_stream()),
+            "upsample_bilinear_ac_backward")
+    return dx
+
+
+def head_conv1x1_upsample_backward(dy, x, w, pad, y=None):
+    """(dx NHWC, dw, dbias) of head_conv1x1_upsample for one output channel and pad 1 (vidc_head_backward); y: the forward output when relu."""
+    _dev(dy, x, w, y)
+    x = x.contiguous()
+    B, h, wd, cin = x.shape
+    w2 = w.reshape(w.shape[0], -1).contiguous().float()
+    if w2.shape[0] != 1 or pad != 1:
+        raise RuntimeError("head_conv1x1_upsample backward: one output channel and pad 1 only (got Cout %d, pad %d)" % (w2.shape[0], pad))
+    dy = dy.contiguous().float()
+    H, W = dy.shape[2], dy.shape[3]
+    g = relu_backward(dy, y) if y is not None else dy
+    g_low = torch.empty((B, h + 2, wd + 2), dtype=torch.float32, device=x.device)
+    L.check(L.lib().vidc_upsample_bilinear_ac_backward(L.ptr(g), L.ptr(g_low), B, h + 2, wd + 2, 1, 1, 1, H, W, L.current_stream()), "upsample_bilinear_ac_backward")
+    dx = torch.empty_like(x)
+    dw = torch.empty(w.shape, dtype=torch.float32, device=x.device)
+    db = torch.empty((1,), dtype=torch.float32, device=x.device)
+    sc = _scratch(L.lib().vidc_head_backward_scratch_bytes(B, h, wd, cin), x.device)
+    L.check(L.lib().vidc_head_backward(L.ptr(g_low), L.ptr(x), L.ptr(w2), L.ptr(dx), L.ptr(dw), L.ptr(db), B, h, wd, cin, cin, cin, L.ptr(sc),
+                                       L.current_stream()), "head_backward")
+    return dx, dw, db

@@ -23,8 +23,19 @@ the operators are the per-op surface for callers that compose the kernels with o
     torch.ops.vidc.enrich_scatter(plane_depth, sparse_depth, sub, sub_offsets, chunk_base)        main.py:286, 290-294
 (the host-side draws that feed them -- np.random.permutation / randint in the reference's order -- are plane.draw_normal_hypotheses
 and plane.draw_enrichment; plane.PlaneBlock is the composition the pipeline uses)
+
+Autograd.  The first eight operators (the warps, the convs and the glue) are differentiable: each has a backward registered with
+`torch.library.register_autograd`, and each backward formula is itself a custom operator (`torch.ops.vidc.*_backward`, listed in
+BACKWARD_OPS) with a shape function, built from HIP kernels only -- the warp adjoints of csrc/warp.hip, vidc_affine_act_backward +
+zero-stuffing + the conv kernel on data-gradient weights + vidc_conv_wgrad for the convs (precision 0 and 1; Winograd forwards share the
+direct form's backward; the data gradient runs in exact fp32 except behind a Winograd forward at precision 1, where it runs in bf16x3 like
+the forward), the backward kernels of csrc/train.hip for the glue.  Gradients flow to images / activations, conv weights, the
+folded scale / shift and the head's bias; only those `ctx.needs_input_grad` asks for are computed, and nothing is saved when gradients are
+disabled.  `gravity` / `aligned` get no gradient (the warp record is built with cosf / atan2f / bbox min-max) and precision 3 (MXFP8) has no
+backward: requesting either raises.  The head's backward covers one output channel with pad 1 (vidc_head_backward).  Double backward is
+not supported.  The plane operators (`plane_*`, `enrich_scatter`) stay non-differentiable: they are RANSAC decisions and index scatters.
 """
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -248,5 +259,265 @@ def _(plane_depth, sparse_depth, sub, sub_offsets, chunk_base):
     return torch.empty_like(sparse_depth)
 
 
-OPS = ("plane_ransac_normal", "plane_offset", "plane_project_depth", "plane_finalize", "enrich_scatter", "warp2dof_fwd", "warp2dof_inv_rot_norm", "conv2d_bn_act", "stem_conv3x3s2", "maxpool3x3s2", "upsample_bilinear_ac",
-       "head_conv1x1_upsample")
+# ---- autograd: backward operators + their registration ----------------------------------------------------------------------------
+def _none_if_empty(t):
+    return t if t.numel() else None
+
+
+def _no_geometry_grad(ctx, what, i_gravity, i_aligned):
+    if ctx.needs_input_grad[i_gravity] or ctx.needs_input_grad[i_aligned]:
+        raise RuntimeError("torch.ops.vidc.%s: gravity / aligned are not differentiable (the warp record is built with cosf / atan2f / bbox "
+                           "min-max); detach them" % what)
+
+
+@torch.library.custom_op("vidc::warp2dof_fwd_backward", mutates_args=(), device_types=_DEV)
+def warp2dof_fwd_backward(dy: torch.Tensor, gravity: torch.Tensor, aligned: torch.Tensor, fx: float, fy: float, cx: float, cy: float,
+                          align_corners: bool) -> torch.Tensor:
+    """dx of warp2dof_fwd: the transposed bilinear gather (vidc_warp2dof_fwd_backward)."""
+    wp = _warper(dy, fx, fy, cx, cy, align_corners)
+    assert tuple(dy.shape[-2:]) == (wp.H, wp.W)
+    return _ops.warp2dof_fwd_backward(dy, wp._params(gravity, aligned), cx, cy, align_corners)
+
+
+@warp2dof_fwd_backward.register_fake
+def _(dy, gravity, aligned, fx, fy, cx, cy, align_corners):
+    return torch.empty_like(dy)
+
+
+def _warp_fwd_setup(ctx, inputs, output):
+    x, gravity, aligned, fx, fy, cx, cy, align_corners = inputs
+    _no_geometry_grad(ctx, "warp2dof_fwd", 1, 2)
+    ctx.save_for_backward(gravity, aligned)
+    ctx.args = (fx, fy, cx, cy, align_corners)
+
+
+def _warp_fwd_backward(ctx, _grad_h, grad_y):
+    gravity, aligned = ctx.saved_tensors
+    return (torch.ops.vidc.warp2dof_fwd_backward(grad_y, gravity, aligned, *ctx.args),) + (None,) * 7
+
+
+torch.library.register_autograd("vidc::warp2dof_fwd", _warp_fwd_backward, setup_context=_warp_fwd_setup)
+
+
+@torch.library.custom_op("vidc::warp2dof_inv_rot_norm_backward", mutates_args=(), device_types=_DEV)
+def warp2dof_inv_rot_norm_backward(x: torch.Tensor, dz: torch.Tensor, gravity: torch.Tensor, aligned: torch.Tensor, fx: float, fy: float,
+                                   cx: float, cy: float, align_corners: bool, normalize: bool) -> torch.Tensor:
+    """dx of warp2dof_inv_rot_norm through normalize, rotation and gather (vidc_warp2dof_inv_rot_norm_backward)."""
+    wp = _warper(x, fx, fy, cx, cy, align_corners)
+    assert tuple(x.shape[-2:]) == (wp.H, wp.W) and x.shape == dz.shape
+    return _ops.warp2dof_inv_rot_norm_backward(x, dz, wp._params(gravity, aligned), cx, cy, align_corners, normalize)
+
+
+@warp2dof_inv_rot_norm_backward.register_fake
+def _(x, dz, gravity, aligned, fx, fy, cx, cy, align_corners, normalize):
+    return torch.empty_like(x)
+
+
+def _warp_inv_setup(ctx, inputs, output):
+    x, gravity, aligned, fx, fy, cx, cy, align_corners, normalize = inputs
+    _no_geometry_grad(ctx, "warp2dof_inv_rot_norm", 1, 2)
+    ctx.save_for_backward(x if normalize else x.new_empty(0), gravity, aligned)      # (the linear form reads no x)
+    ctx.args = (fx, fy, cx, cy, align_corners, normalize)
+
+
+def _warp_inv_backward(ctx, _grad_h, grad_z):
+    x, gravity, aligned = ctx.saved_tensors
+    if not x.numel():
+        x = grad_z
+    return (torch.ops.vidc.warp2dof_inv_rot_norm_backward(x, grad_z, gravity, aligned, *ctx.args),) + (None,) * 8
+
+
+torch.library.register_autograd("vidc::warp2dof_inv_rot_norm", _warp_inv_backward, setup_context=_warp_inv_setup)
+
+
+@torch.library.custom_op("vidc::conv2d_bn_act_backward", mutates_args=(), device_types=_DEV)
+def conv2d_bn_act_backward(dy: torch.Tensor, x_nhwc: Optional[torch.Tensor], w_oihw: torch.Tensor, y: torch.Tensor, scale: torch.Tensor,
+                           shift: torch.Tensor, in_h: int, in_w: int, stride: int, pad: int, relu: bool, precision: int, need_x: bool,
+                           need_w: bool, need_affine: bool, recompute_c: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dw, dscale, dshift) of relu?(conv(x, w) * scale + shift); a gradient that is not needed comes back empty.  The epilogue is
+    transposed first (vidc_affine_act_backward -> dc, dscale, dshift); dx = the conv kernel on data-gradient weights over dc (zero-stuffed when
+    strided) in the arithmetic of `precision`; dw = vidc_conv_wgrad in fp32.  `precision` here is the data gradient's: the forward's for a
+    Winograd forward, 0 for the direct form -- tests/test_torch_ops.py holds the direct form at precision 1 to the fp32 tolerance, so its
+    gradient is held to fp32 accuracy as well, which split-bf16 products (~2^-16 each) miss by 1.5-6 x (profiles/EXPERIMENTS.md); Winograd
+    at precision 1 is granted 10 x fp32 and keeps the faster arithmetic.  dscale sums mask(dy) * c with c = (y - shift) / scale; with
+    recompute_c (the forward ran in bf16x3 or as Winograd, whose y is not an fp32-accurate image of c), and for channels whose scale is 0, c
+    is read from a re-run of the conv in the direct fp32 form with an identity epilogue, so that dscale is an fp32 result like dw and dshift.
+    x_nhwc is read by dw and by that re-run."""
+    c_raw = None
+    if need_affine and (recompute_c or bool((scale == 0).any())):
+        if x_nhwc is None:
+            raise RuntimeError("conv2d_bn_act_backward: dscale of this conv needs the conv's input")
+        c_raw = _ops.conv2d_bn_act(x_nhwc, _ops.pack_conv_weight(w_oihw), torch.ones_like(scale), torch.zeros_like(shift), w_oihw.shape[2],
+                                   w_oihw.shape[3], stride=stride, pad=pad, precision=0)
+    dc, dscale, dshift = _ops.affine_act_backward(dy, y, scale, shift, relu, c_raw, all_from_raw=recompute_c)
+    dx = _ops.conv_backward_data(dc, w_oihw, in_h, in_w, stride, pad, precision) if need_x else dy.new_empty(0)
+    if need_w and x_nhwc is None:
+        raise RuntimeError("conv2d_bn_act_backward: dw needs the conv's input")
+    dw = _ops.conv_backward_weight(dc, x_nhwc, tuple(w_oihw.shape), stride, pad) if need_w else dy.new_empty(0)
+    return dx, dw, (dscale if need_affine else dy.new_empty(0)), (dshift if need_affine else dy.new_empty(0))
+
+
+@conv2d_bn_act_backward.register_fake
+def _(dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, stride, pad, relu, precision, need_x, need_w, need_affine, recompute_c):
+    empty = lambda: dy.new_empty(0)
+    return (dy.new_empty((dy.shape[0], in_h, in_w, w_oihw.shape[1])) if need_x else empty(), torch.empty_like(w_oihw) if need_w else empty(),
+            torch.empty_like(scale) if need_affine else empty(), torch.empty_like(shift) if need_affine else empty())
+
+
+def _conv_setup_common(ctx, what, x, w, scale, shift, y, stride, pad, relu, precision, needs, winograd=False):
+    if precision not in (0, 1):
+        raise RuntimeError("torch.ops.vidc.%s: precision %d (MXFP8 is 3) has no backward; use precision 0 or 1 for inputs that require a gradient"
+                           % (what, precision))
+    need_x, need_w, need_affine = needs[0], needs[1], needs[2] or needs[3]
+    ctx.save_for_backward(x if (need_w or need_affine) else None, w, y, scale, shift)      # (dscale re-runs the conv where a scale is 0)
+    dgrad_precision = precision if winograd else 0      # (see conv2d_bn_act_backward)
+    ctx.args = (x.shape[1], x.shape[2], stride, pad, relu, dgrad_precision, need_x, need_w, need_affine,
+                bool(needs[2] and (precision == 1 or winograd)))
+
+
+def _conv_grads(ctx, grad_y):
+    x, w, y, scale, shift = ctx.saved_tensors
+    dx, dw, dscale, dshift = torch.ops.vidc.conv2d_bn_act_backward(grad_y, x, w, y, scale, shift, *ctx.args)
+    return (_none_if_empty(dx), _none_if_empty(dw), dscale.reshape(scale.shape) if ctx.needs_input_grad[2] else None,
+            dshift.reshape(shift.shape) if ctx.needs_input_grad[3] else None)
+
+
+def _conv_setup(ctx, inputs, output):
+    x, w, scale, shift, stride, pad, relu, precision = inputs
+    _conv_setup_common(ctx, "conv2d_bn_act", x, w, scale, shift, output, stride, pad, relu, precision, ctx.needs_input_grad)
+
+
+def _conv_backward(ctx, grad_y):
+    return _conv_grads(ctx, grad_y) + (None,) * 4
+
+
+torch.library.register_autograd("vidc::conv2d_bn_act", _conv_backward, setup_context=_conv_setup)
+
+
+def _wino_setup(ctx, inputs, output):
+    x, w, scale, shift, m, relu, precision = inputs
+    # the gradient of a 3x3 conv does not care how the forward was evaluated: the direct form's backward with stride 1 / pad 1
+    _conv_setup_common(ctx, "conv3x3_winograd", x, w, scale, shift, output, 1, 1, relu, precision, ctx.needs_input_grad, winograd=True)
+
+
+def _wino_backward(ctx, grad_y):
+    return _conv_grads(ctx, grad_y) + (None,) * 3
+
+
+torch.library.register_autograd("vidc::conv3x3_winograd", _wino_backward, setup_context=_wino_setup)
+
+
+@torch.library.custom_op("vidc::stem_conv3x3s2_backward", mutates_args=(), device_types=_DEV)
+def stem_conv3x3s2_backward(dy: torch.Tensor, x_nchw: Optional[torch.Tensor], w_oihw: torch.Tensor, y: torch.Tensor, in_h: int, in_w: int,
+                            relu: bool, need_x: bool, need_w: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dx NCHW, dw) of stem_conv3x3s2: vidc_stem_conv3x3s2_backward_data / vidc_stem_wgrad; a gradient that is not needed comes back empty."""
+    dx = _ops.stem_conv3x3s2_backward_data(dy, y, w_oihw, in_h, in_w, relu) if need_x else dy.new_empty(0)
+    if need_w and x_nchw is None:
+        raise RuntimeError("stem_conv3x3s2_backward: dw needs the conv's input")
+    dw = _ops.stem_conv3x3s2_backward_weight(dy, y, x_nchw, tuple(w_oihw.shape), relu) if need_w else dy.new_empty(0)
+    return dx, dw
+
+
+@stem_conv3x3s2_backward.register_fake
+def _(dy, x_nchw, w_oihw, y, in_h, in_w, relu, need_x, need_w):
+    return (dy.new_empty((dy.shape[0], w_oihw.shape[1], in_h, in_w)) if need_x else dy.new_empty(0),
+            torch.empty_like(w_oihw) if need_w else dy.new_empty(0))
+
+
+def _stem_setup(ctx, inputs, output):
+    x, w, relu = inputs
+    need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    ctx.save_for_backward(x if need_w else None, w, output)
+    ctx.args = (x.shape[2], x.shape[3], relu, need_x, need_w)
+
+
+def _stem_backward(ctx, grad_y):
+    x, w, y = ctx.saved_tensors
+    dx, dw = torch.ops.vidc.stem_conv3x3s2_backward(grad_y, x, w, y, *ctx.args)
+    return _none_if_empty(dx), _none_if_empty(dw), None
+
+
+torch.library.register_autograd("vidc::stem_conv3x3s2", _stem_backward, setup_context=_stem_setup)
+
+
+@torch.library.custom_op("vidc::maxpool3x3s2_backward", mutates_args=(), device_types=_DEV)
+def maxpool3x3s2_backward(dy: torch.Tensor, x_nhwc: torch.Tensor) -> torch.Tensor:
+    return _ops.maxpool3x3s2_backward(dy, x_nhwc)
+
+
+@maxpool3x3s2_backward.register_fake
+def _(dy, x_nhwc):
+    return torch.empty_like(x_nhwc)
+
+
+def _maxpool_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0])
+
+
+def _maxpool_backward(ctx, grad_y):
+    return torch.ops.vidc.maxpool3x3s2_backward(grad_y, ctx.saved_tensors[0])
+
+
+torch.library.register_autograd("vidc::maxpool3x3s2", _maxpool_backward, setup_context=_maxpool_setup)
+
+
+@torch.library.custom_op("vidc::upsample_bilinear_ac_backward", mutates_args=(), device_types=_DEV)
+def upsample_bilinear_ac_backward(dy: torch.Tensor, y: Optional[torch.Tensor], in_h: int, in_w: int) -> torch.Tensor:
+    """dx of upsample_bilinear_ac; y: the forward output when its ReLU was applied (vidc_relu_backward first), else None."""
+    return _ops.upsample_bilinear_ac_backward(dy, (in_h, in_w), y)
+
+
+@upsample_bilinear_ac_backward.register_fake
+def _(dy, y, in_h, in_w):
+    return dy.new_empty((dy.shape[0], in_h, in_w, dy.shape[3]))
+
+
+def _upsample_setup(ctx, inputs, output):
+    x, _oh, _ow, relu = inputs
+    ctx.save_for_backward(output if relu else None)
+    ctx.args = (x.shape[1], x.shape[2])
+
+
+def _upsample_backward(ctx, grad_y):
+    return torch.ops.vidc.upsample_bilinear_ac_backward(grad_y, ctx.saved_tensors[0], *ctx.args), None, None, None
+
+
+torch.library.register_autograd("vidc::upsample_bilinear_ac", _upsample_backward, setup_context=_upsample_setup)
+
+
+@torch.library.custom_op("vidc::head_conv1x1_upsample_backward", mutates_args=(), device_types=_DEV)
+def head_conv1x1_upsample_backward(dy: torch.Tensor, x_nhwc: torch.Tensor, w: torch.Tensor, y: Optional[torch.Tensor],
+                                   pad: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx NHWC, dw, dbias) of head_conv1x1_upsample: vidc_relu_backward (y given), vidc_upsample_bilinear_ac_backward, vidc_head_backward.
+    One output channel and pad 1 only."""
+    return _ops.head_conv1x1_upsample_backward(dy, x_nhwc, w, pad, y)
+
+
+@head_conv1x1_upsample_backward.register_fake
+def _(dy, x_nhwc, w, y, pad):
+    return torch.empty_like(x_nhwc), torch.empty_like(w), dy.new_empty((w.shape[0],))
+
+
+def _head_setup(ctx, inputs, output):
+    x, w, bias, pad, _oh, _ow, relu = inputs
+    if w.shape[0] != 1 or pad != 1:
+        raise RuntimeError("torch.ops.vidc.head_conv1x1_upsample: the backward covers one output channel and pad 1 only (got Cout %d, pad %d)"
+                           % (w.shape[0], pad))
+    ctx.save_for_backward(x, w, output if relu else None)
+    ctx.pad, ctx.bias_shape = pad, bias.shape
+
+
+def _head_backward(ctx, grad_y):
+    x, w, y = ctx.saved_tensors
+    dx, dw, db = torch.ops.vidc.head_conv1x1_upsample_backward(grad_y, x, w, y, ctx.pad)
+    need = ctx.needs_input_grad
+    return (dx if need[0] else None, dw if need[1] else None, db.reshape(ctx.bias_shape) if need[2] else None, None, None, None, None)
+
+
+torch.library.register_autograd("vidc::head_conv1x1_upsample", _head_backward, setup_context=_head_setup)
+
+
+BACKWARD_OPS = ("warp2dof_fwd_backward", "warp2dof_inv_rot_norm_backward", "conv2d_bn_act_backward", "stem_conv3x3s2_backward", "maxpool3x3s2_backward",
+                "upsample_bilinear_ac_backward", "head_conv1x1_upsample_backward")
+OPS = ("plane_ransac_normal", "plane_offset", "plane_project_depth", "plane_finalize", "enrich_scatter", "warp2dof_fwd", "warp2dof_inv_rot_norm", "conv2d_bn_act",
+       "conv3x3_winograd", "stem_conv3x3s2", "maxpool3x3s2", "upsample_bilinear_ac", "head_conv1x1_upsample") + BACKWARD_OPS
