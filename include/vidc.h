@@ -658,6 +658,37 @@ size_t vidc_stem_wgrad_scratch_bytes(int B, int Cin, int H, int W, int Cout);
 int vidc_stem_wgrad(const float* dy, const float* x_nchw, float* dw_oihw, int B, int Cin, int H, int W, int Cout, int lddy, void* scratch,
                     vidc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training step of the surface-normal network: what it needs beyond the entries above (csrc/sn_train.hip)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* `_network_loss`, branch `_network_estimates_normal()` (network_run.py:181-189) + compute_normal_vectors_loss_l1 (normal_utils.py:20-34)
+ * and the gradient of the loss, in one call.  pred, normal_gt, dpred: NCHW [B][3][H][W] fp32; mask: [B][H][W] fp32, m = 1 where > 0, else 0.
+ *   gh = F.normalize(normal_gt, dim=1, eps=1e-12) (network_run.py:183; normal_gt is passed raw),
+ *   n  = pred when normalize_prediction == 0 -- the reference's code exactly as shipped -- and Normalize(pred) otherwise.  `Normalize` is
+ *        an UNDEFINED name in the reference's normal_utils.py (the call at network_run.py:186 raises NameError as shipped); it is read here as
+ *        F.normalize(., dim=1, eps=1e-12), the function the network's own last line uses (surface_normal.py:170),
+ *   *count = N = sum m (pixels, not elements; may be NULL),   *loss = sum_{b,c,y,x} |n m - gh m| / N,
+ *   *angle = sum m acos(clamp(n . gh, -1, 1)) 180 / pi (may be NULL; not differentiated, the reference only logs it),
+ *   dpred = d loss / d pred: sign(n - gh) m / N with sign(0) = 0 (torch's L1 backward), taken through the normalisation as torch does:
+ *        (g - n (n . g)) / |pred| where |pred| >= eps and g / eps below it (the clamp passes no gradient -- the inverse warp leaves exact
+ *        zeros outside the warped region).
+ * N == 0 divides by zero as the reference does: loss and dpred are NaN.  Normalisation, dot product and acos run in fp64 from the fp32
+ * inputs; the three sums are fp64 workgroup partials reduced in a fixed order (no floating-point atomics: the same bits on every run and
+ * stream); dpred is scaled by 1 / N read from device memory, so the call is capturable.  scratch: vidc_normal_l1_loss_scratch_bytes,
+ * 8-byte aligned. */
+size_t vidc_normal_l1_loss_scratch_bytes(int B, int H, int W);
+int vidc_normal_l1_loss(const float* pred, const float* normal_gt, const float* mask, int B, int H, int W, int normalize_prediction,
+                        double* loss, double* count, double* angle, float* dpred, void* scratch, vidc_stream_t stream);
+/* Backward of the 1x1 head conv of vidc_head_conv1x1_upsample with Cout = 1..4 output channels and zero padding `pad`
+ * (surface_normal.py:143: Conv2d(64, 3, 1); pad = 1, Cout = 1 is vidc_head_backward's case, which stays the depth trainer's entry).
+ * g_low: [B*Cout][h+2pad][w+2pad] planes, the layout of that call's `lowres`; x: NHWC [B][h][w][ldx]; wgt: [Cout][C] ->
+ * dx NHWC [B][h][w][lddx], dw [Cout][C], dbias [Cout] (over the whole padded plane: a padded 1x1 conv's border outputs are the bias).
+ * dw, dbias: fp64 chunk partials reduced in a fixed order.  scratch: vidc_head_backward_multi_scratch_bytes, 8-byte aligned. */
+size_t vidc_head_backward_multi_scratch_bytes(int B, int h, int w, int C, int Cout, int pad);
+int vidc_head_backward_multi(const float* g_low, const float* x, const float* wgt, float* dx, float* dw, float* dbias, int B, int h, int w,
+                             int C, int ldx, int lddx, int Cout, int pad, void* scratch, vidc_stream_t stream);
+
 enum vidc_op_kind { VIDC_OP_CONV = 1, VIDC_OP_STEM = 2, VIDC_OP_MAXPOOL = 3, VIDC_OP_UPSAMPLE = 4, VIDC_OP_HEAD = 5,
                     VIDC_OP_WARP_PARAMS = 6, VIDC_OP_WARP_FWD = 7, VIDC_OP_WARP_INV = 8, VIDC_OP_COPY = 9, VIDC_OP_SPLIT = 10,
                     VIDC_OP_AVGPOOL = 11, VIDC_OP_NORMALIZE = 12, VIDC_OP_DET_IM2COL = 13, VIDC_OP_NEAREST2X = 14,

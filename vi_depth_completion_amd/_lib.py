@@ -174,6 +174,10 @@ SIGNATURES = {
     "vidc_head_backward_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "vidc_head_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vidc_masked_l1_loss": (C.c_int, [_vp, _vp, C.c_longlong, _i, _vp, _vp, _vp, _vp, _vp]),
+    "vidc_normal_l1_loss_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
+    "vidc_normal_l1_loss": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vidc_head_backward_multi_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "vidc_head_backward_multi": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vidc_clock_stamp": (C.c_int, [_vp, _vp]),
     "vidc_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_longlong, _f, _f, _f, _f, _i, _vp]),
     "vidc_train_bn_fold": (C.c_int, [_i]),

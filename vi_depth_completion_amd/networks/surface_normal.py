@@ -17,6 +17,8 @@ from .warping_2dof_alignment import Warping2DOFAlignment
 class _HipModule(nn.Module):
     """Shared plumbing: derived-weight cache invalidation and per-batch-size program cache."""
 
+    _train_hint = ""           # appended to the train-mode refusal of forward(): where the module's training step lives, if it has one
+
     def _init_engine(self):
         self._weights = engine.WeightStore(self)
         self._programs = {}
@@ -43,7 +45,7 @@ class _HipModule(nn.Module):
 
     def _check(self, *tensors):
         if self.training:
-            raise RuntimeError("%s: the HIP path is inference-only (BatchNorm is folded); call .eval()" % type(self).__name__)
+            raise RuntimeError("%s: the HIP path is inference-only (BatchNorm is folded); call .eval()%s" % (type(self).__name__, self._train_hint))
         for t in tensors:
             if not t.is_cuda:
                 raise RuntimeError("%s runs on the GPU only: there is no CPU/eager fallback" % type(self).__name__)
@@ -65,6 +67,8 @@ class _HipModule(nn.Module):
 
 
 class SurfaceNormalPrediction(_HipModule):
+    _train_hint = ", or train the network with vi_depth_completion_amd.training.SurfaceNormalTrainer"
+
     def __init__(self, output_size=(240, 320), in_channels=3, training_mode="train_L2_loss",
                  fc_img=np.array([0.5 * 577.87061, 0.5 * 580.25851]),
                  cc_img=np.array([0.5 * 319.87654, 0.5 * 239.87603]), use_mask=False, align_corners=False):

@@ -1,4 +1,5 @@
-"""Training step of the depth-completion network on the GPU (BASELINE configs[4]).
+"""Training steps of the two networks on the GPU: the depth-completion network (BASELINE configs[4]) and, with
+`SurfaceNormalTrainer` at the end of this file, the surface-normal network.  Both share `_TrainerBase`; the text below describes the depth step.
 
 `DepthCompletionTrainer(cnn, learning_rate).step(image, normal, depth_in, depth_gt)` is the body of the reference's
 `ImageNetworkRunInterface._run_training_iteration` (network_run.py:231-254) for `self.cnn = ModifiedFPN`:
@@ -155,15 +156,22 @@ class GradientBuckets:
         return waits
 
 
-class DepthCompletionTrainer:
-    """Build the trainer AFTER `torch.distributed.init_process_group` (and after the network is on its GPU): the flat layout of parameters, gradients, Adam
+class _TrainerBase:
+    """What the two trainers share: the flat parameter / gradient / Adam-moment buffers, the recording ops (conv, bn, add, maxpool, upsample, the
+    ResNet-101 pyramid and the decoder branches -- each launches its forward and records its backward on the tape), weight packing, the tape and
+    its stream lanes, graph capture / replay of a step and the Adam step.  A subclass names its pyramids (`pyramid_names`) and writes the
+    network walk, the loss and `step`.
+
+    Build the trainer AFTER `torch.distributed.init_process_group` (and after the network is on its GPU): the flat layout of parameters, gradients, Adam
     moments and BatchNorm running statistics is chosen here (`self.layout`: "grouped" = the three pyramids interleaved per parameter name, the multi-rank
-    default; "per_pyramid" otherwise) and every launch of the step addresses tensors as base + offset into those buffers.  A later `cnn.to()` / `.float()` /
-    `.cuda()` that rebinds `p.data` is caught at the next `step()` (`_check_bindings`), not silently read through stale pointers."""
+    default of the depth trainer; "per_pyramid" otherwise) and every launch of the step addresses tensors as base + offset into those buffers.  A later
+    `cnn.to()` / `.float()` / `.cuda()` that rebinds `p.data` is caught at the next `step()` (`_check_bindings`), not silently read through stale pointers."""
+
+    pyramid_names = PYRAMIDS
 
     def __init__(self, cnn, learning_rate=1e-4, betas=(0.9, 0.999), eps=1e-8):
         if not torch.cuda.is_available():
-            raise RuntimeError("DepthCompletionTrainer needs a GPU: the HIP path has no CPU fallback")
+            raise RuntimeError("%s needs a GPU: the HIP path has no CPU fallback" % type(self).__name__)
         self.cnn = cnn
         self.lr, self.betas, self.eps = float(learning_rate), betas, float(eps)
         self.named = [(k, p) for k, p in cnn.named_parameters()]
@@ -183,14 +191,15 @@ class DepthCompletionTrainer:
         # does not care (27.8 / 28.4 ms at 4 / 8 queues): the multi-rank default must not depend on a queue count nobody controls.
         mode = os.environ.get("VIDC_TRAIN_GROUPED", "auto")
         want = self._distributed() if mode == "auto" else mode == "1"
-        self.grouped = (want and os.environ.get("VIDC_TRAIN_WGRAD_INPLACE", "1") == "1" and all(hasattr(cnn, pn) for pn in PYRAMIDS))
+        self.grouped = (want and os.environ.get("VIDC_TRAIN_WGRAD_INPLACE", "1") == "1" and
+                        len(self.pyramid_names) > 1 and all(hasattr(cnn, pn) for pn in self.pyramid_names))
         if self.grouped:
             by_name = dict(self.named)
-            first = PYRAMIDS[0] + "."
+            first = self.pyramid_names[0] + "."
             inter = []
             for k, _p in self.named:
                 if k.startswith(first):
-                    for pn in PYRAMIDS:
+                    for pn in self.pyramid_names:
                         kk = pn + "." + k[len(first):]
                         inter.append((kk, by_name[kk]))
             seen = {k for k, _ in inter}
@@ -215,13 +224,13 @@ class DepthCompletionTrainer:
             o += k_n
         self.buf = {k: b for k, b in cnn.named_buffers()}
         if self.grouped:      # BatchNorm running statistics of the three pyramids: the same interleaved order, in a flat buffer of their own
-            first = PYRAMIDS[0] + "."
+            first = self.pyramid_names[0] + "."
             fl = [k for k in self.buf if k.startswith(first) and self.buf[k].dtype == torch.float32]
-            tot = sum(self.buf[k].numel() for k in fl) * len(PYRAMIDS)
+            tot = sum(self.buf[k].numel() for k in fl) * len(self.pyramid_names)
             self.flat_b = torch.empty(tot, dtype=torch.float32, device=dev)
             o = 0
             for k in fl:
-                for pn in PYRAMIDS:
+                for pn in self.pyramid_names:
                     b = self.buf[pn + "." + k[len(first):]]
                     self.flat_b[o:o + b.numel()].copy_(b.detach().reshape(-1))
                     b.data = self.flat_b[o:o + b.numel()].view(b.shape)
@@ -230,7 +239,7 @@ class DepthCompletionTrainer:
         self.layout = "grouped" if self.grouped else "per_pyramid"      # (exported with `flat_state()`: moments of one layout are not another's)
         self._bind_probe = [(self.named[i][1], self.param[self.named[i][0]].data_ptr(), self.grad[self.named[i][0]].data_ptr()) for i in (0, len(self.named) - 1)]
         if self.grouped:
-            fb = [k for k in self.buf if self.buf[k].dtype == torch.float32 and any(k.startswith(pn + ".") for pn in PYRAMIDS)]
+            fb = [k for k in self.buf if self.buf[k].dtype == torch.float32 and any(k.startswith(pn + ".") for pn in self.pyramid_names)]
             self._bind_probe += [(self.buf[k], self.buf[k].data_ptr(), None) for k in (fb[0], fb[-1])] if fb else []
         self.buckets = GradientBuckets(n, compress=("bf16" if os.environ.get("VIDC_TRAIN_GRAD_BF16", "0") == "1" else None))
         # the decoder's parameters (feature*_upsamping, feature_concat) form the tail of the flat buffers (named_parameters order): their
@@ -441,8 +450,8 @@ class DepthCompletionTrainer:
         (base + g * numel) would then read the old storage."""
         for t, p_ptr, g_ptr in self._bind_probe:
             if t.data_ptr() != p_ptr or (g_ptr is not None and (t.grad is None or t.grad.data_ptr() != g_ptr)):
-                raise RuntimeError("DepthCompletionTrainer: a parameter / buffer of the network was rebound after the trainer was built (layout %r); "
-                                   "build a new trainer after moving or casting the network" % self.layout)
+                raise RuntimeError("%s: a parameter / buffer of the network was rebound after the trainer was built (layout %r); "
+                                   "build a new trainer after moving or casting the network" % (type(self).__name__, self.layout))
 
     def flat_state(self):
         """Optimizer state for a checkpoint: the flat Adam moments with the layout they belong to and the parameter order that defines the offsets."""
@@ -813,55 +822,10 @@ class DepthCompletionTrainer:
             outs.append(t)
         return outs
 
-    def forward(self, image, normal, depth_in):
-        """Train-mode forward; returns the predicted depth (B,1,H,W).  The tape of backward closures is left in self.tape."""
-        self.tape, self._nbt = [], []
-        self.repack()
-        B, _, H, W = image.shape
-        sizes = [((H - 1) // 2 + 1, (W - 1) // 2 + 1)]
-        sizes[0] = ((sizes[0][0] - 1) // 2 + 1, (sizes[0][1] - 1) // 2 + 1)
-        for _ in range(3):
-            sizes.append(((sizes[-1][0] - 1) // 2 + 1, (sizes[-1][1] - 1) // 2 + 1))
-        chans = [256, 512, 1024, 2048]
-        cat = [self._empty(B, sizes[l][0], sizes[l][1], 3 * chans[l]) for l in range(4)]
-        levels = [Act(c) for c in cat]
-        subs = []
-        # The three pyramids are independent until the decoder: each runs on its own HIP stream (forward here, backward in
-        # loss_and_backward), so the fixed cost of one pyramid's ~100 small launches hides under the other two's -- in the captured graph
-        # they are three parallel branches.  Scratch and split-K workspaces are per lane.  VIDC_TRAIN_STREAMS=1: one stream.
+    def _decoder(self, levels, sizes, multi):
+        """The four decoder branches by `_BRANCH_PLAN` (conv + BatchNorm + ReLU / upsample; widths from the parameters' shapes) and their sum
+        z1 + z2 + z3 + z4.  The branches are independent until the sum: one stream lane each when `multi`."""
         main = torch.cuda.current_stream()
-        multi = self.n_lanes > 1
-        if self.grouped:
-            # ONE chain of grouped launches for the three pyramids on the caller's stream: a third of the launches, each three times the
-            # work; level l's last block writes the concat buffer directly and the decoder reads the very same activation object, so the
-            # decoder's d(concat) IS the pyramids' level gradient (no slicing step)
-            xs = [t.contiguous().float() for t in (image, normal, depth_in)]
-            levels = self._pyramid(xs, tuple(n + "." for n in PYRAMIDS), getattr(self.cnn, PYRAMIDS[0]), cat)
-        for pi, (name, x) in enumerate(() if self.grouped else (("resnet_rgb", image), ("resnet_normal", normal), ("resnet_depth", depth_in))):
-            outs = [cat[l][..., pi * chans[l]:(pi + 1) * chans[l]] for l in range(4)]
-            x = x.contiguous().float()
-            if not multi:
-                subs.append(self._pyramid(x, name + ".", getattr(self.cnn, name), outs))
-                continue
-            side = self._lane_streams()[pi]
-            side.wait_stream(main)
-            self._cur = pi + 1
-            with torch.cuda.stream(side):
-                subs.append(self._pyramid(x, name + ".", getattr(self.cnn, name), outs))
-            self._cur = 0
-        if multi and not self.grouped:
-            for side in self._lane_streams():
-                main.wait_stream(side)
-
-        def split_level_grads():                     # runs (in the backward) once the decoder has produced d(concat): slices become the
-            for l in range(4 if not self.grouped else 0):      # gradients of the three pyramids' level outputs (grouped: the same objects)
-                for pi in range(3):
-                    g = levels[l].grad[..., pi * chans[l]:(pi + 1) * chans[l]]
-                    subs[pi][l].grad = g if subs[pi][l].grad is None else subs[pi][l].grad
-        # NB: appended BEFORE the decoder ops, so it runs after all of them in the reversed tape; a level's slice is also fed by the next
-        # stage of its pyramid, whose backward (later in the reversed order) accumulates into the same slice.
-        split_level_grads._decoder_done = True       # everything recorded after this point (= run before it) is the decoder's backward
-        self._record(split_level_grads)
 
         def branch(b):
             t = levels[b - 1]
@@ -892,47 +856,7 @@ class DepthCompletionTrainer:
         if multi:
             for side in self._lane_streams():
                 main.wait_stream(side)
-        z = self.add(self.add(self.add(zs[0], zs[1], False), zs[2], False), zs[3], False)
-        h = self.conv(z, "feature_concat.0", 1, 1, relu=True)
-        # padded 1x1 head -> bilinear to (H, W) -> ReLU (depth_completion.py:143-147)
-        w2, b2 = self.param["feature_concat.2.weight"], self.param["feature_concat.2.bias"]
-        hh, hw_ = h.t.shape[1], h.t.shape[2]
-        low = self._empty(B, 1, hh + 2, hw_ + 2)
-        pred = self._empty(B, 1, H, W)
-        L.check(L.lib().vidc_head_conv1x1_upsample(L.ptr(h.t), L.ptr(w2), L.ptr(b2), L.ptr(low), L.ptr(pred), B, hh, hw_, 192, h.ld, 1, 1, H, W, 1,
-                                                   L.current_stream()), "head")
-        self._pred_grad = None
-
-        def head_backward():
-            lib = L.lib()
-            n = B * H * W
-            g = self._empty(n)
-            L.check(lib.vidc_relu_backward(L.ptr(self._pred_grad), L.ptr(pred), L.ptr(g), n // 4, 4, 4, 4, 4, 0, L.current_stream()), "relu_bwd")
-            g_low = self._empty(B, hh + 2, hw_ + 2)
-            L.check(lib.vidc_upsample_bilinear_ac_backward(L.ptr(g), L.ptr(g_low), B, hh + 2, hw_ + 2, 1, 1, 1, H, W, L.current_stream()), "upsample_bwd")
-            h.grad = self._empty(B, hh, hw_, 192)
-            sc = self._scratch_bytes(lib.vidc_head_backward_scratch_bytes(B, hh, hw_, 192))
-            L.check(lib.vidc_head_backward(L.ptr(g_low), L.ptr(h.t), L.ptr(w2), L.ptr(h.grad), L.ptr(self.grad["feature_concat.2.weight"]),
-                                           L.ptr(self.grad["feature_concat.2.bias"]), B, hh, hw_, 192, h.ld, 192, L.ptr(sc), L.current_stream()), "head_bwd")
-
-        self._record(head_backward)
-        self._pred = pred
-        self.flush_counters()
-        return pred
-
-    def loss_and_backward(self, pred, depth_gt, stop_after_decoder=False):
-        """network_run.py:163-173 + `total_loss.backward()`: fills the flat gradient buffer; returns the loss (0-dim fp64 GPU tensor)."""
-        B, _, H, W = pred.shape
-        n = pred.numel()
-        gt = depth_gt.contiguous().float()
-        loss = torch.zeros((), dtype=torch.float64, device=self.device)
-        self._pred_grad = self._empty(n)
-        terms = self._empty(n)
-        sc = self._scratch_bytes((n // 512 + 64) * 8)
-        L.check(L.lib().vidc_masked_l1_loss(L.ptr(pred), L.ptr(gt), n, H * W, L.ptr(loss), L.ptr(self._pred_grad), L.ptr(terms), L.ptr(sc), L.current_stream()),
-                "loss")
-        self._run_tape(stop_after_decoder)
-        return loss
+        return self.add(self.add(self.add(zs[0], zs[1], False), zs[2], False), zs[3], False)
 
     def _run_tape(self, stop_after_decoder=False):
         """Runs the recorded backward closures, last first, each on the stream lane it was recorded on.  stop_after_decoder: return once
@@ -983,17 +907,6 @@ class DepthCompletionTrainer:
         self._keepalive = []                              # every lane has joined: nothing queued anywhere still touches these tensors
 
     @torch.no_grad()
-    def forward_backward(self, image, normal, depth_in, depth_gt):
-        for t in (image, normal, depth_in, depth_gt):
-            if not t.is_cuda:
-                raise RuntimeError("DepthCompletionTrainer takes GPU tensors only (no CPU fallback)")
-        if not self.cnn.training:
-            raise RuntimeError("call cnn.train() first (network_run.py:232): the trainer implements BatchNorm's train() mode")
-        pred = self.forward(image.float(), normal.float(), depth_in.float())
-        loss = self.loss_and_backward(pred, depth_gt)
-        return loss, pred
-
-    @torch.no_grad()
     def optimizer_step(self, reduced=False):
         """torch.optim.Adam.step over the flat buffers; gradients are summed over ranks first (frame-sharded batch) unless `step` has
         done that already, overlapped with the backward."""
@@ -1008,6 +921,147 @@ class DepthCompletionTrainer:
     def _distributed(self):
         from .sharding import collectives_active
         return collectives_active()
+
+    def _graphed(self, ins, multi=False):
+        """A step's forward + backward on `ins`: eager the first two times a shape is seen (that creates the packed-weight table, constants,
+        scratch and split-K workspaces), then captured once (`_record_step` on static copies of the inputs) and replayed.  Returns
+        (loss, completion callbacks of the all-reduces started)."""
+        key = tuple((tuple(t.shape), t.dtype) for t in ins) + (multi,)
+        ent = self._graphs.get(key)
+        if ent is None:
+            seen = self._graph_seen[key] = self._graph_seen.get(key, 0) + 1
+            if seen <= 2:                     # eager: creates the packed-weight table, constants, scratch and split-K workspace
+                return self._eager_forward_backward(*ins, multi)
+            static = [t.clone() for t in ins]
+            torch.cuda.synchronize()
+            graph, rest = torch.cuda.CUDAGraph(), None
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):      # (RCCL's watchdog thread polls events while this thread captures)
+                loss, pred = self._record_step(static, multi)
+            if multi:                         # second graph: the pyramids' backward (same memory pool: it reads the first one's tensors)
+                rest = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(rest, pool=graph.pool(), capture_error_mode="thread_local"):
+                    self._run_tape()
+            ent = self._graphs[key] = (graph, rest, static, loss, pred)
+        graph, rest, static, loss, pred = ent
+        for dst, src in zip(static, ins):
+            dst.copy_(src)
+        self._packed_fresh = True             # the graph starts with repack()
+        graph.replay()
+        waits = []
+        if rest is not None:
+            waits = self.buckets.all_reduce_async(self.flat_g, self._dec_off, None)
+            rest.replay()
+            waits += self.buckets.all_reduce_async(self.flat_g, 0, self._dec_off)
+        return loss.clone(), waits
+
+
+
+class DepthCompletionTrainer(_TrainerBase):
+    """`_run_training_iteration` of `ModifiedFPN` (module docstring): three ResNet-101 pyramids (`self.layout`: "grouped" = interleaved per parameter
+    name, the multi-rank default; "per_pyramid" otherwise), the 192-wide decoder, the padded one-channel head, the masked L1 depth loss."""
+
+    def forward(self, image, normal, depth_in):
+        """Train-mode forward; returns the predicted depth (B,1,H,W).  The tape of backward closures is left in self.tape."""
+        self.tape, self._nbt = [], []
+        self.repack()
+        B, _, H, W = image.shape
+        sizes = [((H - 1) // 2 + 1, (W - 1) // 2 + 1)]
+        sizes[0] = ((sizes[0][0] - 1) // 2 + 1, (sizes[0][1] - 1) // 2 + 1)
+        for _ in range(3):
+            sizes.append(((sizes[-1][0] - 1) // 2 + 1, (sizes[-1][1] - 1) // 2 + 1))
+        chans = [256, 512, 1024, 2048]
+        cat = [self._empty(B, sizes[l][0], sizes[l][1], 3 * chans[l]) for l in range(4)]
+        levels = [Act(c) for c in cat]
+        subs = []
+        # The three pyramids are independent until the decoder: each runs on its own HIP stream (forward here, backward in
+        # loss_and_backward), so the fixed cost of one pyramid's ~100 small launches hides under the other two's -- in the captured graph
+        # they are three parallel branches.  Scratch and split-K workspaces are per lane.  VIDC_TRAIN_STREAMS=1: one stream.
+        main = torch.cuda.current_stream()
+        multi = self.n_lanes > 1
+        if self.grouped:
+            # ONE chain of grouped launches for the three pyramids on the caller's stream: a third of the launches, each three times the
+            # work; level l's last block writes the concat buffer directly and the decoder reads the very same activation object, so the
+            # decoder's d(concat) IS the pyramids' level gradient (no slicing step)
+            xs = [t.contiguous().float() for t in (image, normal, depth_in)]
+            levels = self._pyramid(xs, tuple(n + "." for n in PYRAMIDS), getattr(self.cnn, PYRAMIDS[0]), cat)
+        for pi, (name, x) in enumerate(() if self.grouped else (("resnet_rgb", image), ("resnet_normal", normal), ("resnet_depth", depth_in))):
+            outs = [cat[l][..., pi * chans[l]:(pi + 1) * chans[l]] for l in range(4)]
+            x = x.contiguous().float()
+            if not multi:
+                subs.append(self._pyramid(x, name + ".", getattr(self.cnn, name), outs))
+                continue
+            side = self._lane_streams()[pi]
+            side.wait_stream(main)
+            self._cur = pi + 1
+            with torch.cuda.stream(side):
+                subs.append(self._pyramid(x, name + ".", getattr(self.cnn, name), outs))
+            self._cur = 0
+        if multi and not self.grouped:
+            for side in self._lane_streams():
+                main.wait_stream(side)
+
+        def split_level_grads():                     # runs (in the backward) once the decoder has produced d(concat): slices become the
+            for l in range(4 if not self.grouped else 0):      # gradients of the three pyramids' level outputs (grouped: the same objects)
+                for pi in range(3):
+                    g = levels[l].grad[..., pi * chans[l]:(pi + 1) * chans[l]]
+                    subs[pi][l].grad = g if subs[pi][l].grad is None else subs[pi][l].grad
+        # NB: appended BEFORE the decoder ops, so it runs after all of them in the reversed tape; a level's slice is also fed by the next
+        # stage of its pyramid, whose backward (later in the reversed order) accumulates into the same slice.
+        split_level_grads._decoder_done = True       # everything recorded after this point (= run before it) is the decoder's backward
+        self._record(split_level_grads)
+
+        z = self._decoder(levels, sizes, multi)
+        h = self.conv(z, "feature_concat.0", 1, 1, relu=True)
+        # padded 1x1 head -> bilinear to (H, W) -> ReLU (depth_completion.py:143-147)
+        w2, b2 = self.param["feature_concat.2.weight"], self.param["feature_concat.2.bias"]
+        hh, hw_ = h.t.shape[1], h.t.shape[2]
+        low = self._empty(B, 1, hh + 2, hw_ + 2)
+        pred = self._empty(B, 1, H, W)
+        L.check(L.lib().vidc_head_conv1x1_upsample(L.ptr(h.t), L.ptr(w2), L.ptr(b2), L.ptr(low), L.ptr(pred), B, hh, hw_, 192, h.ld, 1, 1, H, W, 1,
+                                                   L.current_stream()), "head")
+        self._pred_grad = None
+
+        def head_backward():
+            lib = L.lib()
+            n = B * H * W
+            g = self._empty(n)
+            L.check(lib.vidc_relu_backward(L.ptr(self._pred_grad), L.ptr(pred), L.ptr(g), n // 4, 4, 4, 4, 4, 0, L.current_stream()), "relu_bwd")
+            g_low = self._empty(B, hh + 2, hw_ + 2)
+            L.check(lib.vidc_upsample_bilinear_ac_backward(L.ptr(g), L.ptr(g_low), B, hh + 2, hw_ + 2, 1, 1, 1, H, W, L.current_stream()), "upsample_bwd")
+            h.grad = self._empty(B, hh, hw_, 192)
+            sc = self._scratch_bytes(lib.vidc_head_backward_scratch_bytes(B, hh, hw_, 192))
+            L.check(lib.vidc_head_backward(L.ptr(g_low), L.ptr(h.t), L.ptr(w2), L.ptr(h.grad), L.ptr(self.grad["feature_concat.2.weight"]),
+                                           L.ptr(self.grad["feature_concat.2.bias"]), B, hh, hw_, 192, h.ld, 192, L.ptr(sc), L.current_stream()), "head_bwd")
+
+        self._record(head_backward)
+        self._pred = pred
+        self.flush_counters()
+        return pred
+
+    def loss_and_backward(self, pred, depth_gt, stop_after_decoder=False):
+        """network_run.py:163-173 + `total_loss.backward()`: fills the flat gradient buffer; returns the loss (0-dim fp64 GPU tensor)."""
+        B, _, H, W = pred.shape
+        n = pred.numel()
+        gt = depth_gt.contiguous().float()
+        loss = torch.zeros((), dtype=torch.float64, device=self.device)
+        self._pred_grad = self._empty(n)
+        terms = self._empty(n)
+        sc = self._scratch_bytes((n // 512 + 64) * 8)
+        L.check(L.lib().vidc_masked_l1_loss(L.ptr(pred), L.ptr(gt), n, H * W, L.ptr(loss), L.ptr(self._pred_grad), L.ptr(terms), L.ptr(sc), L.current_stream()),
+                "loss")
+        self._run_tape(stop_after_decoder)
+        return loss
+
+    @torch.no_grad()
+    def forward_backward(self, image, normal, depth_in, depth_gt):
+        for t in (image, normal, depth_in, depth_gt):
+            if not t.is_cuda:
+                raise RuntimeError("DepthCompletionTrainer takes GPU tensors only (no CPU fallback)")
+        if not self.cnn.training:
+            raise RuntimeError("call cnn.train() first (network_run.py:232): the trainer implements BatchNorm's train() mode")
+        pred = self.forward(image.float(), normal.float(), depth_in.float())
+        loss = self.loss_and_backward(pred, depth_gt)
+        return loss, pred
 
     def step(self, image, normal, depth_in, depth_gt):
         """One `_run_training_iteration`: returns the loss (0-dim fp64 GPU tensor, this rank's frames).
@@ -1040,36 +1094,155 @@ class DepthCompletionTrainer:
         waits += self.buckets.all_reduce_async(self.flat_g, 0, self._dec_off)
         return loss, waits
 
+    def _record_step(self, static, multi):
+        if multi:
+            pred = self.forward(static[0].float(), static[1].float(), static[2].float())
+            return self.loss_and_backward(pred, static[3], stop_after_decoder=True), pred
+        return self.forward_backward(*static)
+
     def _graphed_forward_backward(self, image, normal, depth_in, depth_gt, multi=False):
-        ins = (image, normal, depth_in, depth_gt)
-        key = tuple((tuple(t.shape), t.dtype) for t in ins) + (multi,)
-        ent = self._graphs.get(key)
-        if ent is None:
-            seen = self._graph_seen[key] = self._graph_seen.get(key, 0) + 1
-            if seen <= 2:                     # eager: creates the packed-weight table, constants, scratch and split-K workspace
-                return self._eager_forward_backward(*ins, multi)
-            static = [t.clone() for t in ins]
-            torch.cuda.synchronize()
-            graph, rest = torch.cuda.CUDAGraph(), None
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):      # (RCCL's watchdog thread polls events while this thread captures)
-                if multi:
-                    pred = self.forward(static[0].float(), static[1].float(), static[2].float())
-                    loss = self.loss_and_backward(pred, static[3], stop_after_decoder=True)
-                else:
-                    loss, pred = self.forward_backward(*static)
-            if multi:                         # second graph: the pyramids' backward (same memory pool: it reads the first one's tensors)
-                rest = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(rest, pool=graph.pool(), capture_error_mode="thread_local"):
-                    self._run_tape()
-            ent = self._graphs[key] = (graph, rest, static, loss, pred)
-        graph, rest, static, loss, pred = ent
-        for dst, src in zip(static, ins):
-            dst.copy_(src)
-        self._packed_fresh = True             # the graph starts with repack()
-        graph.replay()
-        waits = []
-        if rest is not None:
-            waits = self.buckets.all_reduce_async(self.flat_g, self._dec_off, None)
-            rest.replay()
-            waits += self.buckets.all_reduce_async(self.flat_g, 0, self._dec_off)
-        return loss.clone(), waits
+        return self._graphed((image, normal, depth_in, depth_gt), multi)
+
+
+class SurfaceNormalTrainer(_TrainerBase):
+    """`_run_training_iteration` (network_run.py:231-254) for `self.cnn = SurfaceNormalPrediction`, i.e. a `DefaultImageNetwork(...,
+    estimates_normal=True)` run: `SurfaceNormalTrainer(cnn, learning_rate).step(image, gravity, alignment, normal_gt, mask)`.
+
+        cnn.train(); normals = cnn(image, gravity, alignment)      surface_normal.py:147-171: forward warp, the ResNet-101 pyramid, the four
+                                                                   128-wide decoder branches, feature_concat, inverse warp + R^T + F.normalize
+        loss, angle = compute_normal_vectors_loss_l1(F.normalize(normal_gt), normals, mask > 0)      network_run.py:181-189
+        loss.backward(); Adam(cnn.parameters(), lr).step()
+
+    normalize_prediction is the loss's own argument (normal_utils.py:20).  True, its default, calls `Normalize`, a name the reference never
+    defines; it is read as F.normalize(., dim=1, eps=1e-12) (include/vidc.h, vidc_normal_l1_loss).  False is the reference's code as shipped.
+    No gradient is taken with respect to the image: neither the forward warp's adjoint nor the stem's data gradient runs.  `last_angle`
+    is the reference's `other_outputs['angle']` before rounding (a 0-dim fp64 GPU tensor), `last_count` the N the loss was divided by.
+
+    Refused: `use_mask=True` networks (the masked branch needs a mask-multiply backward) and a process group of more than one rank -- N
+    is a per-batch count here, so the sum of the ranks' gradients is not the reference's gradient (the depth loss divides by the
+    constant H*W, which is why that step shards)."""
+
+    pyramid_names = ("resnet_pyramids",)
+
+    def __init__(self, cnn, learning_rate=1e-4, betas=(0.9, 0.999), eps=1e-8, normalize_prediction=True):
+        if getattr(cnn, "use_mask", False):
+            raise RuntimeError("SurfaceNormalTrainer: use_mask=True networks are not supported (surface_normal.py:150-162 multiplies the features by the "
+                               "warp's validity mask; that multiply has no backward here yet)")
+        self._refuse_ranks()
+        super().__init__(cnn, learning_rate, betas, eps)
+        self.normalize_prediction = bool(normalize_prediction)
+        self._stats = torch.zeros(3, dtype=torch.float64, device=self.device)      # loss, N, angle sum of the step that ran last (written by the loss kernel)
+        self.last_angle = self.last_count = None
+
+    def _refuse_ranks(self):
+        if self._distributed():
+            raise RuntimeError("SurfaceNormalTrainer runs on one rank only: the normal loss divides by N, the number of unmasked pixels of the batch "
+                               "(normal_utils.py:32-33), so gradients summed over ranks that each divide by their own N are not the reference's gradient")
+
+    def forward(self, image, gravity, alignment):
+        """Train-mode forward of surface_normal.py:147-171; returns the unit normals (B,3,H,W).  The tape of backward closures is left in self.tape."""
+        wp = self.cnn.warp_2dof_alignment
+        B, cin, H, W = image.shape
+        if (H, W) != (wp.H, wp.W) or tuple(self.cnn.output_size) != (H, W) or cin != 3:
+            raise RuntimeError("SurfaceNormalTrainer: the network is built for 3 x %d x %d images (cc_img) and output_size %s, got %d x %d x %d"
+                               % (wp.H, wp.W, tuple(self.cnn.output_size), cin, H, W))
+        self.tape, self._nbt = [], []
+        self.repack()
+        lib, ac = L.lib(), int(wp.align_corners)
+        g = gravity.reshape(B, 3).contiguous().float()
+        a = alignment.reshape(B, 3).contiguous().float()
+        params = self._empty(B, L.WARP_PARAMS)
+        L.check(lib.vidc_warp2dof_params(L.ptr(g), L.ptr(a), B, wp.fx, wp.fy, wp.cx, wp.cy, L.ptr(wp.kinv(self.device)), W, H, L.ptr(params), L.current_stream()),
+                "warp params")
+        x = image.contiguous()
+        warped = torch.empty_like(x)
+        L.check(lib.vidc_warp2dof_fwd(L.ptr(x), L.ptr(params), L.ptr(warped), B, 3, H, W, wp.cx, wp.cy, ac, L.current_stream()), "warp")
+        sizes = [((H - 1) // 2 + 1, (W - 1) // 2 + 1)]
+        sizes[0] = ((sizes[0][0] - 1) // 2 + 1, (sizes[0][1] - 1) // 2 + 1)
+        for _ in range(3):
+            sizes.append(((sizes[-1][0] - 1) // 2 + 1, (sizes[-1][1] - 1) // 2 + 1))
+        # one pyramid on the caller's stream; the decoder's branches read its level outputs directly, so their d(level) accumulates into the
+        # activation the next stage's backward adds to
+        levels = self._pyramid(warped, "resnet_pyramids.", self.cnn.resnet_pyramids, [None] * 4)
+        z = self._decoder(levels, sizes, self.n_lanes > 1)
+        h = self.conv(z, "feature_concat.0", 1, 1, relu=True)
+        # unpadded three-channel 1x1 head -> bilinear to (H, W) (surface_normal.py:143-144) -> inverse warp + R^T + F.normalize (:166-170)
+        w2, b2 = self.param["feature_concat.2.weight"], self.param["feature_concat.2.bias"]
+        co, ch = w2.shape[0], w2.shape[1]
+        hh, hw_ = h.t.shape[1], h.t.shape[2]
+        low = self._empty(B, co, hh, hw_)
+        raw = self._empty(B, co, H, W)
+        L.check(lib.vidc_head_conv1x1_upsample(L.ptr(h.t), L.ptr(w2), L.ptr(b2), L.ptr(low), L.ptr(raw), B, hh, hw_, ch, h.ld, co, 0, H, W, 0, L.current_stream()),
+                "head")
+        pred = self._empty(B, 3, H, W)
+        L.check(lib.vidc_warp2dof_inv_rot_norm(L.ptr(raw), L.ptr(params), L.ptr(pred), B, H, W, wp.cx, wp.cy, ac, 1, L.current_stream()), "inverse warp")
+        self._pred_grad = None
+
+        def head_backward():
+            d_raw = self._empty(B, 3, H, W)
+            L.check(lib.vidc_warp2dof_inv_rot_norm_backward(L.ptr(raw), L.ptr(self._pred_grad), L.ptr(params), L.ptr(d_raw), B, H, W, wp.cx, wp.cy, ac, 1,
+                                                            L.current_stream()), "inverse warp_bwd")
+            g_low = self._empty(B * co, hh, hw_)                 # the planar gradient is B * 3 one-channel images
+            L.check(lib.vidc_upsample_bilinear_ac_backward(L.ptr(d_raw), L.ptr(g_low), B * co, hh, hw_, 1, 1, 1, H, W, L.current_stream()), "upsample_bwd")
+            h.grad = self._empty(B, hh, hw_, ch)
+            sc = self._scratch_bytes(lib.vidc_head_backward_multi_scratch_bytes(B, hh, hw_, ch, co, 0))
+            L.check(lib.vidc_head_backward_multi(L.ptr(g_low), L.ptr(h.t), L.ptr(w2), L.ptr(h.grad), L.ptr(self.grad["feature_concat.2.weight"]),
+                                                 L.ptr(self.grad["feature_concat.2.bias"]), B, hh, hw_, ch, h.ld, ch, co, 0, L.ptr(sc), L.current_stream()), "head_bwd")
+
+        self._record(head_backward)
+        self._pred = pred
+        self.flush_counters()
+        return pred
+
+    def loss_and_backward(self, pred, normal_gt, mask):
+        """network_run.py:181-189 + `total_loss.backward()`: fills the flat gradient buffer; returns the loss (0-dim fp64 GPU tensor).  The
+        angle sum and N of this step are in `self._stats` ([loss, N, angle])."""
+        B, _, H, W = pred.shape
+        gt = normal_gt.contiguous().float()
+        m = mask.reshape(B, H, W).contiguous().float()
+        if tuple(gt.shape) != (B, 3, H, W):
+            raise RuntimeError("SurfaceNormalTrainer: normal_gt must be (B, 3, H, W) = %s, got %s" % ((B, 3, H, W), tuple(gt.shape)))
+        self._pred_grad = self._empty(B, 3, H, W)
+        st = self._stats
+        sc = self._scratch_bytes(L.lib().vidc_normal_l1_loss_scratch_bytes(B, H, W))
+        L.check(L.lib().vidc_normal_l1_loss(L.ptr(pred), L.ptr(gt), L.ptr(m), B, H, W, int(self.normalize_prediction), L.ptr(st), L.ptr(st[1:]), L.ptr(st[2:]),
+                                            L.ptr(self._pred_grad), L.ptr(sc), L.current_stream()), "normal loss")
+        self._run_tape()
+        return st[0].clone()
+
+    @torch.no_grad()
+    def forward_backward(self, image, gravity, alignment, normal_gt, mask):
+        for t in (image, gravity, alignment, normal_gt, mask):
+            if not t.is_cuda:
+                raise RuntimeError("SurfaceNormalTrainer takes GPU tensors only (no CPU fallback)")
+        if not self.cnn.training:
+            raise RuntimeError("call cnn.train() first (network_run.py:232): the trainer implements BatchNorm's train() mode")
+        pred = self.forward(image.float(), gravity, alignment)
+        loss = self.loss_and_backward(pred, normal_gt, mask)
+        return loss, pred
+
+    def _eager_forward_backward(self, image, gravity, alignment, normal_gt, mask, multi=False):
+        return self.forward_backward(image, gravity, alignment, normal_gt, mask)[0], []
+
+    def _record_step(self, static, multi):
+        return self.forward_backward(*static)
+
+    def step(self, image, gravity, alignment, normal_gt, mask):
+        """One `_run_training_iteration`: returns the loss (0-dim fp64 GPU tensor); `last_angle` holds the angle sum.  From the third step of
+        a shape on the forward + backward is replayed as one captured hipGraph (VIDC_TRAIN_GRAPH=0: always eager); Adam stays outside."""
+        self._refuse_ranks()
+        self._check_bindings()
+        ins = (image, gravity, alignment, normal_gt, mask)
+        if self.use_graph:
+            for t in ins:                     # (before a capture starts, not inside it)
+                if not t.is_cuda:
+                    raise RuntimeError("SurfaceNormalTrainer takes GPU tensors only (no CPU fallback)")
+            if not self.cnn.training:
+                raise RuntimeError("call cnn.train() first (network_run.py:232): the trainer implements BatchNorm's train() mode")
+            loss, _ = self._graphed(ins)
+        else:
+            loss, _ = self._eager_forward_backward(*ins)
+        self.last_count, self.last_angle = self._stats[1].clone(), self._stats[2].clone()
+        self.optimizer_step(reduced=True)
+        self.last_loss = loss
+        return loss
