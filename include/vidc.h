@@ -571,8 +571,16 @@ int vidc_maxpool3x3s2_backward(const float* x, const float* dy, float* dx, int B
 /* Backward of vidc_upsample_bilinear_ac: dy [B][H][W] rows -> dx [B][h][w] rows (gather form, deterministic). */
 int vidc_upsample_bilinear_ac_backward(const float* dy, float* dx, int B, int h, int w, int C, int lddy, int lddx, int H, int W,
                                        vidc_stream_t stream);
-/* Backward of the padded 1x1 head conv (depth_completion.py:145: Conv2d(192, 1, 1, padding=1)): g_low [B][h+2][w+2] -> dx NHWC
- * [B][h][w][C], dw [C], dbias [1].  scratch: vidc_head_backward_scratch_bytes. */
+/* Backward of the 1x1 head conv of vidc_head_conv1x1_upsample with Cout = 1..4 output channels and zero padding `pad`
+ * (surface_normal.py:143: Conv2d(64, 3, 1); depth_completion.py:145: Conv2d(192, 1, 1, padding=1)) -- the one implementation, csrc/train.hip.
+ * g_low: [B*Cout][h+2pad][w+2pad] planes, the layout of that call's `lowres`; x: NHWC [B][h][w][ldx]; wgt: [Cout][C] ->
+ * dx NHWC [B][h][w][lddx], dw [Cout][C], dbias [Cout] (over the whole padded plane: a padded 1x1 conv's border outputs are the bias).
+ * dw, dbias: fp64 chunk partials reduced in a fixed order.  scratch: vidc_head_backward_multi_scratch_bytes, 8-byte aligned. */
+size_t vidc_head_backward_multi_scratch_bytes(int B, int h, int w, int C, int Cout, int pad);
+int vidc_head_backward_multi(const float* g_low, const float* x, const float* wgt, float* dx, float* dw, float* dbias, int B, int h, int w,
+                             int C, int ldx, int lddx, int Cout, int pad, void* scratch, vidc_stream_t stream);
+/* The depth network's head: vidc_head_backward_multi with Cout = 1, pad = 1 (forwarding wrappers; the same scratch size).  g_low
+ * [B][h+2][w+2] -> dx NHWC [B][h][w][lddx], dw [C], dbias [1]. */
 size_t vidc_head_backward_scratch_bytes(int B, int h, int w, int C);
 int vidc_head_backward(const float* g_low, const float* x, const float* wgt, float* dx, float* dw, float* dbias, int B, int h, int w, int C,
                        int ldx, int lddx, void* scratch, vidc_stream_t stream);
@@ -659,7 +667,7 @@ int vidc_stem_wgrad(const float* dy, const float* x_nchw, float* dw_oihw, int B,
                     vidc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Training step of the surface-normal network: what it needs beyond the entries above (csrc/sn_train.hip)
+ * Training step of the surface-normal network: what it needs beyond the entries above (csrc/sn_train.hip: the loss)
  * ---------------------------------------------------------------------------------------------- */
 
 /* `_network_loss`, branch `_network_estimates_normal()` (network_run.py:181-189) + compute_normal_vectors_loss_l1 (normal_utils.py:20-34)
@@ -680,14 +688,6 @@ int vidc_stem_wgrad(const float* dy, const float* x_nchw, float* dw_oihw, int B,
 size_t vidc_normal_l1_loss_scratch_bytes(int B, int H, int W);
 int vidc_normal_l1_loss(const float* pred, const float* normal_gt, const float* mask, int B, int H, int W, int normalize_prediction,
                         double* loss, double* count, double* angle, float* dpred, void* scratch, vidc_stream_t stream);
-/* Backward of the 1x1 head conv of vidc_head_conv1x1_upsample with Cout = 1..4 output channels and zero padding `pad`
- * (surface_normal.py:143: Conv2d(64, 3, 1); pad = 1, Cout = 1 is vidc_head_backward's case, which stays the depth trainer's entry).
- * g_low: [B*Cout][h+2pad][w+2pad] planes, the layout of that call's `lowres`; x: NHWC [B][h][w][ldx]; wgt: [Cout][C] ->
- * dx NHWC [B][h][w][lddx], dw [Cout][C], dbias [Cout] (over the whole padded plane: a padded 1x1 conv's border outputs are the bias).
- * dw, dbias: fp64 chunk partials reduced in a fixed order.  scratch: vidc_head_backward_multi_scratch_bytes, 8-byte aligned. */
-size_t vidc_head_backward_multi_scratch_bytes(int B, int h, int w, int C, int Cout, int pad);
-int vidc_head_backward_multi(const float* g_low, const float* x, const float* wgt, float* dx, float* dw, float* dbias, int B, int h, int w,
-                             int C, int ldx, int lddx, int Cout, int pad, void* scratch, vidc_stream_t stream);
 
 enum vidc_op_kind { VIDC_OP_CONV = 1, VIDC_OP_STEM = 2, VIDC_OP_MAXPOOL = 3, VIDC_OP_UPSAMPLE = 4, VIDC_OP_HEAD = 5,
                     VIDC_OP_WARP_PARAMS = 6, VIDC_OP_WARP_FWD = 7, VIDC_OP_WARP_INV = 8, VIDC_OP_COPY = 9, VIDC_OP_SPLIT = 10,

@@ -120,18 +120,27 @@ def test_normal_loss_kernel_vs_float64_autograd(B, H, W, flag):
 
 
 # ---- the head backward ----------------------------------------------------------------------------------------------------------------
-def _head_backward_multi(g_low, x, wgt, pad):
+def _head_backward_multi(g_low, x, wgt, pad, ld=None):
+    """vidc_head_backward_multi on CPU inputs -> (dx, dw, dbias) on the CPU.  ld: x and dx are channels 2 .. 2 + C of buffers ld wide; what
+    the kernel leaves of dx's buffer outside the slice must be the fill."""
     from vi_depth_completion_amd import _lib as L
     lib = L.lib()
     B, h, w, C = x.shape
     co = wgt.shape[0]
-    gd, xd, wd = g_low.to(DEV), x.to(DEV), wgt.to(DEV)
-    dx, dw, db = torch.full((B, h, w, C), 7.0, device=DEV), torch.full((co, C), 7.0, device=DEV), torch.full((co,), 7.0, device=DEV)
+    ld = C if ld is None else ld
+    off = 2 if ld > C else 0
+    gd, wd = g_low.to(DEV), wgt.to(DEV)
+    x_buf, dx_buf = torch.full((B, h, w, ld), 3.0, device=DEV), torch.full((B, h, w, ld), 7.0, device=DEV)
+    xd, dx = x_buf[..., off:off + C], dx_buf[..., off:off + C]
+    xd.copy_(x)
+    dw, db = torch.full((co, C), 7.0, device=DEV), torch.full((co,), 7.0, device=DEV)
     sc = torch.empty(lib.vidc_head_backward_multi_scratch_bytes(B, h, w, C, co, pad), dtype=torch.uint8, device=DEV)
-    L.check(lib.vidc_head_backward_multi(L.ptr(gd), L.ptr(xd), L.ptr(wd), L.ptr(dx), L.ptr(dw), L.ptr(db), B, h, w, C, C, C, co, pad, L.ptr(sc), L.current_stream()),
+    L.check(lib.vidc_head_backward_multi(L.ptr(gd), L.ptr(xd), L.ptr(wd), L.ptr(dx), L.ptr(dw), L.ptr(db), B, h, w, C, ld, ld, co, pad, L.ptr(sc), L.current_stream()),
             "head_backward_multi")
     torch.cuda.synchronize()
-    return dx.cpu(), dw.cpu(), db.cpu()
+    outside = torch.cat([dx_buf[..., :off], dx_buf[..., off + C:]], -1)
+    assert torch.equal(outside, torch.full_like(outside, 7.0))
+    return dx.cpu().contiguous(), dw.cpu(), db.cpu()
 
 
 def _within(got, want, name):
@@ -140,14 +149,9 @@ def _within(got, want, name):
     assert err <= 2e-4 * scale, name
 
 
-@gpu
-@pytest.mark.parametrize("h,w,pad", [(5, 7, 0), (5, 7, 1), (13, 21, 0), (45, 50, 1)])
-def test_head_backward_multi_vs_float64_autograd(h, w, pad):
-    """Conv2d(64, 3, 1, padding=pad) differentiated: dx, dw, dbias against float64 F.conv2d autograd within 2e-4 of max |want|, identical
-    bits on a second run.  5 x 7 is one chunk of the weight-gradient reduction, 13 x 21 three, 45 x 50 eighteen and two workgroups of the
-    bias sum."""
-    B, C, co = 2, 64, 3
-    g = torch.Generator().manual_seed(5)
+def _head_case(B, h, w, C, co, pad, seed):
+    """Seeded (g_low, x, wgt) and Conv2d(C, co, 1, padding=pad) differentiated by float64 F.conv2d autograd: (dx NHWC, dw, dbias)."""
+    g = torch.Generator().manual_seed(seed)
     x = torch.randn(B, h, w, C, generator=g)
     wgt, bias = torch.randn(co, C, generator=g) * 0.2, torch.randn(co, generator=g)
     g_low = torch.randn(B * co, h + 2 * pad, w + 2 * pad, generator=g)
@@ -155,31 +159,63 @@ def test_head_backward_multi_vs_float64_autograd(h, w, pad):
     with torch.enable_grad():
         y = F.conv2d(xr, wr[:, :, None, None], br, padding=pad)
         (y * g_low.double().view(B, co, h + 2 * pad, w + 2 * pad)).sum().backward()
-    dx, dw, db = _head_backward_multi(g_low, x, wgt, pad)
-    _within(dx, xr.grad.permute(0, 2, 3, 1), "dx")
-    _within(dw, wr.grad, "dw")
-    _within(db, br.grad, "dbias")
-    for a, b in zip((dx, dw, db), _head_backward_multi(g_low, x, wgt, pad)):
+    return (g_low, x, wgt), (xr.grad.permute(0, 2, 3, 1), wr.grad, br.grad)
+
+
+def _check_head_backward_multi(B, h, w, C, co, pad, ld=None):
+    ins, want = _head_case(B, h, w, C, co, pad, 5)
+    got = _head_backward_multi(*ins, pad, ld)
+    for a, b, name in zip(got, want, ("dx", "dw", "dbias")):
+        _within(a, b, name)
+    for a, b in zip(got, _head_backward_multi(*ins, pad, ld)):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
 @gpu
-def test_head_backward_multi_one_channel_equals_the_depth_head():
-    """Cout = 1, pad = 1 is vidc_head_backward's case (the depth trainer keeps that entry): the two agree within the kernel bar."""
+@pytest.mark.parametrize("h,w,pad", [(5, 7, 0), (5, 7, 1), (13, 21, 0), (45, 50, 1)])
+def test_head_backward_multi_vs_float64_autograd(h, w, pad):
+    """Conv2d(64, 3, 1, padding=pad) differentiated: dx, dw, dbias against float64 F.conv2d autograd within 2e-4 of max |want|, identical
+    bits on a second run.  5 x 7 is one chunk of the weight-gradient reduction, 13 x 21 three, 45 x 50 eighteen and two workgroups of the
+    bias sum."""
+    _check_head_backward_multi(2, h, w, 64, 3, pad)
+
+
+@gpu
+@pytest.mark.parametrize("B,h,w,C,co,pad,ld", [(2, 65, 64, 64, 3, 1, None), (2, 5, 7, 20, 3, 0, None), (2, 13, 21, 64, 3, 1, 68), (1, 6, 5, 20, 4, 0, 24)],
+                         ids=["33-chunks", "60-outputs", "ld-68", "cout-4-ld-24"])
+def test_head_backward_multi_vs_float64_autograd_edge_geometries(B, h, w, C, co, pad, ld):
+    """The same check (same bar, same second run) where the geometry takes another path.  2 x 65 x 64 rows = 8320 = 33 chunks of 256: a lane
+    of the final reduction (32 lanes) sums more than one chunk.  C = 20, Cout = 3: 60 outputs, not a multiple of the 8 outputs a workgroup
+    of the final reduction holds, and fewer channels than a workgroup has threads.  ld = C + 4: x and dx are channel slices of wider
+    buffers, whose other channels the kernels must leave alone -- once more with the largest Cout the entry takes."""
+    _check_head_backward_multi(B, h, w, C, co, pad, ld)
+
+
+@gpu
+def test_head_backward_one_channel_vs_float64_autograd():
+    """vidc_head_backward (the depth network's head: Conv2d(C, 1, 1, padding=1)) against float64 F.conv2d autograd within 2e-4 of max
+    |want| (the bar of the tests above); it forwards to vidc_head_backward_multi with Cout = 1, pad = 1, so its bits are that call's, and
+    those of a second run.  2 x 13 x 21 rows: three chunks."""
     from vi_depth_completion_amd import _lib as L
     lib = L.lib()
-    B, h, w, C = 2, 5, 7, 64
-    g = torch.Generator().manual_seed(6)
-    x, wgt, g_low = torch.randn(B, h, w, C, generator=g), torch.randn(1, C, generator=g), torch.randn(B, h + 2, w + 2, generator=g)
-    dx, dw, db = _head_backward_multi(g_low, x, wgt, 1)
-    gd, xd, wd = g_low.to(DEV), x.to(DEV), wgt.to(DEV)
-    dx0, dw0, db0 = torch.empty(B, h, w, C, device=DEV), torch.empty(C, device=DEV), torch.empty(1, device=DEV)
-    sc = torch.empty(lib.vidc_head_backward_scratch_bytes(B, h, w, C), dtype=torch.uint8, device=DEV)
-    L.check(lib.vidc_head_backward(L.ptr(gd), L.ptr(xd), L.ptr(wd), L.ptr(dx0), L.ptr(dw0), L.ptr(db0), B, h, w, C, C, C, L.ptr(sc), L.current_stream()), "head_backward")
-    torch.cuda.synchronize()
-    _within(dx, dx0.cpu(), "dx")
-    _within(dw.reshape(-1), dw0.cpu(), "dw")
-    _within(db, db0.cpu(), "dbias")
+    B, h, w, C = 2, 13, 21, 64
+    (g_low, x, wgt), want = _head_case(B, h, w, C, 1, 1, 6)
+    assert lib.vidc_head_backward_scratch_bytes(B, h, w, C) == lib.vidc_head_backward_multi_scratch_bytes(B, h, w, C, 1, 1)
+
+    def run():
+        gd, xd, wd = g_low.to(DEV), x.to(DEV), wgt.to(DEV)
+        dx, dw, db = torch.full((B, h, w, C), 7.0, device=DEV), torch.full((1, C), 7.0, device=DEV), torch.full((1,), 7.0, device=DEV)
+        sc = torch.empty(lib.vidc_head_backward_scratch_bytes(B, h, w, C), dtype=torch.uint8, device=DEV)
+        L.check(lib.vidc_head_backward(L.ptr(gd), L.ptr(xd), L.ptr(wd), L.ptr(dx), L.ptr(dw), L.ptr(db), B, h, w, C, C, C, L.ptr(sc), L.current_stream()), "head_backward")
+        torch.cuda.synchronize()
+        return dx.cpu(), dw.cpu(), db.cpu()
+
+    got = run()
+    for a, b, name in zip(got, want, ("dx", "dw", "dbias")):
+        _within(a, b, name)
+    for other in (_head_backward_multi(g_low, x, wgt, 1), run()):
+        for a, b in zip(got, other):
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
 # ---- the trainer ----------------------------------------------------------------------------------------------------------------------

@@ -39,6 +39,22 @@ inline hipStream_t as_stream(vidc_stream_t s) { return reinterpret_cast<hipStrea
 
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// ---- the training kernels' workgroup (csrc/train.hip, csrc/sn_train.hip) ----------------------------------------------------------
+constexpr int TT = 256;
+inline unsigned blocks(long long n) { return (unsigned)((n + TT - 1) / TT); }
+// Sums red[k][0..TT) into red[k][0] for k = 0..K-1 (pairwise tree, fixed order).
+template <int K>
+__device__ inline void block_tree(double (*red)[TT]) {
+    __syncthreads();
+    for (int off = TT / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
+        }
+        __syncthreads();
+    }
+}
+
 // csrc/wgemm.hip: the streamed grouped GEMM behind vidc_conv2d_bn_act's tile VIDC_TILE_G96x32_STREAM
 int launch_wgemm_stream(const vidc_conv_desc& d, hipStream_t st);
 // csrc/wfused.hip: Winograd F(4x4, 3x3) in one launch behind the tile VIDC_TILE_WINO4_FUSED

@@ -1,30 +1,16 @@
 // Training step of the surface-normal network: what it needs beyond csrc/train.hip (include/vidc.h, "Training step of the surface-normal
-// network").  The normal loss of network_run.py:181-189 / normal_utils.py:20-34 with its gradient, and the backward of the 1x1 head conv
-// with up to four output channels (surface_normal.py:143).  Every sum: fp64 partials per workgroup, reduced in a fixed order -- no
-// floating-point atomics, the same bits on every run and stream.
+// network").  The normal loss of network_run.py:181-189 / normal_utils.py:20-34 with its gradient.  Every sum: fp64 partials per workgroup,
+// reduced in a fixed order -- no floating-point atomics, the same bits on every run and stream.
 #include "common.h"
 #include <cstdint>
 
 namespace {
 
-constexpr int TT = 256;
+using vidc::TT;
+using vidc::blocks;
+using vidc::block_tree;
 constexpr double kNormEps = 1e-12;            // F.normalize's default eps
 constexpr double kDegPerRad = 57.295779513082320876798154814105;
-
-inline unsigned blocks(long long n) { return (unsigned)((n + TT - 1) / TT); }
-
-// Sums red[k][0..TT) into red[k][0] for k = 0..K-1 (pairwise tree, fixed order).
-template <int K>
-__device__ inline void block_tree(double (*red)[TT]) {
-    __syncthreads();
-    for (int off = TT / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-        }
-        __syncthreads();
-    }
-}
 
 // ---- normal loss ---------------------------------------------------------------------------------------------------------------------
 // One pixel: n = pred (or F.normalize(pred)), gh = F.normalize(gt), m = mask > 0.  term = m * sum_c |n_c - gh_c|, angle = m * acos(clamp(n . gh))
@@ -144,108 +130,6 @@ __global__ void __launch_bounds__(TT) normal_loss_scale_kernel(float* __restrict
 
 inline int normal_loss_blocks(long long n_pix, int V) { return (int)((n_pix + (long long)TT * V - 1) / ((long long)TT * V)); }
 
-// ---- 1x1 head conv with Cout <= 4 output channels: backward ---------------------------------------------------------------------------
-// g_low: [B*Cout][h+2p][w+2p] planes (the layout of vidc_head_conv1x1_upsample's lowres); x: NHWC [B][h][w][C]; wgt: [Cout][C].
-constexpr int kRowsPerChunk = 256;            // rows per workgroup of the weight-gradient partial sums (vidc_head_backward's geometry)
-constexpr int kFinalLanes = 32;
-constexpr int kMaxCout = 4;
-
-// dx[b,y,x,c] = sum_o g_low[b,o,y+p,x+p] * w[o][c], o ascending
-__global__ void __launch_bounds__(TT)
-head_multi_dgrad_kernel(const float* __restrict__ g_low, const float* __restrict__ wgt, float* __restrict__ dx, int B, int h, int w, int C, int Cout, int pad,
-                        int lddx) {
-    const long long i = (long long)blockIdx.x * TT + threadIdx.x;
-    const long long total = (long long)B * h * w * C;
-    if (i >= total) return;
-    const int c = (int)(i % C);
-    long long p = i / C;
-    const int xx = (int)(p % w); p /= w;
-    const int yy = (int)(p % h);
-    const int b = (int)(p / h);
-    const int wp = w + 2 * pad;
-    const long long plane = (long long)(h + 2 * pad) * wp;
-    const float* g = g_low + (long long)b * Cout * plane + (long long)(yy + pad) * wp + xx + pad;
-    float acc = g[0] * wgt[c];
-    for (int o = 1; o < Cout; ++o) acc = fmaf(g[o * plane], wgt[o * C + c], acc);
-    dx[(((long long)b * h + yy) * w + xx) * lddx + c] = acc;
-}
-
-// partial[chunk][o][c] = sum over the chunk's rows of g_low_interior[o] * x[.., c]; one thread per (chunk, c), fp64
-__global__ void __launch_bounds__(TT)
-head_multi_wgrad_partial_kernel(const float* __restrict__ g_low, const float* __restrict__ x, int B, int h, int w, int C, int Cout, int pad, int ldx,
-                                double* __restrict__ partial) {
-    const int c = blockIdx.x * TT + threadIdx.x;
-    if (c >= C) return;
-    const long long M = (long long)B * h * w;
-    const long long r0 = (long long)blockIdx.y * kRowsPerChunk, r1 = min(M, r0 + kRowsPerChunk);
-    const int wp = w + 2 * pad;
-    const long long plane = (long long)(h + 2 * pad) * wp;
-    double s[kMaxCout] = {0.0, 0.0, 0.0, 0.0};
-    for (long long r = r0; r < r1; ++r) {
-        const int xx = (int)(r % w);
-        const long long q = r / w;
-        const int yy = (int)(q % h), b = (int)(q / h);
-        const float* g = g_low + (long long)b * Cout * plane + (long long)(yy + pad) * wp + xx + pad;
-        const double xv = (double)x[r * ldx + c];
-#pragma unroll
-        for (int o = 0; o < kMaxCout; ++o)
-            if (o < Cout) s[o] += (double)g[o * plane] * xv;
-    }
-#pragma unroll
-    for (int o = 0; o < kMaxCout; ++o)
-        if (o < Cout) partial[((size_t)blockIdx.y * Cout + o) * C + c] = s[o];
-}
-
-// n_out = Cout * C outputs; kFinalLanes lanes per output: lane j sums chunks j, j + kFinalLanes, ..., then the lanes' sums are added for j = 0, 1, ...
-__global__ void __launch_bounds__(TT) head_multi_wgrad_final_kernel(const double* __restrict__ partial, int n_chunks, int n_out, float* __restrict__ dw) {
-    __shared__ double red[kFinalLanes][TT / kFinalLanes];
-    const int l = threadIdx.x % (TT / kFinalLanes), j = threadIdx.x / (TT / kFinalLanes);
-    const int c = blockIdx.x * (TT / kFinalLanes) + l;
-    double s = 0.0;
-    if (c < n_out)
-        for (int k = j; k < n_chunks; k += kFinalLanes) s += partial[(size_t)k * n_out + c];
-    red[j][l] = s;
-    __syncthreads();
-    if (j == 0 && c < n_out) {
-        double t = red[0][l];
-#pragma unroll
-        for (int q = 1; q < kFinalLanes; ++q) t += red[q][l];
-        dw[c] = (float)t;
-    }
-}
-
-// dbias[o] = sum over b and the WHOLE padded plane (a padded 1x1 conv's border outputs are the bias): blockIdx.y = o, 16 values per thread
-constexpr int kBiasPer = 16;
-__global__ void __launch_bounds__(TT)
-head_multi_bias_partial_kernel(const float* __restrict__ g_low, int B, int Cout, long long plane, double* __restrict__ partial) {
-    __shared__ double red[1][TT];
-    const int o = blockIdx.y;
-    const long long n = (long long)B * plane, base = (long long)blockIdx.x * TT * kBiasPer;
-    double s = 0.0;
-    for (int k = 0; k < kBiasPer; ++k) {
-        const long long i = base + (long long)k * TT + threadIdx.x;
-        if (i < n) {
-            const long long b = i / plane;
-            s += (double)g_low[(b * Cout + o) * plane + (i - b * plane)];
-        }
-    }
-    red[0][threadIdx.x] = s;
-    block_tree<1>(red);
-    if (threadIdx.x == 0) partial[(size_t)o * gridDim.x + blockIdx.x] = red[0][0];
-}
-__global__ void __launch_bounds__(TT) head_multi_bias_final_kernel(const double* __restrict__ partial, int nb, float* __restrict__ dbias) {
-    __shared__ double red[1][TT];
-    const double* p = partial + (size_t)blockIdx.x * nb;
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nb; i += TT) s += p[i];
-    red[0][threadIdx.x] = s;
-    block_tree<1>(red);
-    if (threadIdx.x == 0) dbias[blockIdx.x] = (float)red[0][0];
-}
-
-inline int head_chunks(long long M) { return (int)((M + kRowsPerChunk - 1) / kRowsPerChunk); }
-inline int head_bias_blocks(long long n) { return (int)((n + (long long)TT * kBiasPer - 1) / ((long long)TT * kBiasPer)); }
-
 }  // namespace
 
 extern "C" size_t vidc_normal_l1_loss_scratch_bytes(int B, int H, int W) {
@@ -277,32 +161,5 @@ extern "C" int vidc_normal_l1_loss(const float* pred, const float* normal_gt, co
     else
         hipLaunchKernelGGL(normal_loss_scale_kernel<1>, dim3(blocks(n)), dim3(TT), 0, st, dpred, n, inv_count);
     VIDC_CHECK_LAUNCH("normal_l1_loss");
-    return VIDC_OK;
-}
-
-extern "C" size_t vidc_head_backward_multi_scratch_bytes(int B, int h, int w, int C, int Cout, int pad) {
-    if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || Cout <= 0 || pad < 0) return 0;
-    const long long M = (long long)B * h * w, n = (long long)B * (h + 2 * pad) * (w + 2 * pad);
-    return ((size_t)head_chunks(M) * Cout * C + (size_t)Cout * head_bias_blocks(n) + 8) * sizeof(double);
-}
-
-extern "C" int vidc_head_backward_multi(const float* g_low, const float* x, const float* wgt, float* dx, float* dw, float* dbias, int B, int h, int w, int C,
-                                        int ldx, int lddx, int Cout, int pad, void* scratch, vidc_stream_t stream) {
-    VIDC_REQUIRE(g_low && x && wgt && dx && dw && dbias && scratch, VIDC_ERR_NULL, "vidc_head_backward_multi: null pointer");
-    VIDC_REQUIRE(B > 0 && h > 0 && w > 0 && C > 0 && ldx >= C && lddx >= C && pad >= 0, VIDC_ERR_SHAPE, "vidc_head_backward_multi: bad shape");
-    VIDC_REQUIRE(Cout >= 1 && Cout <= kMaxCout, VIDC_ERR_SHAPE, "vidc_head_backward_multi: Cout must be 1..4 (as vidc_head_conv1x1_upsample)");
-    VIDC_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7) == 0, VIDC_ERR_SHAPE, "vidc_head_backward_multi: scratch must be 8-byte aligned");
-    hipStream_t st = vidc::as_stream(stream);
-    const long long M = (long long)B * h * w;
-    const long long plane = (long long)(h + 2 * pad) * (w + 2 * pad);
-    const int nch = head_chunks(M), nb = head_bias_blocks((long long)B * plane), n_out = Cout * C;
-    double* partial = reinterpret_cast<double*>(scratch);
-    double* p2 = partial + (size_t)nch * n_out;
-    hipLaunchKernelGGL(head_multi_dgrad_kernel, dim3(blocks(M * C)), dim3(TT), 0, st, g_low, wgt, dx, B, h, w, C, Cout, pad, lddx);
-    hipLaunchKernelGGL(head_multi_wgrad_partial_kernel, dim3(blocks(C), nch), dim3(TT), 0, st, g_low, x, B, h, w, C, Cout, pad, ldx, partial);
-    hipLaunchKernelGGL(head_multi_wgrad_final_kernel, dim3((n_out + TT / kFinalLanes - 1) / (TT / kFinalLanes)), dim3(TT), 0, st, partial, nch, n_out, dw);
-    hipLaunchKernelGGL(head_multi_bias_partial_kernel, dim3(nb, Cout), dim3(TT), 0, st, g_low, B, Cout, plane, p2);
-    hipLaunchKernelGGL(head_multi_bias_final_kernel, dim3(Cout), dim3(TT), 0, st, p2, nb, dbias);
-    VIDC_CHECK_LAUNCH("head_backward_multi");
     return VIDC_OK;
 }

@@ -13,7 +13,9 @@
 
 namespace {
 
-constexpr int TT = 256;
+using vidc::TT;
+using vidc::blocks;
+using vidc::block_tree;
 
 // What the per-channel sums become, applied by the thread that finishes a channel in chan_final_kernel (no extra launch).
 // batch mean, biased variance and invstd from the two per-channel sums (shared by chan_final_kernel's FinalStats and the kernels that
@@ -565,10 +567,17 @@ upsample_bwd4_kernel(const float* __restrict__ dy, float* __restrict__ dx, int B
     *reinterpret_cast<float4*>(dx + (unsigned)((b * h + ii) * w + jj) * (unsigned)lddx + c) = make_float4(acc[0], acc[1], acc[2], acc[3]);
 }
 
-// ---- padded 1x1 head (depth_completion.py:141-147: Conv2d(192, 1, 1, padding=1)) backward -----------------------------------------
-// g_low: [B][h+2][w+2] gradient at the 62x82 map; x: NHWC [B][h][w][C].  dx[b,y,x,c] = g_low[b,y+1,x+1] * w[c]
+// ---- 1x1 head conv with Cout <= 4 output channels and any padding: backward ---------------------------------------------------------
+// (depth_completion.py:141-147: Conv2d(192, 1, 1, padding=1); surface_normal.py:143: Conv2d(64, 3, 1))
+// g_low: [B*Cout][h+2p][w+2p] planes (the layout of vidc_head_conv1x1_upsample's lowres); x: NHWC [B][h][w][C]; wgt: [Cout][C].
+constexpr int kRowsPerChunk = 256;        // rows per workgroup of the per-channel reductions: M = 10^4..10^5 rows -> hundreds of workgroups per 64 channels
+constexpr int kFinalLanes = 32;
+constexpr int kMaxCout = 4;
+
+// dx[b,y,x,c] = sum_o g_low[b,o,y+p,x+p] * w[o][c], o ascending
 __global__ void __launch_bounds__(TT)
-head_dgrad_kernel(const float* __restrict__ g_low, const float* __restrict__ wgt, float* __restrict__ dx, int B, int h, int w, int C, int lddx) {
+head_dgrad_kernel(const float* __restrict__ g_low, const float* __restrict__ wgt, float* __restrict__ dx, int B, int h, int w, int C, int Cout, int pad,
+                  int lddx) {
     const long long i = (long long)blockIdx.x * TT + threadIdx.x;
     const long long total = (long long)B * h * w * C;
     if (i >= total) return;
@@ -577,39 +586,54 @@ head_dgrad_kernel(const float* __restrict__ g_low, const float* __restrict__ wgt
     const int xx = (int)(p % w); p /= w;
     const int yy = (int)(p % h);
     const int b = (int)(p / h);
-    dx[(((long long)b * h + yy) * w + xx) * lddx + c] = g_low[((long long)b * (h + 2) + yy + 1) * (w + 2) + xx + 1] * wgt[c];
+    const int wp = w + 2 * pad;
+    const long long plane = (long long)(h + 2 * pad) * wp;
+    const float* g = g_low + (long long)b * Cout * plane + (long long)(yy + pad) * wp + xx + pad;
+    float acc = g[0] * wgt[c];
+    for (int o = 1; o < Cout; ++o) acc = fmaf(g[o * plane], wgt[o * C + c], acc);
+    dx[(((long long)b * h + yy) * w + xx) * lddx + c] = acc;
 }
-// dw[c] = sum g_low_interior * x[...,c]; one block per channel chunk would re-read g: here one thread per (chunk, c), partials in fp64
+
+// partial[chunk][o][c] = sum over the chunk's rows of g_low_interior[o] * x[.., c]; one block per channel chunk would re-read g: here one
+// thread per (chunk, c), fp64
 __global__ void __launch_bounds__(TT)
-head_wgrad_partial_kernel(const float* __restrict__ g_low, const float* __restrict__ x, int B, int h, int w, int C, int ldx, int rows_per_chunk,
+head_wgrad_partial_kernel(const float* __restrict__ g_low, const float* __restrict__ x, int B, int h, int w, int C, int Cout, int pad, int ldx,
                           double* __restrict__ partial) {
     const int c = blockIdx.x * TT + threadIdx.x;
     if (c >= C) return;
     const long long M = (long long)B * h * w;
-    const long long r0 = (long long)blockIdx.y * rows_per_chunk, r1 = min(M, r0 + rows_per_chunk);
-    double s = 0.0;
+    const long long r0 = (long long)blockIdx.y * kRowsPerChunk, r1 = min(M, r0 + kRowsPerChunk);
+    const int wp = w + 2 * pad;
+    const long long plane = (long long)(h + 2 * pad) * wp;
+    double s[kMaxCout] = {0.0, 0.0, 0.0, 0.0};
     for (long long r = r0; r < r1; ++r) {
         const int xx = (int)(r % w);
         const long long q = r / w;
         const int yy = (int)(q % h), b = (int)(q / h);
-        s += (double)g_low[((long long)b * (h + 2) + yy + 1) * (w + 2) + xx + 1] * (double)x[r * ldx + c];
+        const float* g = g_low + (long long)b * Cout * plane + (long long)(yy + pad) * wp + xx + pad;
+        const double xv = (double)x[r * ldx + c];
+#pragma unroll
+        for (int o = 0; o < kMaxCout; ++o)
+            if (o < Cout) s[o] += (double)g[o * plane] * xv;
     }
-    partial[(size_t)blockIdx.y * C + c] = s;
+#pragma unroll
+    for (int o = 0; o < kMaxCout; ++o)
+        if (o < Cout) partial[((size_t)blockIdx.y * Cout + o) * C + c] = s[o];
 }
-// kFinalLanes lanes per output: lane j sums chunks j, j + kFinalLanes, ... and the partial sums are added in the order j = 0, 1, ... -- a
-// fixed order, so the result is reproducible; one lane per output walked up to 600 chunks serially (120 us on the critical path of every
-// pyramid's stem).
-constexpr int kFinalLanes = 32;
-__global__ void __launch_bounds__(TT) head_wgrad_final_kernel(const double* __restrict__ partial, int n_chunks, int C, float* __restrict__ dw) {
+
+// n_out outputs (the head's Cout * C, the stem's Cout * Cin * 9); kFinalLanes lanes per output: lane j sums chunks j, j + kFinalLanes, ... and
+// the lanes' sums are added in the order j = 0, 1, ... -- a fixed order, so the result is reproducible; one lane per output walked up to 600
+// chunks serially (120 us on the critical path of every pyramid's stem).
+__global__ void __launch_bounds__(TT) head_wgrad_final_kernel(const double* __restrict__ partial, int n_chunks, int n_out, float* __restrict__ dw) {
     __shared__ double red[kFinalLanes][TT / kFinalLanes];
     const int l = threadIdx.x % (TT / kFinalLanes), j = threadIdx.x / (TT / kFinalLanes);
     const int c = blockIdx.x * (TT / kFinalLanes) + l;
     double s = 0.0;
-    if (c < C)
-        for (int k = j; k < n_chunks; k += kFinalLanes) s += partial[(size_t)k * C + c];
+    if (c < n_out)
+        for (int k = j; k < n_chunks; k += kFinalLanes) s += partial[(size_t)k * n_out + c];
     red[j][l] = s;
     __syncthreads();
-    if (j == 0 && c < C) {
+    if (j == 0 && c < n_out) {
         double t = red[0][l];
 #pragma unroll
         for (int q = 1; q < kFinalLanes; ++q) t += red[q][l];
@@ -617,34 +641,36 @@ __global__ void __launch_bounds__(TT) head_wgrad_final_kernel(const double* __re
     }
 }
 
-// ---- generic fixed-order sum of n floats (fp64): head bias gradient, loss ----------------------------------------------------------
-__global__ void __launch_bounds__(TT) sum_partial_kernel(const float* __restrict__ v, long long n, int per, double* __restrict__ partial) {
-    __shared__ double red[TT];
-    const long long base = (long long)blockIdx.x * TT * per;
+// ---- fixed-order fp64 sums of float planes: the loss (one plane) and the head's bias gradient ---------------------------------------
+// v: [B][n_planes][plane].  partial[o][blockIdx.x] = this workgroup's share of the sum over b of plane o = blockIdx.y (for the head that is
+// the WHOLE padded plane: a padded 1x1 conv's border outputs are the bias); kSumPer values per thread.
+constexpr int kSumPer = 16;
+inline int sum_blocks(long long n) { return (int)((n + (long long)TT * kSumPer - 1) / ((long long)TT * kSumPer)); }
+__global__ void __launch_bounds__(TT) sum_partial_kernel(const float* __restrict__ v, int B, int n_planes, long long plane, double* __restrict__ partial) {
+    __shared__ double red[1][TT];
+    const int o = blockIdx.y;
+    const long long n = (long long)B * plane, base = (long long)blockIdx.x * TT * kSumPer;
     double s = 0.0;
-    for (int k = 0; k < per; ++k) {
+    for (int k = 0; k < kSumPer; ++k) {
         const long long i = base + (long long)k * TT + threadIdx.x;
-        if (i < n) s += (double)v[i];
+        if (i < n) {
+            const long long b = i / plane;
+            s += (double)v[(b * n_planes + o) * plane + (i - b * plane)];
+        }
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = TT / 2; off > 0; off >>= 1) {
-        if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    red[0][threadIdx.x] = s;
+    block_tree<1>(red);
+    if (threadIdx.x == 0) partial[(size_t)o * gridDim.x + blockIdx.x] = red[0][0];
 }
-__global__ void __launch_bounds__(TT) sum_final_kernel(const double* __restrict__ partial, int n, double* __restrict__ out_d, float* __restrict__ out_f) {
-    __shared__ double red[TT];
+// one workgroup per plane: its nb partials in a fixed order
+__global__ void __launch_bounds__(TT) sum_final_kernel(const double* __restrict__ partial, int nb, double* __restrict__ out_d, float* __restrict__ out_f) {
+    __shared__ double red[1][TT];
+    const double* p = partial + (size_t)blockIdx.x * nb;
     double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += TT) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = TT / 2; off > 0; off >>= 1) {
-        if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { if (out_d) *out_d = red[0]; if (out_f) *out_f = (float)red[0]; }
+    for (int i = threadIdx.x; i < nb; i += TT) s += p[i];
+    red[0][threadIdx.x] = s;
+    block_tree<1>(red);
+    if (threadIdx.x == 0) { if (out_d) out_d[blockIdx.x] = red[0][0]; if (out_f) out_f[blockIdx.x] = (float)red[0][0]; }
 }
 
 // ---- masked L1 loss (network_run.py:163-173): terms |pred - gt| / (H*W) on gt > 0, and d loss / d pred ----------------------------
@@ -1194,7 +1220,6 @@ stem_wgrad_partial_kernel(const float* __restrict__ dy, const float* __restrict_
 namespace {
 constexpr int kStemRows = 64;             // rows per workgroup of vidc_stem_wgrad (M = 153 600 at batch 8: 2400 chunks of 192 threads -- the kernel is
                                           // a chain of dependent L2 latencies per thread, so it wants many short chains rather than few long ones)
-constexpr int kRowsPerChunk = 256;        // rows per workgroup of the per-channel reductions: M = 10^4..10^5 rows -> hundreds of workgroups per 64 channels
 inline int chunks_for(long long M) { return (int)((M + kRowsPerChunk - 1) / kRowsPerChunk); }
 // Rows per workgroup of the per-channel reductions (chan_partial_kernel): about 512 workgroups per launch whatever the shape -- a function of
 // (M, C) only, so the summation order of a given tensor never changes.  Multiple of 16 (the row-lanes of a block), 32..256.
@@ -1205,7 +1230,6 @@ inline int rows_for(long long M, int C) {
     return (int)(r < 32 ? 32 : (r > 256 ? 256 : r));
 }
 inline int chunks_for(long long M, int C) { const int r = rows_for(M, C); return (int)((M + r - 1) / r); }
-inline unsigned blocks(long long n) { return (unsigned)((n + TT - 1) / TT); }
 // The final reduction of a BatchNorm's chunk sums inside the consuming kernel's prologue (bn_apply_fold_kernel, bn_bwd_apply_t64_kernel<true>)
 // instead of a chan_final launch: every 64 x 64 workgroup re-reads n_chunks x 64 x 2 doubles, so it is only offered where pixel blocks x
 // chunks is small -- the ResNet-101 layer-3 / layer-4 maps and the coarse decoder levels, three quarters of a step's BatchNorms.  Same sums,
@@ -1391,30 +1415,39 @@ extern "C" int vidc_upsample_bilinear_ac_backward(const float* dy, float* dx, in
     return VIDC_OK;
 }
 
-extern "C" int vidc_head_backward(const float* g_low, const float* x, const float* wgt, float* dx, float* dw, float* dbias, int B, int h, int w, int C,
-                                  int ldx, int lddx, void* scratch, vidc_stream_t stream) {
-    VIDC_REQUIRE(g_low && x && wgt && dx && dw && dbias && scratch, VIDC_ERR_NULL, "vidc_head_backward: null pointer");
-    VIDC_REQUIRE(B > 0 && h > 0 && w > 0 && C > 0, VIDC_ERR_SHAPE, "vidc_head_backward: bad shape");
+extern "C" size_t vidc_head_backward_multi_scratch_bytes(int B, int h, int w, int C, int Cout, int pad) {
+    if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || Cout <= 0 || pad < 0) return 0;
+    const long long M = (long long)B * h * w, n = (long long)B * (h + 2 * pad) * (w + 2 * pad);
+    return ((size_t)chunks_for(M) * Cout * C + (size_t)Cout * sum_blocks(n) + 8) * sizeof(double);
+}
+
+extern "C" int vidc_head_backward_multi(const float* g_low, const float* x, const float* wgt, float* dx, float* dw, float* dbias, int B, int h, int w, int C,
+                                        int ldx, int lddx, int Cout, int pad, void* scratch, vidc_stream_t stream) {
+    VIDC_REQUIRE(g_low && x && wgt && dx && dw && dbias && scratch, VIDC_ERR_NULL, "vidc_head_backward_multi: null pointer");
+    VIDC_REQUIRE(B > 0 && h > 0 && w > 0 && C > 0 && ldx >= C && lddx >= C && pad >= 0, VIDC_ERR_SHAPE, "vidc_head_backward_multi: bad shape");
+    VIDC_REQUIRE(Cout >= 1 && Cout <= kMaxCout, VIDC_ERR_SHAPE, "vidc_head_backward_multi: Cout must be 1..4 (as vidc_head_conv1x1_upsample)");
+    VIDC_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7) == 0, VIDC_ERR_SHAPE, "vidc_head_backward_multi: scratch must be 8-byte aligned");
     hipStream_t st = vidc::as_stream(stream);
     const long long M = (long long)B * h * w;
-    const int nch = chunks_for(M);
+    const long long plane = (long long)(h + 2 * pad) * (w + 2 * pad);
+    const int nch = chunks_for(M), nb = sum_blocks((long long)B * plane), n_out = Cout * C;
     double* partial = reinterpret_cast<double*>(scratch);
-    hipLaunchKernelGGL(head_dgrad_kernel, dim3(blocks(M * C)), dim3(TT), 0, st, g_low, wgt, dx, B, h, w, C, lddx);
-    hipLaunchKernelGGL(head_wgrad_partial_kernel, dim3(blocks(C), nch), dim3(TT), 0, st, g_low, x, B, h, w, C, ldx, kRowsPerChunk, partial);
-    hipLaunchKernelGGL(head_wgrad_final_kernel, dim3((C + TT / kFinalLanes - 1) / (TT / kFinalLanes)), dim3(TT), 0, st, partial, nch, C, dw);
-    const long long n = (long long)B * (h + 2) * (w + 2);
-    const int nb = (int)((n + (long long)TT * 16 - 1) / ((long long)TT * 16));
-    double* p2 = partial + (size_t)nch * C;
-    hipLaunchKernelGGL(sum_partial_kernel, dim3(nb), dim3(TT), 0, st, g_low, n, 16, p2);
-    hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(TT), 0, st, p2, nb, (double*)nullptr, dbias);
-    VIDC_CHECK_LAUNCH("head_backward");
+    double* p2 = partial + (size_t)nch * n_out;
+    hipLaunchKernelGGL(head_dgrad_kernel, dim3(blocks(M * C)), dim3(TT), 0, st, g_low, wgt, dx, B, h, w, C, Cout, pad, lddx);
+    hipLaunchKernelGGL(head_wgrad_partial_kernel, dim3(blocks(C), nch), dim3(TT), 0, st, g_low, x, B, h, w, C, Cout, pad, ldx, partial);
+    hipLaunchKernelGGL(head_wgrad_final_kernel, dim3((n_out + TT / kFinalLanes - 1) / (TT / kFinalLanes)), dim3(TT), 0, st, partial, nch, n_out, dw);
+    hipLaunchKernelGGL(sum_partial_kernel, dim3(nb, Cout), dim3(TT), 0, st, g_low, B, Cout, plane, p2);
+    hipLaunchKernelGGL(sum_final_kernel, dim3(Cout), dim3(TT), 0, st, p2, nb, (double*)nullptr, dbias);
+    VIDC_CHECK_LAUNCH("head_backward_multi");
     return VIDC_OK;
 }
 
-extern "C" size_t vidc_head_backward_scratch_bytes(int B, int h, int w, int C) {
-    const long long M = (long long)B * h * w;
-    const long long n = (long long)B * (h + 2) * (w + 2);
-    return ((size_t)chunks_for(M) * C + (size_t)((n + (long long)TT * 16 - 1) / ((long long)TT * 16)) + 8) * sizeof(double);
+// the depth network's head: one output channel, pad 1
+extern "C" size_t vidc_head_backward_scratch_bytes(int B, int h, int w, int C) { return vidc_head_backward_multi_scratch_bytes(B, h, w, C, 1, 1); }
+
+extern "C" int vidc_head_backward(const float* g_low, const float* x, const float* wgt, float* dx, float* dw, float* dbias, int B, int h, int w, int C,
+                                  int ldx, int lddx, void* scratch, vidc_stream_t stream) {
+    return vidc_head_backward_multi(g_low, x, wgt, dx, dw, dbias, B, h, w, C, ldx, lddx, 1, 1, scratch, stream);
 }
 
 extern "C" int vidc_masked_l1_loss(const float* pred, const float* gt, long long n, int hw, double* loss, float* dpred, float* terms, void* scratch,
@@ -1423,8 +1456,8 @@ extern "C" int vidc_masked_l1_loss(const float* pred, const float* gt, long long
     VIDC_REQUIRE(n > 0 && hw > 0, VIDC_ERR_SHAPE, "vidc_masked_l1_loss: bad shape");
     hipStream_t st = vidc::as_stream(stream);
     hipLaunchKernelGGL(l1_loss_kernel, dim3(blocks(n)), dim3(TT), 0, st, pred, gt, n, 1.0f / (float)hw, terms, dpred);
-    const int nb = (int)((n + (long long)TT * 16 - 1) / ((long long)TT * 16));
-    hipLaunchKernelGGL(sum_partial_kernel, dim3(nb), dim3(TT), 0, st, terms, n, 16, reinterpret_cast<double*>(scratch));
+    const int nb = sum_blocks(n);
+    hipLaunchKernelGGL(sum_partial_kernel, dim3(nb), dim3(TT), 0, st, terms, 1, 1, n, reinterpret_cast<double*>(scratch));
     hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(TT), 0, st, reinterpret_cast<const double*>(scratch), nb, loss, (float*)nullptr);
     VIDC_CHECK_LAUNCH("masked_l1_loss");
     return VIDC_OK;

@@ -486,7 +486,7 @@ def upsample_bilinear_ac_backward(dy, size_in, y=None):
 
 
 def head_conv1x1_upsample_backward(dy, x, w, pad, y=None):
-    """(dx NHWC, dw, dbias) of head_conv1x1_upsample for one output channel and pad 1 (vidc_head_backward); y: the forward output when relu."""
+    """(dx NHWC, dw, dbias) of head_conv1x1_upsample for one output channel and pad 1 (vidc_head_backward_multi's Cout = 1, pad = 1); y: the forward output when relu."""
     _dev(dy, x, w, y)
     x = x.contiguous()
     B, h, wd, cin = x.shape
@@ -501,7 +501,7 @@ def head_conv1x1_upsample_backward(dy, x, w, pad, y=None):
     dx = torch.empty_like(x)
     dw = torch.empty(w.shape, dtype=torch.float32, device=x.device)
     db = torch.empty((1,), dtype=torch.float32, device=x.device)
-    sc = _scratch(L.lib().vidc_head_backward_scratch_bytes(B, h, wd, cin), x.device)
-    L.check(L.lib().vidc_head_backward(L.ptr(g_low), L.ptr(x), L.ptr(w2), L.ptr(dx), L.ptr(dw), L.ptr(db), B, h, wd, cin, cin, cin, L.ptr(sc),
-                                       L.current_stream()), "head_backward")
+    sc = _scratch(L.lib().vidc_head_backward_multi_scratch_bytes(B, h, wd, cin, 1, pad), x.device)
+    L.check(L.lib().vidc_head_backward_multi(L.ptr(g_low), L.ptr(x), L.ptr(w2), L.ptr(dx), L.ptr(dw), L.ptr(db), B, h, wd, cin, cin, cin, 1, pad, L.ptr(sc),
+                                             L.current_stream()), "head_backward")
     return dx, dw, db

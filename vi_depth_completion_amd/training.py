@@ -159,8 +159,8 @@ class GradientBuckets:
 class _TrainerBase:
     """What the two trainers share: the flat parameter / gradient / Adam-moment buffers, the recording ops (conv, bn, add, maxpool, upsample, the
     ResNet-101 pyramid and the decoder branches -- each launches its forward and records its backward on the tape), weight packing, the tape and
-    its stream lanes, graph capture / replay of a step and the Adam step.  A subclass names its pyramids (`pyramid_names`) and writes the
-    network walk, the loss and `step`.
+    its stream lanes, the head, `step` with its graph capture / replay and the Adam step.  A subclass names its pyramids (`pyramid_names`) and
+    writes the network walk (`forward`: three inputs) and the loss (`loss_and_backward`: the prediction and the remaining inputs).
 
     Build the trainer AFTER `torch.distributed.init_process_group` (and after the network is on its GPU): the flat layout of parameters, gradients, Adam
     moments and BatchNorm running statistics is chosen here (`self.layout`: "grouped" = the three pyramids interleaved per parameter name, the multi-rank
@@ -858,6 +858,55 @@ class _TrainerBase:
                 main.wait_stream(side)
         return self.add(self.add(self.add(zs[0], zs[1], False), zs[2], False), zs[3], False)
 
+    def head(self, h, key, pad, out_hw, relu):
+        """The network's last op: the 1x1 conv `key` with padding `pad` and up to four output channels -> bilinear (align_corners) to out_hw ->
+        ReLU if `relu`.  Returns the (B, Cout, H, W) planes as an Act; the backward turns their .grad into h.grad and the conv's gradients."""
+        lib = L.lib()
+        w2, b2 = self.param[key + ".weight"], self.param[key + ".bias"]
+        co, ch = w2.shape[0], w2.shape[1]
+        B, hh, hw_ = h.t.shape[:3]
+        H, W = out_hw
+        ph, pw = hh + 2 * pad, hw_ + 2 * pad
+        low = self._empty(B, co, ph, pw)
+        y = Act(self._empty(B, co, H, W))
+        L.check(lib.vidc_head_conv1x1_upsample(L.ptr(h.t), L.ptr(w2), L.ptr(b2), L.ptr(low), L.ptr(y.t), B, hh, hw_, ch, h.ld, co, pad, H, W, int(relu),
+                                               L.current_stream()), "head")
+
+        def head_backward():
+            g, n = y.grad, y.t.numel()
+            if relu:
+                g = self._empty(n)
+                L.check(lib.vidc_relu_backward(L.ptr(y.grad), L.ptr(y.t), L.ptr(g), n // 4, 4, 4, 4, 4, 0, L.current_stream()), "relu_bwd")
+            g_low = self._empty(B * co, ph, pw)                  # the planar gradient is B * Cout one-channel images
+            L.check(lib.vidc_upsample_bilinear_ac_backward(L.ptr(g), L.ptr(g_low), B * co, ph, pw, 1, 1, 1, H, W, L.current_stream()), "upsample_bwd")
+            h.grad = self._empty(B, hh, hw_, ch)
+            sc = self._scratch_bytes(lib.vidc_head_backward_multi_scratch_bytes(B, hh, hw_, ch, co, pad))
+            L.check(lib.vidc_head_backward_multi(L.ptr(g_low), L.ptr(h.t), L.ptr(w2), L.ptr(h.grad), L.ptr(self.grad[key + ".weight"]),
+                                                 L.ptr(self.grad[key + ".bias"]), B, hh, hw_, ch, h.ld, ch, co, pad, L.ptr(sc), L.current_stream()), "head_bwd")
+
+        self._record(head_backward)
+        return y
+
+    @staticmethod
+    def _level_sizes(H, W):
+        """(h, w) of the four pyramid levels of an H x W image: the stem and the max-pool halve it, then each of three stages does."""
+        def half(s):
+            return (s[0] - 1) // 2 + 1, (s[1] - 1) // 2 + 1
+        sizes = [half(half((H, W)))]
+        for _ in range(3):
+            sizes.append(half(sizes[-1]))
+        return sizes
+
+    def _begin_forward(self):
+        self.tape, self._nbt = [], []
+        self.repack()
+
+    def _end_forward(self, pred):
+        """pred: the Act of the network's output; the loss writes pred.grad, which the tape starts from."""
+        self._pred = pred
+        self.flush_counters()
+        return pred.t
+
     def _run_tape(self, stop_after_decoder=False):
         """Runs the recorded backward closures, last first, each on the stream lane it was recorded on.  stop_after_decoder: return once
         the decoder's part is done (its last closure hands the level gradients to the pyramids), leaving the pyramids' closures in
@@ -922,21 +971,53 @@ class _TrainerBase:
         from .sharding import collectives_active
         return collectives_active()
 
+    cut_at_decoder = False      # across ranks, cut the backward where the decoder's part ends and all-reduce its gradients under the rest
+
+    def _check_inputs(self, tensors):
+        """What a step refuses, before any capture starts."""
+        for t in tensors:
+            if not t.is_cuda:
+                raise RuntimeError("%s takes GPU tensors only (no CPU fallback)" % type(self).__name__)
+        if not self.cnn.training:
+            raise RuntimeError("call cnn.train() first (network_run.py:232): the trainer implements BatchNorm's train() mode")
+
+    def _after_step(self):
+        """Hook: what a subclass keeps of the step that just ran."""
+
+    @torch.no_grad()
+    def _forward_backward(self, ins, multi=False):
+        """(loss, pred) of `forward` on the first three inputs and `loss_and_backward` on the rest; multi: the tape stops after the decoder."""
+        self._check_inputs(ins)
+        pred = self.forward(*ins[:3])
+        if multi:
+            return self.loss_and_backward(pred, *ins[3:], stop_after_decoder=True), pred
+        return self.loss_and_backward(pred, *ins[3:]), pred
+
+    def _reduce_around(self, rest):
+        """Multi-rank: starts the all-reduce of the decoder's gradients, runs `rest` (the pyramids' backward) under it, then starts the others'."""
+        waits = self.buckets.all_reduce_async(self.flat_g, self._dec_off, None)
+        rest()
+        return waits + self.buckets.all_reduce_async(self.flat_g, 0, self._dec_off)
+
+    def _eager_forward_backward(self, ins, multi):
+        loss, _ = self._forward_backward(ins, multi)
+        return loss, (self._reduce_around(self._run_tape) if multi else [])
+
     def _graphed(self, ins, multi=False):
         """A step's forward + backward on `ins`: eager the first two times a shape is seen (that creates the packed-weight table, constants,
-        scratch and split-K workspaces), then captured once (`_record_step` on static copies of the inputs) and replayed.  Returns
+        scratch and split-K workspaces), then captured once (`_forward_backward` on static copies of the inputs) and replayed.  Returns
         (loss, completion callbacks of the all-reduces started)."""
         key = tuple((tuple(t.shape), t.dtype) for t in ins) + (multi,)
         ent = self._graphs.get(key)
         if ent is None:
             seen = self._graph_seen[key] = self._graph_seen.get(key, 0) + 1
             if seen <= 2:                     # eager: creates the packed-weight table, constants, scratch and split-K workspace
-                return self._eager_forward_backward(*ins, multi)
+                return self._eager_forward_backward(ins, multi)
             static = [t.clone() for t in ins]
             torch.cuda.synchronize()
             graph, rest = torch.cuda.CUDAGraph(), None
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):      # (RCCL's watchdog thread polls events while this thread captures)
-                loss, pred = self._record_step(static, multi)
+                loss, pred = self._forward_backward(static, multi)
             if multi:                         # second graph: the pyramids' backward (same memory pool: it reads the first one's tensors)
                 rest = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(rest, pool=graph.pool(), capture_error_mode="thread_local"):
@@ -947,28 +1028,41 @@ class _TrainerBase:
             dst.copy_(src)
         self._packed_fresh = True             # the graph starts with repack()
         graph.replay()
-        waits = []
-        if rest is not None:
-            waits = self.buckets.all_reduce_async(self.flat_g, self._dec_off, None)
-            rest.replay()
-            waits += self.buckets.all_reduce_async(self.flat_g, 0, self._dec_off)
-        return loss.clone(), waits
+        return loss.clone(), (self._reduce_around(rest.replay) if rest is not None else [])
 
+    def step(self, *ins):
+        """One `_run_training_iteration` on the subclass's inputs (`forward`'s three, then the loss's): returns the loss (0-dim fp64 GPU
+        tensor, this rank's frames).
+
+        The forward + backward of a step is ~4000 launches from Python (~17 us of host time each: host-bound once the convs run in the
+        bf16 modes), all with shape-static arguments, so from the third step of a given input shape on it is replayed as captured
+        hipGraphs (VIDC_TRAIN_GRAPH=0: always eager).  The all-reduce and the Adam launch (its bias correction takes the step number
+        by value) stay outside the graphs.  Across ranks the depth trainer's backward is cut where the decoder's part ends
+        (`cut_at_decoder`): the all-reduce of the decoder's gradients (59 % of the 1.24 GB) is started there and runs under the pyramids'
+        backward, the rest follows."""
+        multi = self.cut_at_decoder and self._distributed()
+        self._check_bindings()
+        self._check_inputs(ins)
+        loss, waits = self._graphed(ins, multi) if self.use_graph else self._eager_forward_backward(ins, multi)
+        for w in waits:
+            w()
+        self.optimizer_step(reduced=multi)
+        self.last_loss = loss
+        self._after_step()
+        return loss
 
 
 class DepthCompletionTrainer(_TrainerBase):
     """`_run_training_iteration` of `ModifiedFPN` (module docstring): three ResNet-101 pyramids (`self.layout`: "grouped" = interleaved per parameter
     name, the multi-rank default; "per_pyramid" otherwise), the 192-wide decoder, the padded one-channel head, the masked L1 depth loss."""
 
+    cut_at_decoder = True
+
     def forward(self, image, normal, depth_in):
         """Train-mode forward; returns the predicted depth (B,1,H,W).  The tape of backward closures is left in self.tape."""
-        self.tape, self._nbt = [], []
-        self.repack()
+        self._begin_forward()
         B, _, H, W = image.shape
-        sizes = [((H - 1) // 2 + 1, (W - 1) // 2 + 1)]
-        sizes[0] = ((sizes[0][0] - 1) // 2 + 1, (sizes[0][1] - 1) // 2 + 1)
-        for _ in range(3):
-            sizes.append(((sizes[-1][0] - 1) // 2 + 1, (sizes[-1][1] - 1) // 2 + 1))
+        sizes = self._level_sizes(H, W)
         chans = [256, 512, 1024, 2048]
         cat = [self._empty(B, sizes[l][0], sizes[l][1], 3 * chans[l]) for l in range(4)]
         levels = [Act(c) for c in cat]
@@ -1013,30 +1107,7 @@ class DepthCompletionTrainer(_TrainerBase):
         z = self._decoder(levels, sizes, multi)
         h = self.conv(z, "feature_concat.0", 1, 1, relu=True)
         # padded 1x1 head -> bilinear to (H, W) -> ReLU (depth_completion.py:143-147)
-        w2, b2 = self.param["feature_concat.2.weight"], self.param["feature_concat.2.bias"]
-        hh, hw_ = h.t.shape[1], h.t.shape[2]
-        low = self._empty(B, 1, hh + 2, hw_ + 2)
-        pred = self._empty(B, 1, H, W)
-        L.check(L.lib().vidc_head_conv1x1_upsample(L.ptr(h.t), L.ptr(w2), L.ptr(b2), L.ptr(low), L.ptr(pred), B, hh, hw_, 192, h.ld, 1, 1, H, W, 1,
-                                                   L.current_stream()), "head")
-        self._pred_grad = None
-
-        def head_backward():
-            lib = L.lib()
-            n = B * H * W
-            g = self._empty(n)
-            L.check(lib.vidc_relu_backward(L.ptr(self._pred_grad), L.ptr(pred), L.ptr(g), n // 4, 4, 4, 4, 4, 0, L.current_stream()), "relu_bwd")
-            g_low = self._empty(B, hh + 2, hw_ + 2)
-            L.check(lib.vidc_upsample_bilinear_ac_backward(L.ptr(g), L.ptr(g_low), B, hh + 2, hw_ + 2, 1, 1, 1, H, W, L.current_stream()), "upsample_bwd")
-            h.grad = self._empty(B, hh, hw_, 192)
-            sc = self._scratch_bytes(lib.vidc_head_backward_scratch_bytes(B, hh, hw_, 192))
-            L.check(lib.vidc_head_backward(L.ptr(g_low), L.ptr(h.t), L.ptr(w2), L.ptr(h.grad), L.ptr(self.grad["feature_concat.2.weight"]),
-                                           L.ptr(self.grad["feature_concat.2.bias"]), B, hh, hw_, 192, h.ld, 192, L.ptr(sc), L.current_stream()), "head_bwd")
-
-        self._record(head_backward)
-        self._pred = pred
-        self.flush_counters()
-        return pred
+        return self._end_forward(self.head(h, "feature_concat.2", 1, (H, W), relu=True))
 
     def loss_and_backward(self, pred, depth_gt, stop_after_decoder=False):
         """network_run.py:163-173 + `total_loss.backward()`: fills the flat gradient buffer; returns the loss (0-dim fp64 GPU tensor)."""
@@ -1044,64 +1115,19 @@ class DepthCompletionTrainer(_TrainerBase):
         n = pred.numel()
         gt = depth_gt.contiguous().float()
         loss = torch.zeros((), dtype=torch.float64, device=self.device)
-        self._pred_grad = self._empty(n)
+        dpred = self._pred.grad = self._empty(n)
         terms = self._empty(n)
         sc = self._scratch_bytes((n // 512 + 64) * 8)
-        L.check(L.lib().vidc_masked_l1_loss(L.ptr(pred), L.ptr(gt), n, H * W, L.ptr(loss), L.ptr(self._pred_grad), L.ptr(terms), L.ptr(sc), L.current_stream()),
+        L.check(L.lib().vidc_masked_l1_loss(L.ptr(pred), L.ptr(gt), n, H * W, L.ptr(loss), L.ptr(dpred), L.ptr(terms), L.ptr(sc), L.current_stream()),
                 "loss")
         self._run_tape(stop_after_decoder)
         return loss
 
-    @torch.no_grad()
     def forward_backward(self, image, normal, depth_in, depth_gt):
-        for t in (image, normal, depth_in, depth_gt):
-            if not t.is_cuda:
-                raise RuntimeError("DepthCompletionTrainer takes GPU tensors only (no CPU fallback)")
-        if not self.cnn.training:
-            raise RuntimeError("call cnn.train() first (network_run.py:232): the trainer implements BatchNorm's train() mode")
-        pred = self.forward(image.float(), normal.float(), depth_in.float())
-        loss = self.loss_and_backward(pred, depth_gt)
-        return loss, pred
+        return self._forward_backward((image, normal, depth_in, depth_gt))
 
     def step(self, image, normal, depth_in, depth_gt):
-        """One `_run_training_iteration`: returns the loss (0-dim fp64 GPU tensor, this rank's frames).
-
-        The forward + backward of a step is ~4000 launches from Python (~17 us of host time each: host-bound once the convs run in the
-        bf16 modes), all with shape-static arguments, so from the third step of a given input shape on it is replayed as captured
-        hipGraphs (VIDC_TRAIN_GRAPH=0: always eager).  The all-reduce and the Adam launch (its bias correction takes the step number
-        by value) stay outside the graphs.  Across ranks the backward is cut where the decoder's part ends: the all-reduce of the
-        decoder's gradients (59 % of the 1.24 GB) is started there and runs under the pyramids' backward, the rest follows."""
-        multi = self._distributed()
-        self._check_bindings()
-        if self.use_graph:
-            loss, waits = self._graphed_forward_backward(image, normal, depth_in, depth_gt, multi)
-        else:
-            loss, waits = self._eager_forward_backward(image, normal, depth_in, depth_gt, multi)
-        for w in waits:
-            w()
-        self.optimizer_step(reduced=multi)
-        self.last_loss = loss
-        return loss
-
-    @torch.no_grad()
-    def _eager_forward_backward(self, image, normal, depth_in, depth_gt, multi):
-        if not multi:
-            return self.forward_backward(image, normal, depth_in, depth_gt)[0], []
-        pred = self.forward(image.float(), normal.float(), depth_in.float())
-        loss = self.loss_and_backward(pred, depth_gt, stop_after_decoder=True)
-        waits = self.buckets.all_reduce_async(self.flat_g, self._dec_off, None)
-        self._run_tape()
-        waits += self.buckets.all_reduce_async(self.flat_g, 0, self._dec_off)
-        return loss, waits
-
-    def _record_step(self, static, multi):
-        if multi:
-            pred = self.forward(static[0].float(), static[1].float(), static[2].float())
-            return self.loss_and_backward(pred, static[3], stop_after_decoder=True), pred
-        return self.forward_backward(*static)
-
-    def _graphed_forward_backward(self, image, normal, depth_in, depth_gt, multi=False):
-        return self._graphed((image, normal, depth_in, depth_gt), multi)
+        return super().step(image, normal, depth_in, depth_gt)
 
 
 class SurfaceNormalTrainer(_TrainerBase):
@@ -1134,6 +1160,10 @@ class SurfaceNormalTrainer(_TrainerBase):
         self._stats = torch.zeros(3, dtype=torch.float64, device=self.device)      # loss, N, angle sum of the step that ran last (written by the loss kernel)
         self.last_angle = self.last_count = None
 
+    def _check_inputs(self, tensors):
+        self._refuse_ranks()
+        super()._check_inputs(tensors)
+
     def _refuse_ranks(self):
         if self._distributed():
             raise RuntimeError("SurfaceNormalTrainer runs on one rank only: the normal loss divides by N, the number of unmasked pixels of the batch "
@@ -1146,53 +1176,33 @@ class SurfaceNormalTrainer(_TrainerBase):
         if (H, W) != (wp.H, wp.W) or tuple(self.cnn.output_size) != (H, W) or cin != 3:
             raise RuntimeError("SurfaceNormalTrainer: the network is built for 3 x %d x %d images (cc_img) and output_size %s, got %d x %d x %d"
                                % (wp.H, wp.W, tuple(self.cnn.output_size), cin, H, W))
-        self.tape, self._nbt = [], []
-        self.repack()
+        self._begin_forward()
         lib, ac = L.lib(), int(wp.align_corners)
         g = gravity.reshape(B, 3).contiguous().float()
         a = alignment.reshape(B, 3).contiguous().float()
         params = self._empty(B, L.WARP_PARAMS)
         L.check(lib.vidc_warp2dof_params(L.ptr(g), L.ptr(a), B, wp.fx, wp.fy, wp.cx, wp.cy, L.ptr(wp.kinv(self.device)), W, H, L.ptr(params), L.current_stream()),
                 "warp params")
-        x = image.contiguous()
+        x = image.contiguous().float()
         warped = torch.empty_like(x)
         L.check(lib.vidc_warp2dof_fwd(L.ptr(x), L.ptr(params), L.ptr(warped), B, 3, H, W, wp.cx, wp.cy, ac, L.current_stream()), "warp")
-        sizes = [((H - 1) // 2 + 1, (W - 1) // 2 + 1)]
-        sizes[0] = ((sizes[0][0] - 1) // 2 + 1, (sizes[0][1] - 1) // 2 + 1)
-        for _ in range(3):
-            sizes.append(((sizes[-1][0] - 1) // 2 + 1, (sizes[-1][1] - 1) // 2 + 1))
         # one pyramid on the caller's stream; the decoder's branches read its level outputs directly, so their d(level) accumulates into the
         # activation the next stage's backward adds to
         levels = self._pyramid(warped, "resnet_pyramids.", self.cnn.resnet_pyramids, [None] * 4)
-        z = self._decoder(levels, sizes, self.n_lanes > 1)
+        z = self._decoder(levels, self._level_sizes(H, W), self.n_lanes > 1)
         h = self.conv(z, "feature_concat.0", 1, 1, relu=True)
         # unpadded three-channel 1x1 head -> bilinear to (H, W) (surface_normal.py:143-144) -> inverse warp + R^T + F.normalize (:166-170)
-        w2, b2 = self.param["feature_concat.2.weight"], self.param["feature_concat.2.bias"]
-        co, ch = w2.shape[0], w2.shape[1]
-        hh, hw_ = h.t.shape[1], h.t.shape[2]
-        low = self._empty(B, co, hh, hw_)
-        raw = self._empty(B, co, H, W)
-        L.check(lib.vidc_head_conv1x1_upsample(L.ptr(h.t), L.ptr(w2), L.ptr(b2), L.ptr(low), L.ptr(raw), B, hh, hw_, ch, h.ld, co, 0, H, W, 0, L.current_stream()),
-                "head")
-        pred = self._empty(B, 3, H, W)
-        L.check(lib.vidc_warp2dof_inv_rot_norm(L.ptr(raw), L.ptr(params), L.ptr(pred), B, H, W, wp.cx, wp.cy, ac, 1, L.current_stream()), "inverse warp")
-        self._pred_grad = None
+        raw = self.head(h, "feature_concat.2", 0, (H, W), relu=False)
+        pred = Act(self._empty(B, 3, H, W))
+        L.check(lib.vidc_warp2dof_inv_rot_norm(L.ptr(raw.t), L.ptr(params), L.ptr(pred.t), B, H, W, wp.cx, wp.cy, ac, 1, L.current_stream()), "inverse warp")
 
-        def head_backward():
-            d_raw = self._empty(B, 3, H, W)
-            L.check(lib.vidc_warp2dof_inv_rot_norm_backward(L.ptr(raw), L.ptr(self._pred_grad), L.ptr(params), L.ptr(d_raw), B, H, W, wp.cx, wp.cy, ac, 1,
+        def inverse_warp_backward():
+            raw.grad = self._empty(B, 3, H, W)
+            L.check(lib.vidc_warp2dof_inv_rot_norm_backward(L.ptr(raw.t), L.ptr(pred.grad), L.ptr(params), L.ptr(raw.grad), B, H, W, wp.cx, wp.cy, ac, 1,
                                                             L.current_stream()), "inverse warp_bwd")
-            g_low = self._empty(B * co, hh, hw_)                 # the planar gradient is B * 3 one-channel images
-            L.check(lib.vidc_upsample_bilinear_ac_backward(L.ptr(d_raw), L.ptr(g_low), B * co, hh, hw_, 1, 1, 1, H, W, L.current_stream()), "upsample_bwd")
-            h.grad = self._empty(B, hh, hw_, ch)
-            sc = self._scratch_bytes(lib.vidc_head_backward_multi_scratch_bytes(B, hh, hw_, ch, co, 0))
-            L.check(lib.vidc_head_backward_multi(L.ptr(g_low), L.ptr(h.t), L.ptr(w2), L.ptr(h.grad), L.ptr(self.grad["feature_concat.2.weight"]),
-                                                 L.ptr(self.grad["feature_concat.2.bias"]), B, hh, hw_, ch, h.ld, ch, co, 0, L.ptr(sc), L.current_stream()), "head_bwd")
 
-        self._record(head_backward)
-        self._pred = pred
-        self.flush_counters()
-        return pred
+        self._record(inverse_warp_backward)
+        return self._end_forward(pred)
 
     def loss_and_backward(self, pred, normal_gt, mask):
         """network_run.py:181-189 + `total_loss.backward()`: fills the flat gradient buffer; returns the loss (0-dim fp64 GPU tensor).  The
@@ -1202,47 +1212,20 @@ class SurfaceNormalTrainer(_TrainerBase):
         m = mask.reshape(B, H, W).contiguous().float()
         if tuple(gt.shape) != (B, 3, H, W):
             raise RuntimeError("SurfaceNormalTrainer: normal_gt must be (B, 3, H, W) = %s, got %s" % ((B, 3, H, W), tuple(gt.shape)))
-        self._pred_grad = self._empty(B, 3, H, W)
+        dpred = self._pred.grad = self._empty(B, 3, H, W)
         st = self._stats
         sc = self._scratch_bytes(L.lib().vidc_normal_l1_loss_scratch_bytes(B, H, W))
         L.check(L.lib().vidc_normal_l1_loss(L.ptr(pred), L.ptr(gt), L.ptr(m), B, H, W, int(self.normalize_prediction), L.ptr(st), L.ptr(st[1:]), L.ptr(st[2:]),
-                                            L.ptr(self._pred_grad), L.ptr(sc), L.current_stream()), "normal loss")
+                                            L.ptr(dpred), L.ptr(sc), L.current_stream()), "normal loss")
         self._run_tape()
         return st[0].clone()
 
-    @torch.no_grad()
     def forward_backward(self, image, gravity, alignment, normal_gt, mask):
-        for t in (image, gravity, alignment, normal_gt, mask):
-            if not t.is_cuda:
-                raise RuntimeError("SurfaceNormalTrainer takes GPU tensors only (no CPU fallback)")
-        if not self.cnn.training:
-            raise RuntimeError("call cnn.train() first (network_run.py:232): the trainer implements BatchNorm's train() mode")
-        pred = self.forward(image.float(), gravity, alignment)
-        loss = self.loss_and_backward(pred, normal_gt, mask)
-        return loss, pred
-
-    def _eager_forward_backward(self, image, gravity, alignment, normal_gt, mask, multi=False):
-        return self.forward_backward(image, gravity, alignment, normal_gt, mask)[0], []
-
-    def _record_step(self, static, multi):
-        return self.forward_backward(*static)
+        return self._forward_backward((image, gravity, alignment, normal_gt, mask))
 
     def step(self, image, gravity, alignment, normal_gt, mask):
-        """One `_run_training_iteration`: returns the loss (0-dim fp64 GPU tensor); `last_angle` holds the angle sum.  From the third step of
-        a shape on the forward + backward is replayed as one captured hipGraph (VIDC_TRAIN_GRAPH=0: always eager); Adam stays outside."""
-        self._refuse_ranks()
-        self._check_bindings()
-        ins = (image, gravity, alignment, normal_gt, mask)
-        if self.use_graph:
-            for t in ins:                     # (before a capture starts, not inside it)
-                if not t.is_cuda:
-                    raise RuntimeError("SurfaceNormalTrainer takes GPU tensors only (no CPU fallback)")
-            if not self.cnn.training:
-                raise RuntimeError("call cnn.train() first (network_run.py:232): the trainer implements BatchNorm's train() mode")
-            loss, _ = self._graphed(ins)
-        else:
-            loss, _ = self._eager_forward_backward(*ins)
+        """`_TrainerBase.step`; `last_angle` holds the step's angle sum and `last_count` its N."""
+        return super().step(image, gravity, alignment, normal_gt, mask)
+
+    def _after_step(self):
         self.last_count, self.last_angle = self._stats[1].clone(), self._stats[2].clone()
-        self.optimizer_step(reduced=True)
-        self.last_loss = loss
-        return loss
