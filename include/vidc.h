@@ -104,13 +104,17 @@ enum vidc_conv_flags {
     VIDC_ACCUM = 32,       /* y += result (z1+z2+z3+z4, surface_normal.py:168)                */
     VIDC_SPLIT_OUT = 64,   /* also write the split-bf16 image of the result to y_split (layout of y,
                               same channel stride) so a following bf16x3 conv needs no split pass */
-    VIDC_NO_F32_OUT = 128, /* with SPLIT_OUT: skip the fp32 store (nobody reads it)              */
+    VIDC_NO_F32_OUT = 128, /* with SPLIT_OUT / MXFP8_OUT / BF16_OUT: skip the fp32 store (nobody reads it) */
     VIDC_X_PLANAR_GROUPS = 512, /* group g's input is a plane of its own (B*H*W rows of ldx values at x + g*x_gs) instead of a channel slice of
                               rows shared by all groups: the grouped weight-gradient GEMMs of the training step (dY^T of the three pyramids) */
     VIDC_MXFP8_OUT = 1024, /* also write the MXFP8 image of the final result (after BN, ReLU, residual and accumulate) to y_split, in the
                               layout vidc_quant_mxfp8 writes for C = Cout (a dense image with rows of Cout channels, one plane per group);
                               with NO_F32_OUT the fp32 store is skipped.  VIDC_PREC_MXFP8 convs only (the other precisions' producers
                               are followed by vidc_quant_mxfp8). */
+    VIDC_BF16_OUT = 2048,  /* VIDC_PREC_BF16 convs only: also write the plain-bf16 image of the final result (after the affines, ReLUs, residual and
+                              accumulate) to y_split -- the bytes vidc_cast_bf16 writes for y: rows of ldy bf16 values (a dense y: groups * Cout),
+                              group g at channel g * Cout, round to nearest even; ldy even.  With NO_F32_OUT the fp32 store is skipped.  Not
+                              together with SPLIT_OUT, MXFP8_OUT or STATS_OUT (one user of y_split per launch): VIDC_ERR_SHAPE. */
     VIDC_STATS_OUT = 256   /* training, VIDC_PREC_BF16 only, no second affine / residual / accumulate / split output (with `groups` > 1 the rows of
                               the partials hold groups * Cout doubles, group-major like the channels of y):
                               `y_split` points to ceil(M / 32) x 2 x Cout doubles and receives, per block of 32 output rows, the
@@ -146,8 +150,8 @@ typedef struct vidc_conv_desc {
                               hi|lo bf16 images made by vidc_split_bf16x3 /
                               vidc_pack_conv_weight_bf16x3 (same strides as fp32)     */
     int32_t dilation;      /* tap spacing of the kernel (nn.Conv2d dilation); 0 or 1 = dense                  */
-    void* y_split;         /* split-bf16 image of y (VIDC_SPLIT_OUT), the MXFP8 image of y (VIDC_MXFP8_OUT), the channel-sum partials
-                              (VIDC_STATS_OUT), or NULL */
+    void* y_split;         /* split-bf16 image of y (VIDC_SPLIT_OUT), the MXFP8 image of y (VIDC_MXFP8_OUT), the plain-bf16 image of y
+                              (VIDC_BF16_OUT), the channel-sum partials (VIDC_STATS_OUT), or NULL */
 } vidc_conv_desc;
 
 /* Workgroup tilings (BM x BN output tile; _Kn = n k-slices reduced inside the workgroup through LDS). */
@@ -219,6 +223,9 @@ int vidc_cast_bf16(const float* x, void* y, long long rows, int C, int ldx, vidc
 int vidc_split_bf16x3(const float* x, void* y, long long rows, int C, int ldx, vidc_stream_t stream);
 /* OIHW fp32 -> split packed weights [Cout][Cin/32][KH][KW][hi|lo] (one group per call). */
 int vidc_pack_conv_weight_bf16x3(const float* w_oihw, void* w_packed, int Cout, int Cin, int KH, int KW, vidc_stream_t stream);
+/* OIHW fp32 -> plain-bf16 packed weights [Cout][Cin/64][KH][KW][64 x bf16] for VIDC_PREC_BF16 (one group per call, Cin % 64 == 0): exactly
+ * the bytes of pack kind 4 of vidc_pack_conv_weights_batched, without a descriptor array in device memory. */
+int vidc_pack_conv_weight_bf16(const float* w_oihw, void* w_packed, int Cout, int Cin, int KH, int KW, vidc_stream_t stream);
 
 int vidc_conv2d_bn_act(const vidc_conv_desc* d, vidc_stream_t stream);
 #define VIDC_SPLITK_COUNTERS 16384   /* ticket counters at the head of a split-K workspace (one per output tile) */
@@ -695,7 +702,8 @@ enum vidc_op_kind { VIDC_OP_CONV = 1, VIDC_OP_STEM = 2, VIDC_OP_MAXPOOL = 3, VID
                     /* 15: retired (persistent conv chain, removed in round 5) */ VIDC_OP_MASK = 16 /* vidc_mask_scale: p = x, image, y; i = B,h,w,C,ldx,ldy,H,W */,
                     VIDC_OP_WINO_IN = 17  /* vidc_winograd_input_transform: p = x, v; i = B,H,W,C,ldx,Cin,m,split,ldv */,
                     VIDC_OP_WINO_OUT = 18 /* vidc_winograd_output_transform: p = mm, y, y_split, scale1, shift1, scale2, shift2; i = B,Ho,Wo,C,Cout,ldy,m,flags,ldm */,
-                    VIDC_OP_QUANT = 19    /* vidc_quant_mxfp8: p = x, y; i = rows (lo, hi), C, ldx, groups */ };
+                    VIDC_OP_QUANT = 19    /* vidc_quant_mxfp8: p = x, y; i = rows (lo, hi), C, ldx, groups */,
+                    VIDC_OP_CAST = 20     /* vidc_cast_bf16: p = x, y; i = rows (lo, hi), C, ldx */ };
 
 typedef struct vidc_generic_args {   /* arguments of the non-conv launchers, in declaration order */
     const void* p[8];

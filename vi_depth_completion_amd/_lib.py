@@ -19,9 +19,9 @@ MAX_SEGMENTS = 4
 CLOCK_STAMP_WGS = 8      # VIDC_CLOCK_STAMP_WGS
 
 # vidc_conv_flags / vidc_up_flags / vidc_op_kind / vidc_conv_tile
-RELU1, AFFINE2, RELU2, RESIDUAL, RELU3, ACCUM, SPLIT_OUT, NO_F32_OUT, STATS_OUT, X_PLANAR_GROUPS, MXFP8_OUT = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024
+RELU1, AFFINE2, RELU2, RESIDUAL, RELU3, ACCUM, SPLIT_OUT, NO_F32_OUT, STATS_OUT, X_PLANAR_GROUPS, MXFP8_OUT, BF16_OUT = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048
 UP_RELU, UP_ACCUM, UP_NO_F32_OUT = 1, 2, 4
-OP_CONV, OP_STEM, OP_MAXPOOL, OP_UPSAMPLE, OP_HEAD, OP_WARP_PARAMS, OP_WARP_FWD, OP_WARP_INV, OP_COPY, OP_SPLIT, OP_AVGPOOL, OP_NORMALIZE, OP_DET_IM2COL, OP_NEAREST2X, _OP_RETIRED_15, OP_MASK, OP_WINO_IN, OP_WINO_OUT, OP_QUANT = range(1, 20)
+OP_CONV, OP_STEM, OP_MAXPOOL, OP_UPSAMPLE, OP_HEAD, OP_WARP_PARAMS, OP_WARP_FWD, OP_WARP_INV, OP_COPY, OP_SPLIT, OP_AVGPOOL, OP_NORMALIZE, OP_DET_IM2COL, OP_NEAREST2X, _OP_RETIRED_15, OP_MASK, OP_WINO_IN, OP_WINO_OUT, OP_QUANT, OP_CAST = range(1, 21)
 TILE_AUTO = 0
 TILE_NAMES = {0: "auto", 1: "128x128", 2: "128x64", 3: "64x128", 4: "64x64", 5: "64x64k2", 6: "32x64k2", 7: "32x32k4", 8: "32x128",
               9: "32x32k8", 10: "32x64k2d5", 11: "32x32k4d4", 12: "32x128d6", 13: "64x64k2d4", 14: "32x64k2L", 15: "32x64k2d5L", 16: "32x32k4d4L", 17: "64x64L", 18: "64x64k2d4L",
@@ -32,6 +32,7 @@ TILE_COUNT = 43
 TILE_WINO4_FUSED = 42
 PREC_FP32, PREC_BF16X3, PREC_BF16, PREC_MXFP8 = 0, 1, 2, 3
 MXFP8_TILES = range(2, 14)         # the tilings with an MXFP8 instance (include/vidc.h)
+BF16_TILES = range(1, 40)          # the tilings of the MFMA conv kernel: every one has a plain-bf16 instance (40 .. 42: the fp32-only streamed / Winograd tiles)
 SPLITK_COUNTERS = 16384            # VIDC_SPLITK_COUNTERS: ticket counters at the head of a split-K workspace
 
 _f32p = C.POINTER(C.c_float)
@@ -62,17 +63,17 @@ class ConvDesc(C.Structure):
 def conv_desc(B, H, W, Cin, Cout, KH=1, KW=1, stride=1, pad=0, dilation=1, groups=1, Ho=None, Wo=None, ldx=None, ldy=None,
               precision=PREC_FP32, x=None, w=None, y=None, scale1=None, shift1=None, shared_affine=False, scale2=None, shift2=None,
               relu1=False, relu2=False, residual=None, ldr=None, relu3=False, accumulate=False, split_out=None, mx_out=None,
-              stats_out=None, no_f32_out=False, wino_fused=False):
+              stats_out=None, no_f32_out=False, wino_fused=False, bf16_out=None):
     """The vidc_conv_desc of a direct conv (include/vidc.h:110-139), or with wino_fused of the same 3x3 / stride 1 / pad 1 conv as the
     one-launch Winograd F(4x4, 3x3) (VIDC_TILE_WINO4_FUSED, vidc.h:169-174).  Without pointers it describes the geometry only.
 
     Geometry in channels, whatever the precision: Cin / Cout per group, ldx / ldy the row strides of x and y (default: groups * Cin /
     Cout; an MXFP8 x is `groups` planes of Cin channels), ldr the residual's (default ldy).  Pointers are ints or None.  The epilogue:
     scale1 / shift1 [groups][Cout], or one [Cout] pair for every group (shared_affine); scale2 / shift2 with relu2 (AFFINE2, RELU2);
-    residual with relu3; accumulate; one image of the result in y_split: split_out (split bf16), mx_out (MXFP8) or stats_out (the
-    channel-sum partials of VIDC_STATS_OUT).  no_f32_out skips the fp32 store behind split_out / mx_out.
+    residual with relu3; accumulate; one image of the result in y_split: split_out (split bf16), mx_out (MXFP8), bf16_out (plain bf16)
+    or stats_out (the channel-sum partials of VIDC_STATS_OUT).  no_f32_out skips the fp32 store behind split_out / mx_out / bf16_out.
     tile = AUTO, splitk = 1 (plan() chooses them), except the fused Winograd form's own tile."""
-    assert sum(p is not None for p in (split_out, mx_out, stats_out)) <= 1
+    assert sum(p is not None for p in (split_out, mx_out, stats_out, bf16_out)) <= 1
     dil = max(dilation, 1)
     Ho = (H + 2 * pad - dil * (KH - 1) - 1) // stride + 1 if Ho is None else Ho
     Wo = (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1 if Wo is None else Wo
@@ -81,7 +82,8 @@ def conv_desc(B, H, W, Cin, Cout, KH=1, KW=1, stride=1, pad=0, dilation=1, group
     flags = ((RELU1 if relu1 else 0) | (AFFINE2 | (RELU2 if relu2 else 0) if scale2 is not None else 0) |
              (RESIDUAL | (RELU3 if relu3 else 0) if residual is not None else 0) | (ACCUM if accumulate else 0) |
              (SPLIT_OUT if split_out is not None else 0) | (MXFP8_OUT if mx_out is not None else 0) | (STATS_OUT if stats_out is not None else 0) |
-             (NO_F32_OUT if no_f32_out and (split_out is not None or mx_out is not None) else 0))
+             (BF16_OUT if bf16_out is not None else 0) |
+             (NO_F32_OUT if no_f32_out and (split_out is not None or mx_out is not None or bf16_out is not None) else 0))
     # group g reads x + g*x_gs, w + g*w_gs, writes y + g*y_gs (vidc.h:110-111): the groups are channel slices of x, y and the residual
     x_gs, w_gs = Cin, Cout * KH * KW * Cin
     if precision == PREC_BF16:          # vidc.h:182-184: two bf16 channels per element in Cin, ldx, x_gs (and so in w_gs)
@@ -99,7 +101,7 @@ def conv_desc(B, H, W, Cin, Cout, KH=1, KW=1, stride=1, pad=0, dilation=1, group
                     x_gs=x_gs, w_gs=w_gs, y_gs=Cout, r_gs=(0 if residual is None else Cout),
                     p_gs=(0 if shared_affine and groups > 1 else Cout),      # (with one group p_gs is never read)
                     tile=(TILE_WINO4_FUSED if wino_fused else TILE_AUTO), splitk=1, precision=precision, dilation=dil,
-                    y_split=next((p for p in (split_out, mx_out, stats_out) if p is not None), None))
+                    y_split=next((p for p in (split_out, mx_out, stats_out, bf16_out) if p is not None), None))
 
 
 def gemm_desc(rows, K, N, groups=1, ldx=None, ldy=None, precision=PREC_FP32, planar=False, x=None, w=None, y=None, scale1=None,
@@ -154,6 +156,7 @@ SIGNATURES = {
     "vidc_pack_conv_weight": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "vidc_split_bf16x3": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _vp]),
     "vidc_pack_conv_weight_bf16x3": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "vidc_pack_conv_weight_bf16": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "vidc_quant_mxfp8": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _i, _vp]),
     "vidc_pack_conv_weight_mxfp8": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "vidc_conv2d_bn_act": (C.c_int, [C.POINTER(ConvDesc), _vp]),

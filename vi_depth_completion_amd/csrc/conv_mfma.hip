@@ -79,6 +79,8 @@ typedef const __attribute__((address_space(1))) void glb_void_t;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
@@ -153,7 +155,8 @@ __device__ __forceinline__ unsigned lds_read_b32(unsigned addr) {
 // Dropping lo*lo leaves ~2^-16 relative error per product: depth RMSE 1.4e-5 vs fp32 over the whole path (bar: 1e-3).
 // PREC 2 ("bf16", the training mode BASELINE configs[4] names): plain bf16 operands, fp32 accumulate.  A 128-byte unit of a row holds
 // 64 bf16 channels, so the caller describes the tensors in units of two channels (Cin, ldx = bf16 channels / 2, weights packed per 64
-// channels) and everything up to the fragment reads is unchanged; a K unit is 2 x 2 v_mfma_f32_32x32x16_bf16.
+// channels) and everything up to the fragment reads is unchanged; a K unit is 2 x 2 v_mfma_f32_32x32x16_bf16.  VIDC_BF16_OUT (inference, the
+// bf16 mode of engine.py): the epilogue also writes the final result as the bf16 operand the next conv reads, so no cast launch follows.
 // PREC 3 ("MXFP8", include/vidc.h): e4m3 operands with one E8M0 scale per 32 K, v_mfma_scale_f32_32x32x64_f8f6f4.  A 128-byte unit of a row
 // holds 128 channels (the descriptor counts four channels per element), so DMA, ring, swizzle and split-K addressing are those of fp32; a K
 // unit is 2 scaled MFMAs of 64 k.  Lane map (checked with exact integer data, tests/test_mxfp8.py): lane l holds A[l & 31][16h + j] for
@@ -707,6 +710,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
     // VIDC_MXFP8_OUT: this group's plane pair of the image, data [M][Cout] bytes then scales [M][Cout / 32]
     unsigned char* ymx = st_mx ? reinterpret_cast<unsigned char*>(a.y_split) + (size_t)g * a.M * a.Cout / 32 * 33 : nullptr;
     double* stats_out = (PREC == 2 && (a.flags & VIDC_STATS_OUT)) ? reinterpret_cast<double*>(a.y_split) : nullptr;
+    // VIDC_BF16_OUT: the plain-bf16 image of y -- rows of ldy bf16 values, this group's channels at g * Cout (vidc_cast_bf16's bytes)
+    unsigned short* ybf = (PREC == 2 && (a.flags & VIDC_BF16_OUT)) ? a.y_split + (size_t)g * a.Cout : nullptr;
 #ifndef VIDC_CONV_TIMING
     // ---- split-K without a second launch: every k-slice workgroup stores its fp32 partial tile, takes a ticket on the tile's
     //      counter (head of the workspace; device-scope atomic), and the LAST one to arrive sums the splitk partials in slice
@@ -845,6 +850,22 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
                         if (FULL || mrow + dm < a.M) store_split(ysp, (size_t)(mrow + dm), a.ldy, n, v[r]);
                     }
                 }
+                if constexpr (PREC == 2) if (ybf) {
+                    // Lanes li and li ^ 1 hold channels n and n ^ 1 of the same 16 rows.  Per register pair (rows dm, dm + 1) they swap one value
+                    // (DPP quad_perm [1,0,3,2]: no LDS), so that the even lane owns both channels of row dm and the odd lane both of row dm + 1:
+                    // one hardware-converted (round to nearest even) bf16 pair = one dword store per lane, 64 contiguous bytes per row and half-wave.
+                    const bool odd = li & 1;
+                    unsigned* row0 = reinterpret_cast<unsigned*>(ybf + (size_t)(mrow + (odd ? 1 : 0)) * a.ldy + (n & ~1));
+#pragma unroll
+                    for (int p = 0; p < 8; ++p) {
+                        const float keep = odd ? v[2 * p + 1] : v[2 * p], give = odd ? v[2 * p] : v[2 * p + 1];
+                        const float got = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, give), 0xB1, 0xF, 0xF, true));
+                        const f32x2 pair = {odd ? got : keep, odd ? keep : got};          // (channel n & ~1, channel n | 1)
+                        const int dm = ((2 * p) & 3) + 8 * ((2 * p) >> 2);                   // row of register 2p; register 2p + 1 is the next row
+                        if (FULL || mrow + dm + (odd ? 1 : 0) < a.M)
+                            row0[(size_t)dm * a.ldy / 2] = __builtin_bit_cast(unsigned, __builtin_convertvector(pair, bf16x2));
+                    }
+                }
                 if constexpr (MX) if (st_mx) {
                     // one register = one row's 32 channels nb .. nb + 31 on the 32 lanes of a half: the block's amax is a 5-step butterfly
 #pragma unroll
@@ -947,6 +968,25 @@ __global__ void __launch_bounds__(256) pack_weight_bf16x3_kernel(const float* __
     unsigned short* base = wp + ((long long)o * (K / 32) + k / 32) * 64 + (k & 31);
     base[0] = hi;
     base[32] = lo;
+}
+
+// OIHW fp32 -> plain-bf16 packed [Cout][Cin/64][KH][KW][64 x bf16] (the bytes of pack kind 4 of vidc_pack_conv_weights_batched); one thread
+// per 8 consecutive packed values = one 16-byte store
+__global__ void __launch_bounds__(256) pack_weight_bf16_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp, int Cout, int Cin,
+                                                               int KH, int KW) {
+    const long long total8 = (long long)Cout * Cin * KH * KW / 8;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total8) return;
+    const int K = Cin * KH * KW;
+    const int o = (int)(idx * 8 / K), k = (int)(idx * 8 - (long long)o * K);
+    const int ci = k & 63, u = k >> 6, taps = KH * KW;
+    const int cu = u / taps, tap = u - cu * taps, kh = tap / KW, kw = tap - kh * KW, c = cu * 64 + ci;
+    unsigned short h[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = bf16_rne(w[(((long long)o * Cin + c + i) * KH + kh) * KW + kw]);
+    uint4 v;
+    v.x = h[0] | ((unsigned)h[1] << 16); v.y = h[2] | ((unsigned)h[3] << 16); v.z = h[4] | ((unsigned)h[5] << 16); v.w = h[6] | ((unsigned)h[7] << 16);
+    *reinterpret_cast<uint4*>(wp + idx * 8) = v;
 }
 
 struct TileInfo { int bm, bn, wmw, wnw, wkw, ns; };   // tiles >= kFirstLoaderTile run with loader waves
@@ -1065,11 +1105,14 @@ int validate(const vidc_conv_desc* d) {
     VIDC_REQUIRE(!(d->flags & VIDC_MXFP8_OUT) || (d->precision == VIDC_PREC_MXFP8 && d->y_split), VIDC_ERR_SHAPE,
                  "conv: MXFP8_OUT needs VIDC_PREC_MXFP8 and y_split");
     VIDC_REQUIRE(d->precision != VIDC_PREC_BF16 || !(d->flags & VIDC_SPLIT_OUT), VIDC_ERR_SHAPE, "conv: SPLIT_OUT writes the bf16x3 format, not plain bf16");
+    VIDC_REQUIRE(!(d->flags & VIDC_BF16_OUT) || (d->precision == VIDC_PREC_BF16 && d->y_split && d->ldy % 2 == 0 &&
+                                                 !(d->flags & (VIDC_SPLIT_OUT | VIDC_MXFP8_OUT | VIDC_STATS_OUT))),
+                 VIDC_ERR_SHAPE, "conv: BF16_OUT needs VIDC_PREC_BF16, y_split and an even ldy, without SPLIT_OUT / MXFP8_OUT / STATS_OUT");
     VIDC_REQUIRE(d->splitk == 1 || d->workspace || d->tile == VIDC_TILE_G96x32_STREAM || d->tile == VIDC_TILE_G96x64_STREAM3, VIDC_ERR_NULL, "conv: split-K needs a workspace");
     VIDC_REQUIRE(!(d->flags & VIDC_SPLIT_OUT) || (d->y_split && d->Cout % 32 == 0 && d->ldy % 32 == 0), VIDC_ERR_NULL,
                  "conv: SPLIT_OUT needs y_split and Cout, ldy multiples of 32");
-    VIDC_REQUIRE(!(d->flags & VIDC_NO_F32_OUT) || (d->flags & (VIDC_SPLIT_OUT | VIDC_MXFP8_OUT)), VIDC_ERR_SHAPE,
-                 "conv: NO_F32_OUT without SPLIT_OUT / MXFP8_OUT writes nothing");
+    VIDC_REQUIRE(!(d->flags & VIDC_NO_F32_OUT) || (d->flags & (VIDC_SPLIT_OUT | VIDC_MXFP8_OUT | VIDC_BF16_OUT)), VIDC_ERR_SHAPE,
+                 "conv: NO_F32_OUT without SPLIT_OUT / MXFP8_OUT / BF16_OUT writes nothing");
     VIDC_REQUIRE(!(d->flags & VIDC_STATS_OUT) || (d->precision == VIDC_PREC_BF16 && d->y_split &&
                                                   !(d->flags & (VIDC_AFFINE2 | VIDC_RESIDUAL | VIDC_ACCUM | VIDC_SPLIT_OUT | VIDC_NO_F32_OUT))),
                  VIDC_ERR_SHAPE, "conv: STATS_OUT needs VIDC_PREC_BF16, y_split = the partials buffer and a plain epilogue");
@@ -1228,6 +1271,16 @@ extern "C" int vidc_pack_conv_weight_bf16x3(const float* w_oihw, void* w_packed,
     hipLaunchKernelGGL(pack_weight_bf16x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, vidc::as_stream(stream), w_oihw,
                        reinterpret_cast<unsigned short*>(w_packed), Cout, Cin, KH, KW);
     VIDC_CHECK_LAUNCH("pack_weight_bf16x3_kernel");
+    return VIDC_OK;
+}
+
+extern "C" int vidc_pack_conv_weight_bf16(const float* w_oihw, void* w_packed, int Cout, int Cin, int KH, int KW, vidc_stream_t stream) {
+    VIDC_REQUIRE(w_oihw && w_packed, VIDC_ERR_NULL, "vidc_pack_conv_weight_bf16: null pointer");
+    VIDC_REQUIRE(Cout > 0 && Cin > 0 && Cin % 64 == 0 && KH > 0 && KW > 0, VIDC_ERR_SHAPE, "vidc_pack_conv_weight_bf16: Cin must be a multiple of 64");
+    const long long total8 = (long long)Cout * Cin * KH * KW / 8;
+    hipLaunchKernelGGL(pack_weight_bf16_kernel, dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, vidc::as_stream(stream), w_oihw,
+                       reinterpret_cast<unsigned short*>(w_packed), Cout, Cin, KH, KW);
+    VIDC_CHECK_LAUNCH("pack_weight_bf16_kernel");
     return VIDC_OK;
 }
 

@@ -75,6 +75,10 @@ int launch_op(const vidc_op& op, hipStream_t st) {
             long long rows = (long long)(uint32_t)g.i[0] | ((long long)(uint32_t)g.i[1] << 32);
             return vidc_quant_mxfp8((const float*)g.p[0], const_cast<void*>(g.p[1]), rows, g.i[2], g.i[3], g.i[4], s);
         }
+        case VIDC_OP_CAST: {   // p[0] fp32 rows -> p[1] dense bf16 rows; i[0..1] = rows (lo, hi), i[2] = C, i[3] = ldx
+            long long rows = (long long)(uint32_t)g.i[0] | ((long long)(uint32_t)g.i[1] << 32);
+            return vidc_cast_bf16((const float*)g.p[0], const_cast<void*>(g.p[1]), rows, g.i[2], g.i[3], s);
+        }
         case VIDC_OP_COPY: {   // p[0] -> p[1], i[0..1] = byte count (lo, hi)
             size_t bytes = (size_t)(uint32_t)g.i[0] | ((size_t)(uint32_t)g.i[1] << 32);
             VIDC_HIP(hipMemcpyAsync(const_cast<void*>(g.p[1]), g.p[0], bytes, hipMemcpyDeviceToDevice, st));

@@ -32,12 +32,13 @@ def _keys(k):
 
 class T:
     """Program tensor: NHWC view (channel slice) of a planned buffer; NCHW for program inputs/outputs."""
-    __slots__ = ("buf", "B", "H", "W", "C", "G", "ld", "ch_off", "nchw")
+    __slots__ = ("buf", "B", "H", "W", "C", "G", "ld", "ch_off", "nchw", "esz")
 
-    def __init__(self, buf, B, H, W, Cc, G=1, ld=None, ch_off=0, nchw=False):
+    def __init__(self, buf, B, H, W, Cc, G=1, ld=None, ch_off=0, nchw=False, esz=4):
         self.buf, self.B, self.H, self.W, self.C, self.G = buf, B, H, W, Cc, G
         self.ld = ld if ld is not None else G * Cc
         self.ch_off, self.nchw = ch_off, nchw
+        self.esz = esz           # bytes per channel: 4, or 2 for a plain-bf16 image (Program.cast), whose ld / ch_off count bf16 channels
 
     @property
     def numel(self):
@@ -76,17 +77,17 @@ class WeightStore:
 
     def packed(self, keys, dry_run=False, precision=0):
         """[G][Cout][KH][KW][Cin] fp32 (precision 0) or the split-bf16 image of the same bytes (precision 1), packed by
-        the C kernels; precision 3: [G][Cout * K * 33 / 32 bytes], the MXFP8 images (include/vidc.h) in float32-typed storage."""
+        the C kernels; precision 2: [G][Cout * K bf16 values], the plain-bf16 rows (64 channels per K unit) in float32-typed storage; precision 3: [G][Cout * K * 33 / 32 bytes], the MXFP8 images (include/vidc.h) in float32-typed storage."""
         ck = ("w", precision) + tuple(keys)
         if ck not in self._cache:
             ws = [self.sd()[k + ".weight"].contiguous() for k in keys]
             co, ci, kh, kw = ws[0].shape
-            per_group = kh * kw * ci if precision != L.PREC_MXFP8 else kh * kw * ci // 128 * 33
+            per_group = {L.PREC_MXFP8: kh * kw * ci // 128 * 33, L.PREC_BF16: kh * kw * ci // 2}.get(precision, kh * kw * ci)
             out = torch.empty((len(ws), co, per_group), dtype=torch.float32, device=ws[0].device)
             for g, w in enumerate(ws):
                 assert tuple(w.shape) == (co, ci, kh, kw)
                 if not dry_run:
-                    fn = {L.PREC_BF16X3: L.lib().vidc_pack_conv_weight_bf16x3,
+                    fn = {L.PREC_BF16X3: L.lib().vidc_pack_conv_weight_bf16x3, L.PREC_BF16: L.lib().vidc_pack_conv_weight_bf16,
                           L.PREC_MXFP8: L.lib().vidc_pack_conv_weight_mxfp8}.get(precision, L.lib().vidc_pack_conv_weight)
                     L.check(fn(L.ptr(w), L.ptr(out[g]), co, ci, kh, kw, L.current_stream()), "pack")
             if dry_run:
@@ -197,7 +198,10 @@ def precision_mode():
        VIDC_PRECISION=mixed : (default) compute-bound convs run split-bf16 3-pass MFMA (per-shape choice from the measured
                               table, else by size); whole-path depth RMSE vs fp32 ~1.4e-5, bar 1e-3.
        VIDC_PRECISION=mxfp8 : the direct convs that mxfp8_layer() selects run block-scaled FP8 (VIDC_PREC_MXFP8, include/vidc.h);
-                              every other layer makes exactly the choice of the mixed mode."""
+                              every other layer makes exactly the choice of the mixed mode.
+       VIDC_PRECISION=bf16  : the direct convs that bf16_layer() selects run on plain bf16 operands with fp32 accumulation (VIDC_PREC_BF16:
+                              one MFMA pass and half the operand bytes of the mixed mode's split bf16); every other layer makes exactly
+                              the choice of the mixed mode.  Opt-in."""
     return os.environ.get("VIDC_PRECISION", "mixed")
 
 
@@ -217,6 +221,17 @@ def mxfp8_layer(key, co, ci, flops):
     return ci % 128 == 0 and co % 32 == 0 and flops >= MXFP8_MIN_FLOPS and not any(e in key for e in MXFP8_EXCLUDED)
 
 
+# layers kept out of plain bf16 for accuracy (key substrings, as MXFP8_EXCLUDED): none -- every qualifying layer runs in bf16
+BF16_EXCLUDED = ()
+
+
+def bf16_layer(key, co, ci, flops):
+    """Whether the direct conv `key` runs in plain bf16 in the bf16 mode: whole 64-channel K units (128 bytes of a bf16 row), whole
+    32-channel output tiles, and not one of the layers BF16_EXCLUDED keeps out.  No size threshold: a small layer between two bf16
+    layers would otherwise cost its producer an fp32 store and itself a split launch."""
+    return ci % 64 == 0 and co % 32 == 0 and not any(e in key for e in BF16_EXCLUDED)
+
+
 def winograd_mode():
     """VIDC_WINOGRAD=auto : (default) 3x3 / stride 1 / pad 1 convs with >= 128 input channels run as Winograd F(m x m, 3x3) GEMMs
                              (csrc/winograd.hip): the entry "W:<direct signature>" of the measured table picks m in {0, 2, 4} (5 = m 4 in ONE launch, fp32 only), else (fp32 mode
@@ -225,14 +240,15 @@ def winograd_mode():
     return os.environ.get("VIDC_WINOGRAD", "auto")
 
 
-def winograd_choice(B, H, W, co, ci, kh, kw, stride, padding, dilation, G, mode=None, precision=None, mxfp8=False):
-    """mxfp8: the caller runs this layer in MXFP8 (Program.conv, mxfp8_layer): no Winograd -- the transforms amplify the quantisation
-    error, and the direct form is what the FP8 rate pays for.  Every other layer of the mxfp8 mode takes the mixed mode's choice."""
-    if mxfp8 or (kh, kw, stride, padding, dilation) != (3, 3, 1, 1, 1) or ci % 32 or co % 32:
+def winograd_choice(B, H, W, co, ci, kh, kw, stride, padding, dilation, G, mode=None, precision=None, reduced=False):
+    """reduced: the caller runs this layer in a reduced-precision operand format (Program.conv: MXFP8 by mxfp8_layer, plain bf16 by
+    bf16_layer): no Winograd -- the transforms amplify the rounding of the operands, and the direct form is what the FP8 / bf16 rate
+    pays for.  Every other layer of the mxfp8 and bf16 modes takes the mixed mode's choice."""
+    if reduced or (kh, kw, stride, padding, dilation) != (3, 3, 1, 1, 1) or ci % 32 or co % 32:
         return 0
     mode = mode if mode is not None else winograd_mode()
     precision = precision if precision is not None else precision_mode()
-    if precision == "mxfp8":
+    if precision in ("mxfp8", "bf16"):
         precision = "mixed"
     if mode in ("0", "2", "4"):
         m = int(mode)
@@ -272,7 +288,7 @@ class Program:
     """Records ops symbolically (buffers are integers), then `finalize()` plans memory and builds the C program."""
 
     def __init__(self, weights, device, batch, reuse_buffers=True, mode=None, winograd=None):
-        """mode: "fp32" | "mixed" | "mxfp8" (default: precision_mode()); winograd: "0" | "2" | "4" | "auto" (default: winograd_mode()) -- a program whose
+        """mode: "fp32" | "mixed" | "mxfp8" | "bf16" (default: precision_mode()); winograd: "0" | "2" | "4" | "auto" (default: winograd_mode()) -- a program whose
         results feed DECISIONS (the plane-mask detector: score / IoU / mask thresholds) is recorded with mode="fp32", winograd="0": exact
         fp32 direct-form sums, the arithmetic its oracle pins."""
         self.ws, self.device, self.B = weights, device, batch
@@ -290,9 +306,12 @@ class Program:
         self._keep = []
         self._split_cache = {}   # (buf, ch_off, channels) -> buffer id of the split-bf16 image
         self._quant_cache = {}   # (buf, ch_off, channels, groups) -> the MXFP8 image (T)
+        self._cast_cache = {}    # (buf, ch_off, channels) -> (buffer id of the plain-bf16 image, its channels per row)
         self.cuts = []           # op indices where a new segment starts (see cut()); filled by finalize()
         self._cut_markers = []
         self.mode = mode if mode is not None else precision_mode()
+        if self.mode not in ("fp32", "mixed", "mxfp8", "bf16"):
+            raise ValueError("unknown precision mode %r (VIDC_PRECISION: fp32, mixed, mxfp8 or bf16)" % (self.mode,))
         self.winograd = winograd
 
     # ---- buffers ----------------------------------------------------------------------------------------
@@ -329,9 +348,10 @@ class Program:
         self.stream_id, self.wait_mask = sid, wait_mask
 
     def _written(self, t):
-        """t's buffer is (re)written: its split / MXFP8 images are stale."""
+        """t's buffer is (re)written: its split / MXFP8 / bf16 images are stale."""
         self._split_cache = {k: v for k, v in self._split_cache.items() if k[0] != t.buf}
         self._quant_cache = {k: v for k, v in self._quant_cache.items() if k[0] != t.buf}
+        self._cast_cache = {k: v for k, v in self._cast_cache.items() if k[0] != t.buf}
 
     def _emit(self, kind, reads, writes, **kw):
         kw.update(stream_id=self.stream_id, wait_mask=self.wait_mask)
@@ -360,9 +380,10 @@ class Program:
             flags |= L.ACCUM
         flops = 2 * self.B * Ho * Wo * co * ci * kh * kw * G
         mx = self.mode == "mxfp8" and mxfp8_layer(keys[0], co, ci, flops)
+        bf = self.mode == "bf16" and bf16_layer(keys[0], co, ci, flops)
         wm = 0
         if residual is None and not accumulate:
-            wm = winograd_choice(self.B, x.H, x.W, co, ci, kh, kw, stride, padding, dilation, G, mode=self.winograd, precision=self.mode, mxfp8=mx)
+            wm = winograd_choice(self.B, x.H, x.W, co, ci, kh, kw, stride, padding, dilation, G, mode=self.winograd, precision=self.mode, reduced=mx or bf)
         if wm:
             self.ref_flops += int(round(flops * ref_flops_scale))
             self.direct_flops += flops
@@ -383,10 +404,12 @@ class Program:
         prec = L.PREC_FP32
         if mx:
             prec = L.PREC_MXFP8
-        elif self.mode in ("mixed", "mxfp8"):
+        elif bf:
+            prec = L.PREC_BF16
+        elif self.mode in ("mixed", "mxfp8", "bf16"):
             ent = tuning_table().get(sig)
             prec = ent[2] if (ent is not None and len(ent) > 2) else default_precision(flops)
-        xin = self.split(x) if prec == L.PREC_BF16X3 else (self.quant(x) if prec == L.PREC_MXFP8 else x)
+        xin = {L.PREC_BF16X3: self.split, L.PREC_MXFP8: self.quant, L.PREC_BF16: self.cast}.get(prec, lambda t: t)(x)
         self._emit("conv", [xin, residual, y if accumulate else None], [y], x=xin, y=y, keys=keys, precision=prec,
                    bn=_keys(bn) if bn is not None else None, bn2=_keys(bn2) if bn2 is not None else None,
                    residual=residual, flags=flags, stride=stride, pad=padding, geom=(co, ci, kh, kw, Ho, Wo), dilation=dilation, sig=sig)
@@ -403,7 +426,7 @@ class Program:
         self.flops += gflops
         sig = conv_signature(L.gemm_desc(tiles, ci, co, groups=a2 * G))
         prec = L.PREC_FP32
-        if self.mode in ("mixed", "mxfp8"):
+        if self.mode in ("mixed", "mxfp8", "bf16"):
             ent = tuning_table().get(sig)
             prec = ent[2] if (ent is not None and len(ent) > 2) else default_precision(gflops)
         V = T(self._new_buf(tiles * a2 * G * ci), 1, 1, tiles, ci, a2 * G)
@@ -454,6 +477,23 @@ class Program:
             self._emit("quant", [x], [y], x=x, y=y)
             self._quant_cache[ck] = y
         return self._quant_cache[ck]
+
+    def cast(self, x):
+        """Plain-bf16 image of an fp32 activation tensor (vidc_cast_bf16: dense rows of x.C * x.G bf16 values, group g at channel g * x.C),
+        made once per tensor: the operand of the VIDC_PREC_BF16 convs.  Its T counts bf16 channels (esz = 2)."""
+        ck = (x.buf, x.ch_off, x.C * x.G)
+        if ck not in self._cast_cache:
+            assert not x.nchw and x.esz == 4 and (x.C * x.G) % 64 == 0
+            # a channel slice of a tensor whose image exists is a slice of that image: dense bf16 rows keep every 64-channel unit (128
+            # bytes) in place, so only ch_off (a multiple of 64) moves
+            for (b0, off0, ch0), (cbuf, ld0) in self._cast_cache.items():
+                if b0 == x.buf and off0 <= x.ch_off and x.ch_off + x.C * x.G <= off0 + ch0 and (x.ch_off - off0) % 64 == 0:
+                    return T(cbuf, x.B, x.H, x.W, x.C, x.G, ld=ld0, ch_off=x.ch_off - off0, esz=2)
+            y = T(self._new_buf(self.B * x.H * x.W * x.C * x.G // 2), x.B, x.H, x.W, x.C, x.G, esz=2)
+            self._emit("cast", [x], [y], x=x, y=y)
+            self._cast_cache[ck] = (y.buf, x.C * x.G)
+        cbuf, ld0 = self._cast_cache[ck]
+        return T(cbuf, x.B, x.H, x.W, x.C, x.G, ld=ld0, esz=2)
 
     def linear(self, x, key, relu=False):
         """nn.Linear on `x.view(B, -1)` of the reference's NCHW tensor (surface_normal_dorn.py:23-24), as a 1x1 conv over the
@@ -620,7 +660,7 @@ class Program:
                 yt = self.ops[t][3]["y"]
                 ok = ok and yt.ld == xs.ld and yt.ch_off % 32 == 0 and (yt.C * yt.G) % 32 == 0 and lo <= yt.ch_off and \
                     yt.ch_off + yt.C * yt.G <= hi and self.ops[t][3].get("split_out") is None and \
-                    self.ops[t][3].get("precision") != L.PREC_MXFP8          # (an MXFP8 conv writes no split image)
+                    self.ops[t][3].get("precision") not in (L.PREC_MXFP8, L.PREC_BF16)      # (an MXFP8 / plain-bf16 conv writes no split image)
                 cover.append((yt.ch_off, yt.ch_off + yt.C * yt.G))
             cover.sort()
             ok = ok and cover[0][0] == lo and cover[-1][1] == hi and all(cover[k][1] == cover[k + 1][0] for k in range(len(cover) - 1))
@@ -682,6 +722,41 @@ class Program:
         self.n_fused_quants = len(drop)
         self.ops = [op for i, op in enumerate(self.ops) if i not in drop]
 
+    def _fuse_casts(self):
+        """A cast op whose input is the whole output of one VIDC_PREC_BF16 conv -- the last writer of the tensor before the cast -- is folded
+        into that conv (VIDC_BF16_OUT: its epilogue writes the image); when nothing else reads the fp32 result the conv does not store it
+        (VIDC_NO_F32_OUT; the output of a Bottleneck's last conv is the next block's residual and keeps its store).  Every other producer --
+        the max-pool, an upsample, the stem, a conv of another precision, producers of channel slices of a concat buffer -- is followed by
+        the stand-alone cast launch."""
+        n = len(self.ops)
+        drop = set()
+        for i, (kind, _r, _w, kw) in enumerate(self.ops):
+            if kind != "cast":
+                continue
+            xs = kw["x"]
+            j = next((t for t in range(i - 1, -1, -1) if xs.buf in self.ops[t][2]), None)
+            if j is None or self.ops[j][0] != "conv":
+                continue
+            pk = self.ops[j][3]
+            y = pk["y"]
+            if pk["precision"] != L.PREC_BF16 or pk.get("bf16_out") is not None or pk.get("wino") or y.buf != xs.buf or \
+                    (y.ch_off, y.C * y.G, y.ld) != (xs.ch_off, xs.C * xs.G, xs.ld) or y.ch_off != 0 or y.ld != y.C * y.G or \
+                    (y.B, y.H, y.W) != (xs.B, xs.H, xs.W):
+                continue
+            if any(id(self.ops[t]) in {id(mk) for mk in self._cut_markers} for t in range(j, i)):      # (a segment boundary in between: the
+                continue                                                                                 #  image must not depend on which segments ran)
+            pk["bf16_out"] = kw["y"]
+            pk["flags"] |= L.BF16_OUT
+            self.ops[j][2].append(kw["y"].buf)
+            drop.add(i)
+        for j, (kind, _r, _w, kw) in enumerate(self.ops):
+            if kind == "conv" and kw.get("bf16_out") is not None and kw["y"].buf not in self.pinned:
+                yb = kw["y"].buf
+                if not any(t not in drop and yb in self.ops[t][1] for t in range(j + 1, n)):
+                    kw["flags"] |= L.NO_F32_OUT
+        self.n_fused_casts = len(drop)
+        self.ops = [op for i, op in enumerate(self.ops) if i not in drop]
+
     def _fuse_warp_into_stem(self):
         """A stem conv whose input is the output of a forward warp that nothing else reads gathers its input through the warp itself
         (vidc_stem_conv3x3s2_warped: the tap sets of warp_fwd_kernel, bit for bit) and the warp launch + the warped image go away
@@ -722,23 +797,27 @@ class Program:
             wp = self.ws.packed_winograd_fused(list(keys), dry_run) if wf else self.ws.packed(list(keys), dry_run, prec)
             s1, b1 = self.ws.affine(list(keys), list(kw["bn"]) if kw["bn"] is not None else None)
             s2, b2 = self.ws.affine([None] * len(keys), list(kw["bn2"])) if kw["bn2"] is not None else (None, None)
-            r, so, mo = kw["residual"], kw.get("split_out"), kw.get("mx_out")
+            r, so, mo, bo = kw["residual"], kw.get("split_out"), kw.get("mx_out"), kw.get("bf16_out")
             d = L.conv_desc(x.B, x.H, x.W, ci, co, kh, kwid, kw["stride"], kw["pad"], kw["dilation"], len(keys), Ho, Wo, x.ld, y.ld, prec,
                             x=addr(x), w=wp.data_ptr(), y=addr(y), scale1=s1.data_ptr(), shift1=b1.data_ptr(),
                             scale2=s2.data_ptr() if s2 is not None else None, shift2=b2.data_ptr() if b2 is not None else None,
                             relu1=f & L.RELU1, relu2=f & L.RELU2, residual=addr(r) if r is not None else None, ldr=r.ld if r is not None else None,
                             relu3=f & L.RELU3, accumulate=f & L.ACCUM, split_out=addr(so) if so is not None else None,
-                            mx_out=addr(mo) if mo is not None else None, no_f32_out=f & L.NO_F32_OUT, wino_fused=bool(wf))
+                            mx_out=addr(mo) if mo is not None else None, bf16_out=addr(bo) if bo is not None else None,
+                            no_f32_out=f & L.NO_F32_OUT, wino_fused=bool(wf))
         self._keep += [t for t in (wp, s1, b1, s2, b2) if t is not None]
         if prec == L.PREC_MXFP8:        # no measured MXFP8 entries: the planner's tiling
             L.plan(d)
+        elif prec == L.PREC_BF16:       # no measured bf16 entries either: the signature's measured tiling (the shape's best for the split-bf16
+            ent = tuning_table().get(sig)                       # or fp32 kernel) where the bf16 kernel has that tile, else the planner's
+            L.plan(d, (ent[0], ent[1]) if ent is not None and ent[0] in L.BF16_TILES else None)
         elif not wf:                    # the fused Winograd form has its own tile
             # the measured entry: [tile, splitk, precision] or [t, sk, prec, t32, sk32] with the best fp32 tiling as well; a 3-element entry
             # of the mixed mode sets the tiling of an fp32 conv of that signature too
             ent = tuning_table().get(sig)
             L.plan(d, None if ent is None else (ent[0], ent[1]) if len(ent) < 5 or prec == ent[2] else (ent[3], ent[4]))
         form = "@wino4f" if wf else ("@wino%d" % wm if wm else "")
-        pname = {L.PREC_FP32: "fp32", L.PREC_BF16X3: "bf16x3", L.PREC_MXFP8: "mxfp8"}[prec]
+        pname = {L.PREC_FP32: "fp32", L.PREC_BF16X3: "bf16x3", L.PREC_BF16: "bf16", L.PREC_MXFP8: "mxfp8"}[prec]
         return d, "conv:%s%s:%s:sk%d:%s %s flags=0x%x" % (keys[0], form, L.TILE_NAMES[d.tile], d.splitk, pname, sig, d.flags)
 
     def _plan_buffers(self):
@@ -791,6 +870,7 @@ class Program:
         if os.environ.get("VIDC_FUSE_SPLIT", "1") == "1":
             self._fuse_splits()
             self._fuse_quants()
+            self._fuse_casts()
         self.cuts = [next(i for i, op in enumerate(self.ops) if op is mk) + 1 for mk in self._cut_markers]
         assert len(self.cuts) < L.MAX_SEGMENTS and self.cuts == sorted(set(self.cuts))
         storage = self._plan_buffers()
@@ -798,7 +878,7 @@ class Program:
         self.bytes_allocated = sum({t.data_ptr(): t.numel() * 4 for t in storage if t is not None}.values())
 
         def addr(t, extra=0):
-            return storage[t.buf].data_ptr() + 4 * (t.ch_off + extra)
+            return storage[t.buf].data_ptr() + t.esz * (t.ch_off + extra)
 
         ops = (L.Op * sum(1 for _ in self.ops))()
         ws_need = {}
@@ -896,6 +976,13 @@ class Program:
                 g.p[0], g.p[1] = addr(x), addr(y)
                 g.i[0], g.i[1], g.i[2], g.i[3], g.i[4] = rows & 0xFFFFFFFF, rows >> 32, x.C, x.ld, x.G
                 self.op_names.append("quant:%dx%dx%d" % (rows, x.C, x.G))
+            elif kind == "cast":
+                x, y = kw["x"], kw["y"]
+                rows = x.B * x.H * x.W
+                op.kind = L.OP_CAST
+                g.p[0], g.p[1] = addr(x), addr(y)
+                g.i[0], g.i[1], g.i[2], g.i[3] = rows & 0xFFFFFFFF, rows >> 32, x.C * x.G, x.ld
+                self.op_names.append("cast:%dx%d" % (rows, x.C * x.G))
             elif kind == "avgpool":
                 x, y = kw["x"], kw["y"]
                 op.kind = L.OP_AVGPOOL
@@ -1040,7 +1127,7 @@ class Program:
                 continue
             grouped = (kind in ("conv", "wino_out") and len(kw["keys"]) == groups) or (kind in ("maxpool", "wino_in") and kw["x"].G == groups)
             # (a split launch of its own -- VIDC_FUSE_SPLIT=0 -- over a grouped tensor has no row stride for its image: it runs whole in every variant)
-            if grouped or keep_ungrouped or (kind in ("split", "quant") and kw["x"].G == groups):
+            if grouped or keep_ungrouped or (kind in ("split", "quant", "cast") and kw["x"].G == groups):
                 picked.append(i)
         ops = (L.Op * len(picked))()
         for j, i in enumerate(picked):
@@ -1054,8 +1141,9 @@ class Program:
                     v = getattr(d, field)                                                              # (a split-bf16 unit = 32 x (hi, lo))
                     if field == "y_split" and d.flags & L.MXFP8_OUT:                                  # (MXFP8 image: one plane pair per group)
                         gs = d.B * d.Ho * d.Wo * d.Cout * 33 // 128
+                    esz = 2 if field == "y_split" and d.flags & L.BF16_OUT else 4                     # (bf16 image: two bytes per channel)
                     if v:
-                        setattr(d, field, v + 4 * g_lo * gs * a2)
+                        setattr(d, field, v + esz * g_lo * gs * a2)
                 d.groups = (g_hi - g_lo) * a2
             elif kind == "wino_in" and kw["x"].G == groups:        # x: group at channel g * cin; V rows: [gg][pos][cin] (row stride explicit)
                 g = ops[j].u.g

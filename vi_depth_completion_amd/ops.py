@@ -47,6 +47,26 @@ def split_bf16x3(x_nhwc):
     return out
 
 
+def pack_conv_weight_bf16(w_oihw):
+    """OIHW fp32 -> plain-bf16 packed weights for VIDC_PREC_BF16: bfloat16 (Cout, K), K order [Cin/64][KH][KW][64]; Cin % 64 == 0."""
+    _dev(w_oihw)
+    w = w_oihw.contiguous().float()
+    co, ci, kh, kw = w.shape
+    out = torch.empty((co, kh * kw * ci), dtype=torch.bfloat16, device=w.device)
+    L.check(L.lib().vidc_pack_conv_weight_bf16(L.ptr(w), L.ptr(out), co, ci, kh, kw, L.current_stream()), "pack_conv_weight_bf16")
+    return out
+
+
+def cast_bf16(x_nhwc):
+    """fp32 NHWC -> the plain-bf16 image of the same shape (round to nearest even): the operand of a VIDC_PREC_BF16 conv; channels % 8 == 0."""
+    _dev(x_nhwc)
+    x = x_nhwc.contiguous().float()
+    Cc = x.shape[-1]
+    out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    L.check(L.lib().vidc_cast_bf16(L.ptr(x), L.ptr(out), x.numel() // Cc, Cc, Cc, L.current_stream()), "cast_bf16")
+    return out
+
+
 def pack_conv_weight_mxfp8(w_oihw):
     """OIHW fp32 -> MXFP8 packed weights (include/vidc.h): uint8 (Cout * K * 33 / 32,), the e4m3 rows then their scale bytes."""
     _dev(w_oihw)
@@ -70,9 +90,11 @@ def quant_mxfp8(x_nhwc, groups=1):
 
 def conv2d_bn_act(x, w_packed, scale1, shift1, kh, kw, stride=1, pad=0, relu1=False, scale2=None, shift2=None, relu2=False,
                   residual=None, relu3=False, accumulate_into=None, tile=0, splitk=1, groups=1, precision=0, split_out=None,
-                  no_f32_out=False, workspace=None, dilation=1, mx_out=None):
+                  no_f32_out=False, workspace=None, dilation=1, mx_out=None, bf16_out=None):
     """x: NHWC (B,H,W,G*Cin) contiguous; w_packed: (G,Cout,kh*kw*Cin) or (Cout,K); returns NHWC (B,Ho,Wo,G*Cout).
     precision=1 (bf16x3): x is split here; w_packed must come from pack_conv_weight_bf16x3.
+    precision=2 (plain bf16): x is cast here; w_packed: the pack_conv_weight_bf16 images of the G groups, concatenated (Cin % 64 == 0).
+    bf16_out: bfloat16 tensor of y's shape receiving the bf16 image of the result (VIDC_BF16_OUT, precision 2 only).
     precision=3 (MXFP8): x is quantised here; w_packed: the pack_conv_weight_mxfp8 images of the G groups, concatenated.
     mx_out: uint8 tensor of G * B*Ho*Wo * Cout * 33 / 32 bytes receiving the MXFP8 image of the result (VIDC_MXFP8_OUT).
     workspace: optional persistent split-K scratch (float32, zero-initialised once by the caller; include/vidc.h)."""
@@ -83,9 +105,15 @@ def conv2d_bn_act(x, w_packed, scale1, shift1, kh, kw, stride=1, pad=0, relu1=Fa
     cin = ld // G
     if precision == L.PREC_BF16X3:
         x = split_bf16x3(x)
+    elif precision == L.PREC_BF16:
+        x = cast_bf16(x)
     elif precision == L.PREC_MXFP8:
         x = quant_mxfp8(x, G)
-    if precision == L.PREC_MXFP8:
+    if precision == L.PREC_BF16:
+        wp = w_packed.contiguous()
+        cout = wp.numel() // (G * kh * kw * cin)
+        assert wp.dtype == torch.bfloat16 and wp.numel() == G * cout * kh * kw * cin
+    elif precision == L.PREC_MXFP8:
         wp = w_packed.contiguous()
         cout = wp.numel() // G // (kh * kw * cin // 32 * 33)
         assert wp.numel() == G * cout * kh * kw * cin // 32 * 33
@@ -99,10 +127,13 @@ def conv2d_bn_act(x, w_packed, scale1, shift1, kh, kw, stride=1, pad=0, relu1=Fa
     residual = residual.contiguous() if residual is not None else None
     if mx_out is not None:
         assert mx_out.dtype == torch.uint8 and mx_out.numel() >= G * B * Ho * Wo * cout // 32 * 33
+    if bf16_out is not None:
+        assert bf16_out.dtype == torch.bfloat16 and bf16_out.is_contiguous() and bf16_out.numel() >= B * Ho * Wo * G * cout
     d = L.conv_desc(B, H, W, cin, cout, kh, kw, stride, pad, dilation, G, Ho, Wo, precision=precision, x=L.ptr(x), w=L.ptr(wp), y=L.ptr(y),
                     scale1=L.ptr(s1), shift1=L.ptr(b1), shared_affine=s1.numel() < G * cout, scale2=L.ptr(s2), shift2=L.ptr(b2),
                     relu1=relu1, relu2=relu2, residual=L.ptr(residual), ldr=residual.shape[-1] if residual is not None else None, relu3=relu3,
-                    accumulate=accumulate_into is not None, split_out=L.ptr(split_out), mx_out=L.ptr(mx_out), no_f32_out=no_f32_out)
+                    accumulate=accumulate_into is not None, split_out=L.ptr(split_out), mx_out=L.ptr(mx_out), no_f32_out=no_f32_out,
+                    bf16_out=L.ptr(bf16_out))
     _launch(d, x.device, tile, splitk, workspace, "conv2d_bn_act")
     return y
 
@@ -249,6 +280,9 @@ def conv3x3_winograd(x, w_oihw_groups, scale1, shift1, m, relu1=False, scale2=No
     """nn.Conv2d(cin, cout, 3, 1, 1) [+ per-channel affines / ReLUs] of G groups as Winograd F(m x m, 3x3): input transform, ONE
     grouped 1x1 GEMM launch (a*a*G groups, identity epilogue) on the MFMA kernel, output transform with the epilogue.
     x NHWC (B,H,W,G*cin); w_oihw_groups: list of G (cout,cin,3,3) tensors; scale / shift: (G, cout)."""
+    if precision not in (L.PREC_FP32, L.PREC_BF16X3):
+        raise RuntimeError("conv3x3_winograd: precision %d has no Winograd form (fp32 = 0 and bf16x3 = 1 only; plain bf16 and MXFP8 run the direct "
+                           "conv: the transforms amplify their rounding)" % precision)
     G = len(w_oihw_groups)
     B, H, W, Cc = x.shape
     cin = Cc // G

@@ -80,9 +80,9 @@ def _(x, gravity, aligned, fx, fy, cx, cy, align_corners, normalize):
 def conv2d_bn_act(x_nhwc: torch.Tensor, w_oihw: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, stride: int, pad: int,
                   relu: bool, precision: int) -> torch.Tensor:
     """relu?(conv(x, w) * scale + shift) on NHWC activations; scale/shift = the folded bias + eval-mode BatchNorm
-    (engine.fold_bn); precision 0 = exact fp32 MFMA, 1 = bf16x3, 3 = MXFP8: the fp32 input is quantised and the weights packed
-    block-scaled, the output is fp32 (vidc_conv_precision)."""
-    pack = {1: _ops.pack_conv_weight_bf16x3, 3: _ops.pack_conv_weight_mxfp8}.get(precision, _ops.pack_conv_weight)
+    (engine.fold_bn); precision 0 = exact fp32 MFMA, 1 = bf16x3, 2 = plain bf16 (input and weights rounded to bf16, fp32 accumulation;
+    Cin % 64 == 0), 3 = MXFP8: the fp32 input is quantised and the weights packed block-scaled; the output is fp32 (vidc_conv_precision)."""
+    pack = {1: _ops.pack_conv_weight_bf16x3, 2: _ops.pack_conv_weight_bf16, 3: _ops.pack_conv_weight_mxfp8}.get(precision, _ops.pack_conv_weight)
     return _ops.conv2d_bn_act(x_nhwc, pack(w_oihw), scale, shift, w_oihw.shape[2], w_oihw.shape[3], stride=stride, pad=pad,
                               relu1=relu, precision=precision)
 
@@ -366,7 +366,7 @@ def _(dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, stride, pad, relu, precis
 
 def _conv_setup_common(ctx, what, x, w, scale, shift, y, stride, pad, relu, precision, needs, winograd=False):
     if precision not in (0, 1):
-        raise RuntimeError("torch.ops.vidc.%s: precision %d (MXFP8 is 3) has no backward; use precision 0 or 1 for inputs that require a gradient"
+        raise RuntimeError("torch.ops.vidc.%s: precision %d (plain bf16 is 2, MXFP8 is 3) has no backward; use precision 0 or 1 for inputs that require a gradient"
                            % (what, precision))
     need_x, need_w, need_affine = needs[0], needs[1], needs[2] or needs[3]
     ctx.save_for_backward(x if (need_w or need_affine) else None, w, y, scale, shift)      # (dscale re-runs the conv where a scale is 0)
