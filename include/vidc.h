@@ -189,6 +189,22 @@ enum vidc_conv_tile { VIDC_TILE_AUTO = 0, VIDC_TILE_128x128 = 1, VIDC_TILE_128x6
                          (a workgroup multiplies for 36 * Cin / 32 stages: a few hundred workgroups should cover the layer). */
                       VIDC_TILE_WINO4_FUSED = 42,
                       VIDC_TILE_COUNT = 43 };
+/* What the library knows about one tiling (its row of csrc/conv_tiles.def): tools, tests and the Python binding ask instead of keeping a
+ * copy.  bm x bn: the output tile of a workgroup of wmw x wnw x wkw compute waves; ns: stages of its LDS ring; spec: 0, 1 = as many
+ * loader waves again (_L), 2 = loader waves + pipelined fragment reads (_P); precisions: bit p set = vidc_conv_precision p has an
+ * instance; planner: vidc_conv2d_plan's cost model may choose it (the others are chosen by measured tables only). */
+enum vidc_conv_tile_kind { VIDC_TILE_KIND_AUTO = 0,        /* VIDC_TILE_AUTO: no kernel, the planner chooses                        */
+                           VIDC_TILE_KIND_MFMA = 1,        /* the implicit-GEMM conv kernel (csrc/conv_mfma.hip)                    */
+                           VIDC_TILE_KIND_STREAM = 2,      /* the streamed grouped GEMM (csrc/wgemm.hip): splitk = group chunks     */
+                           VIDC_TILE_KIND_WINOGRAD = 3 };  /* Winograd F(4x4, 3x3) in one launch (csrc/wfused.hip)                  */
+typedef struct vidc_tile_info {
+    const char* name;      /* short name in static storage, e.g. "64x64k2d4L" */
+    int32_t bm, bn, wmw, wnw, wkw, ns, spec;
+    int32_t kind;          /* vidc_conv_tile_kind */
+    int32_t precisions, planner;
+} vidc_tile_info;
+/* Fills *out for 0 <= tile < VIDC_TILE_COUNT; VIDC_ERR_SHAPE for any other id. */
+int vidc_conv_tile_info(int tile, vidc_tile_info* out);
 
 /* Arithmetic of the contraction.  FP32: v_mfma_f32_32x32x2_f32 on fp32 operands (exact fp32, the reference mode).
  * BF16X3: every operand is split as x = hi + lo (bf16 each, round-to-nearest-even) and each product is computed as
@@ -209,7 +225,8 @@ enum vidc_conv_tile { VIDC_TILE_AUTO = 0, VIDC_TILE_128x128 = 1, VIDC_TILE_128x6
  *   of 32, i.e. 128 channels; ldx a multiple of 32), x_gs = group plane bytes / 4, w_gs = Cout*KH*KW*Cin*33/32.  `x` and `w` point at data
  *   planes; the kernel finds a scale plane behind its data plane (x: B*H*W rows of 4*ldx bytes; w: Cout rows of 4*KH*KW*Cin bytes).
  *   Refused (VIDC_ERR_SHAPE): STATS_OUT, SPLIT_OUT, X_PLANAR_GROUPS, and the tilings of the measured table only (loader-wave, pipelined,
- *   streamed and Winograd tiles, and the 128x128 tile, whose registers spill): VIDC_TILE_AUTO or tiles 2 .. 13. */
+ *   streamed and Winograd tiles, and the 128x128 tile, whose registers spill): VIDC_TILE_AUTO or a tile whose vidc_tile_info
+ *   `precisions` has the MXFP8 bit. */
 enum vidc_conv_precision { VIDC_PREC_FP32 = 0, VIDC_PREC_BF16X3 = 1, VIDC_PREC_BF16 = 2, VIDC_PREC_MXFP8 = 3 };
 /* fp32 NHWC rows [rows][ldx] whose first groups * C channels are `groups` slices of C channels -> the MXFP8 image: per group g, the data
  * plane [rows][C] e4m3 bytes at y + g * rows * C * 33 / 32, followed by its scale plane [rows][C / 32] (format above).  C % 128 == 0. */

@@ -69,12 +69,49 @@ def test_conv_plan_is_sane(lib, M, N, K):
     d.B, d.Ho, d.Wo, d.Cout, d.Cin, d.KH, d.KW, d.groups = 1, 1, M, N, K, 1, 1, 1
     assert lib.vidc_conv2d_plan(C.byref(d)) == 0
     assert 1 <= d.tile < L.TILE_COUNT and d.splitk >= 1
-    import re
-    bm, bn = [int(v) for v in re.match(r"(\d+)x(\d+)", L.TILE_NAMES[d.tile]).groups()]
+    bm, bn = L.TILE_INFO[d.tile].bm, L.TILE_INFO[d.tile].bn
     wgs = -(-M // bm) * -(-N // bn) * d.splitk
     assert wgs >= min(64, (M // 32) * (N // 64))        # the planner must not leave most of the 256 CUs idle
     if d.splitk > 1:
         assert lib.vidc_conv2d_workspace_bytes(C.byref(d)) == (L.SPLITK_COUNTERS + d.splitk * M * N) * 4
+
+
+def test_tile_tables_come_from_the_library(lib):
+    """_lib's tile constants are read from vidc_conv_tile_info (csrc/conv_tiles.def); the derived lists are pinned to the ids the tuning
+    tables and the other tests were written against."""
+    assert L.TILE_COUNT == 43 and sorted(L.TILE_INFO) == list(range(43)) and L.TILE_NAMES[0] == "auto"
+    assert L.BF16_TILES == tuple(range(1, 40)) and L.MXFP8_TILES == tuple(range(2, 14))
+    assert [t for t, ti in L.TILE_INFO.items() if ti.planner] == list(range(1, 14))
+    assert [t for t, ti in L.TILE_INFO.items() if ti.kind == L.TILE_KIND_MFMA] == list(range(1, 40))
+    assert [t for t, ti in L.TILE_INFO.items() if ti.kind == L.TILE_KIND_STREAM] == [40, 41] and L.TILE_WINO4_FUSED == 42
+    assert (L.TILE_NAMES[18], L.TILE_NAMES[40], L.TILE_NAMES[42]) == ("64x64k2d4L", "g96x32s", "wino4f")
+    ti = L.TILE_INFO[18]
+    assert (ti.bm, ti.bn, ti.wmw, ti.wnw, ti.wkw, ti.ns, ti.spec) == (64, 64, 2, 2, 2, 4, 1)
+    assert lib.vidc_conv_tile_info(43, C.byref(L.TileInfo())) == -2 and lib.vidc_conv_tile_info(-1, C.byref(L.TileInfo())) == -2
+    assert lib.vidc_conv_tile_info(0, None) == -1
+
+
+def test_planner_choices_are_the_recorded_ones(lib):
+    """vidc_conv2d_plan on every signature of conv_tuning.json and train_tuning.json ("W:" entries by their direct signature), in fp32,
+    bf16x3 and bf16, and in MXFP8 where Cin is whole 128-channel units: the (tile, splitk) recorded in tests/golden/conv_plan.json before
+    the planner's candidate loop was generated from the tile table."""
+    import json
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "conv_plan.json")))
+    sigs = set()
+    for name in ("conv_tuning.json", "train_tuning.json"):
+        sigs |= {k[2:] if k.startswith("W:") else k for k in json.load(open(os.path.join(ROOT, "vi_depth_completion_amd", name)))}
+    assert sigs == set(want)
+    wrong = []
+    for sig in sorted(sigs):
+        M, N, K, k, s, G = [int(v) for v in re.fullmatch(r"M(\d+)_N(\d+)_K(\d+)_k(\d+)s(\d+)_G(\d+)", sig).groups()]
+        cin = K // (k * k)
+        precs = (0, 1, 2) + ((3,) if cin % 128 == 0 else ())
+        assert len(want[sig]) == 2 * len(precs)
+        for i, prec in enumerate(precs):
+            d = L.plan(L.conv_desc(1, 1, M, cin, N, k, k, s, k // 2, groups=G, Ho=1, Wo=M, precision=prec))
+            if [d.tile, d.splitk] != want[sig][2 * i:2 * i + 2]:
+                wrong.append((sig, prec, d.tile, d.splitk, want[sig][2 * i:2 * i + 2]))
+    assert not wrong, wrong[:10]
 
 
 def test_rng_draws_follow_reference_order():

@@ -24,11 +24,11 @@ from vi_depth_completion_amd.networks.depth_completion import ModifiedFPN   # no
 from vi_depth_completion_amd.networks.surface_normal import SurfaceNormalPrediction   # noqa: E402
 
 OUT = os.path.join(ROOT, "vi_depth_completion_amd", "conv_tuning.json")
-TILE_DIMS = {1: (128, 128), 2: (128, 64), 3: (64, 128), 4: (64, 64), 5: (64, 64), 6: (32, 64), 7: (32, 32), 8: (32, 128), 9: (32, 32),
-             10: (32, 64), 11: (32, 32), 12: (32, 128), 13: (64, 64), 14: (32, 64), 15: (32, 64), 16: (32, 32), 17: (64, 64), 18: (64, 64),
-             19: (64, 128), 20: (128, 64), 21: (64, 32), 22: (64, 32), 23: (64, 32), 24: (128, 128), 25: (128, 128), 26: (256, 128), 27: (128, 256),
-             28: (32, 64), 29: (64, 64), 30: (32, 32), 31: (64, 128), 32: (64, 32), 33: (128, 128), 34: (128, 128), 35: (64, 64), 36: (128, 64),
-             37: (64, 64), 38: (64, 32), 39: (32, 64)}
+
+
+def tile_dims():
+    """id -> (BM, BN) of the tilings of the MFMA conv kernel (the candidates of a sweep)."""
+    return {t: (ti.bm, ti.bn) for t, ti in L.TILE_INFO.items() if ti.kind == L.TILE_KIND_MFMA}
 
 
 _POOL = {}
@@ -169,7 +169,7 @@ def main():
                     for prec in ((0,) if a.fp32_only else (0, 1)):
                         d.precision = prec
                         cands = []
-                        for t, (bm, bn) in TILE_DIMS.items():
+                        for t, (bm, bn) in tile_dims().items():
                             if bn > max(64, d.Cout) or bm >= 4 * max(32, M):
                                 continue
                             for sk in [int(v) for v in a.splitk.split(",")]:

@@ -59,7 +59,7 @@ def main():
         M = int(sig.split("_")[0][1:])
         K = int(sig.split("_")[2][1:])
         for t in range(1, L.TILE_COUNT):
-            bm = int(L.TILE_NAMES[t].split("x")[0])
+            bm = L.TILE_INFO[t].bm
             if bm >= 4 * max(32, M):
                 continue
             for sk in (1, 2, 3, 4, 6, 8):

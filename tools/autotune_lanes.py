@@ -105,7 +105,7 @@ def main():
         sks = sorted({1, max(1, cur[1] - 1), cur[1], cur[1] + 1, 2 * cur[1]})
         only = [int(v) for v in a.tiles.split(",") if v]
         for t in (only if only else range(1, L.TILE_COUNT)):
-            bm = int(L.TILE_NAMES[t].split("x")[0])
+            bm = L.TILE_INFO[t].bm
             if bm >= 4 * max(32, M) or (a.max_bm and bm > a.max_bm):
                 continue
             for sk in sks:

@@ -21,7 +21,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from autotune import TILE_DIMS  # noqa: E402
+from autotune import tile_dims  # noqa: E402
 from vi_depth_completion_amd import _lib as L, engine, synthetic as S, training  # noqa: E402
 from vi_depth_completion_amd.networks.depth_completion import ModifiedFPN  # noqa: E402
 
@@ -117,7 +117,7 @@ def main():
                 p.splitk = 1
             us_plan = time_launches(lib, p, st, None if big_w else pool, junk, 6 if big_w else 16)
             cands = []
-            for t, (bm, bn) in TILE_DIMS.items():
+            for t, (bm, bn) in tile_dims().items():
                 if bn > max(64, d.Cout) or bm >= 4 * max(32, M):
                     continue
                 wgs = -(-M // bm) * -(-d.Cout // bn) * d.groups
@@ -159,7 +159,7 @@ def main():
             p.splitk = 1
         us_plan = time_launches(lib, p, st, None if big_w else pool, junk, 6 if big_w else 16)
         cands = []
-        for t, (bm, bn) in TILE_DIMS.items():
+        for t, (bm, bn) in tile_dims().items():
             if bn > max(64, d.Cout) or bm >= 4 * max(32, M):
                 continue
             wgs = -(-M // bm) * -(-d.Cout // bn) * d.groups

@@ -38,19 +38,20 @@ def main():
         flop = 2.0 * M * N * K * G
         res = []
         for t in tiles:
-            for ch in ([int(c) for c in a.chunks.split(",")] if t >= 40 else [1, 2]):
+            streamed = L.TILE_INFO[t].kind == L.TILE_KIND_STREAM      # splitk = number of group chunks
+            for ch in ([int(c) for c in a.chunks.split(",")] if streamed else [1, 2]):
                 d = L.ConvDesc()
                 d.x, d.y, d.scale1, d.shift1 = L.ptr(x), L.ptr(y), L.ptr(one), L.ptr(zero)
                 d.B, d.H, d.W, d.Cin, d.ldx, d.Ho, d.Wo, d.Cout, d.ldy = 1, 1, M, K, G * K, 1, M, N, G * N
                 d.KH, d.KW, d.stride, d.pad, d.groups, d.flags = 1, 1, 1, 0, G, 0
                 d.x_gs, d.w_gs, d.y_gs, d.p_gs = K, N * K, N, 0
-                d.tile, d.splitk, d.precision = t, max(ch, 1) if t >= 40 else ch, 0
+                d.tile, d.splitk, d.precision = t, max(ch, 1) if streamed else ch, 0
                 wsb = None
                 need = lib.vidc_conv2d_workspace_bytes(C.byref(d))
                 if need:
                     wsb = torch.zeros(need // 4, device=DEV)
                     d.workspace = L.ptr(wsb)
-                if t >= 40:
+                if streamed:
                     d.splitk = ch
 
                 def go(i):
@@ -66,7 +67,7 @@ def main():
                 e1.record()
                 torch.cuda.synchronize()
                 us = e0.elapsed_time(e1) * 1e3 / a.iters
-                res.append((us, "%s%s" % (L.TILE_NAMES[t], (":c%d" % ch) if t >= 40 else (":sk%d" % ch))))
+                res.append((us, "%s%s" % (L.TILE_NAMES[t], (":c%d" % ch) if streamed else (":sk%d" % ch))))
         res.sort()
         print("M%d_N%d_K%d_G%d  %-28s %6.2f GFLOP  weights %5.1f MB | " % (M, N, K, G, label, flop / 1e9, wbytes / 1e6) +
               "  ".join("%s %.1f us (%.0f TF)" % (n, us, flop / us / 1e6) for us, n in res[:7]), flush=True)

@@ -23,16 +23,8 @@ RELU1, AFFINE2, RELU2, RESIDUAL, RELU3, ACCUM, SPLIT_OUT, NO_F32_OUT, STATS_OUT,
 UP_RELU, UP_ACCUM, UP_NO_F32_OUT = 1, 2, 4
 OP_CONV, OP_STEM, OP_MAXPOOL, OP_UPSAMPLE, OP_HEAD, OP_WARP_PARAMS, OP_WARP_FWD, OP_WARP_INV, OP_COPY, OP_SPLIT, OP_AVGPOOL, OP_NORMALIZE, OP_DET_IM2COL, OP_NEAREST2X, _OP_RETIRED_15, OP_MASK, OP_WINO_IN, OP_WINO_OUT, OP_QUANT, OP_CAST = range(1, 21)
 TILE_AUTO = 0
-TILE_NAMES = {0: "auto", 1: "128x128", 2: "128x64", 3: "64x128", 4: "64x64", 5: "64x64k2", 6: "32x64k2", 7: "32x32k4", 8: "32x128",
-              9: "32x32k8", 10: "32x64k2d5", 11: "32x32k4d4", 12: "32x128d6", 13: "64x64k2d4", 14: "32x64k2L", 15: "32x64k2d5L", 16: "32x32k4d4L", 17: "64x64L", 18: "64x64k2d4L",
-              19: "64x128L", 20: "128x64L", 21: "64x32k2", 22: "64x32k2d5", 23: "64x32k2d5L", 24: "128x128d3", 25: "128x128d3L", 26: "256x128", 27: "128x256",
-              28: "32x64k2d2", 29: "64x64d2", 30: "32x32k4d2", 31: "64x128d2", 32: "64x32k2d2",
-              33: "128x128d4P", 34: "128x128d3P", 35: "64x64d4P", 36: "128x64d4P", 37: "64x64k2d4P", 38: "64x32k2d5P", 39: "32x64k2d5P", 40: "g96x32s", 41: "g96x64s3", 42: "wino4f"}
-TILE_COUNT = 43
-TILE_WINO4_FUSED = 42
 PREC_FP32, PREC_BF16X3, PREC_BF16, PREC_MXFP8 = 0, 1, 2, 3
-MXFP8_TILES = range(2, 14)         # the tilings with an MXFP8 instance (include/vidc.h)
-BF16_TILES = range(1, 40)          # the tilings of the MFMA conv kernel: every one has a plain-bf16 instance (40 .. 42: the fp32-only streamed / Winograd tiles)
+TILE_KIND_AUTO, TILE_KIND_MFMA, TILE_KIND_STREAM, TILE_KIND_WINOGRAD = range(4)      # vidc_conv_tile_kind
 SPLITK_COUNTERS = 16384            # VIDC_SPLITK_COUNTERS: ticket counters at the head of a split-K workspace
 
 _f32p = C.POINTER(C.c_float)
@@ -42,6 +34,12 @@ class PackItem(C.Structure):
     """vidc_pack_item (include/vidc.h)."""
     _fields_ = [("w", C.c_void_p), ("packed", C.c_void_p), ("Cout", C.c_int32), ("Cin", C.c_int32), ("KH", C.c_int32), ("KW", C.c_int32),
                 ("kind", C.c_int32), ("reserved", C.c_int32), ("block_begin", C.c_int64)]
+
+
+class TileInfo(C.Structure):
+    """vidc_tile_info (include/vidc.h): one row of csrc/conv_tiles.def."""
+    _fields_ = [("_name", C.c_char_p)] + [(f, C.c_int32) for f in ("bm", "bn", "wmw", "wnw", "wkw", "ns", "spec", "kind", "precisions", "planner")]
+    name = property(lambda self: self._name.decode())
 
 
 class ConvDesc(C.Structure):
@@ -100,7 +98,7 @@ def conv_desc(B, H, W, Cin, Cout, KH=1, KW=1, stride=1, pad=0, dilation=1, group
                     KH=KH, KW=KW, stride=stride, pad=pad, flags=flags, groups=groups,
                     x_gs=x_gs, w_gs=w_gs, y_gs=Cout, r_gs=(0 if residual is None else Cout),
                     p_gs=(0 if shared_affine and groups > 1 else Cout),      # (with one group p_gs is never read)
-                    tile=(TILE_WINO4_FUSED if wino_fused else TILE_AUTO), splitk=1, precision=precision, dilation=dil,
+                    tile=(__getattr__("TILE_WINO4_FUSED") if wino_fused else TILE_AUTO), splitk=1, precision=precision, dilation=dil,
                     y_split=next((p for p in (split_out, mx_out, stats_out, bf16_out) if p is not None), None))
 
 
@@ -162,6 +160,7 @@ SIGNATURES = {
     "vidc_conv2d_bn_act": (C.c_int, [C.POINTER(ConvDesc), _vp]),
     "vidc_conv2d_workspace_bytes": (C.c_size_t, [C.POINTER(ConvDesc)]),
     "vidc_conv2d_plan": (C.c_int, [C.POINTER(ConvDesc)]),
+    "vidc_conv_tile_info": (C.c_int, [_i, C.POINTER(TileInfo)]),
     "vidc_train_scratch_bytes": (C.c_size_t, [C.c_longlong, _i]),
     "vidc_bn_train_forward": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "vidc_bn_train_forward_add": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
@@ -265,7 +264,7 @@ _lib = None
 
 def build(force=False, verbose=False):
     """Compile libvidc.so in-tree: hipcc --offload-arch=gfx950 (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".map")) or f == "Makefile"]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".def", ".map")) or f == "Makefile"]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "vidc.h"))
     if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -293,6 +292,24 @@ def lib():
             raise RuntimeError("libvidc.so ABI version mismatch")
         _lib = L
     return _lib
+
+
+_TILE_TABLES = ("TILE_INFO", "TILE_COUNT", "TILE_NAMES", "MXFP8_TILES", "BF16_TILES", "TILE_WINO4_FUSED")
+
+
+def __getattr__(name):
+    """The tile tables: id -> vidc_tile_info, id -> name, the number of ids, the ids with an MXFP8 / a plain-bf16 instance, the fused Winograd
+    tile.  Read from the library's own table (csrc/conv_tiles.def) on first use, then module attributes: no copy is written down here."""
+    if name not in _TILE_TABLES:
+        raise AttributeError("module %r has no attribute %r" % (__name__, name))
+    info, ti = {}, TileInfo()
+    while lib().vidc_conv_tile_info(len(info), C.byref(ti)) == 0:      # (fails past the last id)
+        info[len(info)], ti = ti, TileInfo()
+    globals().update(TILE_INFO=info, TILE_COUNT=len(info), TILE_NAMES={t: ti.name for t, ti in info.items()},
+                     MXFP8_TILES=tuple(t for t, ti in info.items() if ti.precisions >> PREC_MXFP8 & 1),
+                     BF16_TILES=tuple(t for t, ti in info.items() if ti.precisions >> PREC_BF16 & 1),
+                     TILE_WINO4_FUSED=next(t for t, ti in info.items() if ti.kind == TILE_KIND_WINOGRAD))
+    return globals()[name]
 
 
 def check(rc, what=""):

@@ -23,6 +23,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 32;       // K-step (floats)
 
+// Floats of one slot of a tiling's LDS ring: the operand rows of its WKW k-slices, then (MXFP8) per k-slice 64 * WPK A and B scale dwords.
+constexpr int ring_slot_floats(int BM, int BN, int WPK, int WKW, bool MX) { return (BM + BN) * BK * WKW + (MX ? 2 * 64 * WPK * WKW : 0); }
+// Threads of its workgroup: the compute waves, and with SPEC as many loader waves again.
+constexpr int tile_threads(int WMW, int WNW, int WKW, int SPEC) { return 64 * WMW * WNW * WKW * (SPEC ? 2 : 1); }
+
 struct ConvArgs {
     const float* x; const float* w; float* y;
     const float* scale1; const float* shift1; const float* scale2; const float* shift2;
@@ -189,8 +194,8 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
     constexpr int A_J = (BM / 8) / WPK, B_J = (BN / 8) / WPK;      // operand-row DMA instructions per wave per stage
     constexpr int A_JW = A_J + SJ;                                 // ... and all DMA instructions of an A group
     constexpr int LPS = A_J + B_J + 2 * SJ;
-    constexpr int SOFF = (BM + BN) * BK * WKW;                     // operand rows of a ring slot, then (MXFP8) per k-slice 64 * WPK A and B scale dwords
-    constexpr int STAGE = SOFF + (MX ? 2 * 64 * WPK * WKW : 0);    // floats per ring slot
+    constexpr int SOFF = ring_slot_floats(BM, BN, WPK, WKW, false);      // operand rows of a ring slot; the MXFP8 scale dwords start behind them
+    constexpr int STAGE = ring_slot_floats(BM, BN, WPK, WKW, MX);
     static_assert((BM / 8) % WPK == 0 && (BN / 8) % WPK == 0, "tile rows must split evenly over the waves");
     static_assert(!MX || (BM <= 64 * WPK && BN <= 64 * WPK), "MXFP8: one scale DMA per wave covers the tile's rows");
     static_assert(NS >= 2 && (NS - 2) * LPS <= 63, "vmcnt is a 6-bit counter");
@@ -891,7 +896,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int g, const 
 }
 
 template <int BM, int BN, int WMW, int WNW, int WKW, int NS, int PREC, int SPEC>
-__global__ void __launch_bounds__(64 * WMW * WNW * WKW * (SPEC ? 2 : 1))
+__global__ void __launch_bounds__(tile_threads(WMW, WNW, WKW, SPEC))
 // (Round 4 tried a register budget of 168 for the 2-deep-ring small tiles -- amdgpu_waves_per_eu(3): 172 -> 132 VGPRs, no spills, three
 //  workgroups per CU instead of two, so that the 640 workgroups of a layer-3 launch at M = 640 need no second round.  In the frame:
 //  per-op times unchanged within 2 % (layer-3 trio 1687 -> 1715 us per tick in fp32), fp32 stream 362 vs 364 frames/s: the work per CU
@@ -989,64 +994,33 @@ __global__ void __launch_bounds__(256) pack_weight_bf16_kernel(const float* __re
     *reinterpret_cast<uint4*>(wp + idx * 8) = v;
 }
 
-struct TileInfo { int bm, bn, wmw, wnw, wkw, ns; };   // tiles >= kFirstLoaderTile run with loader waves
-constexpr TileInfo kTiles[VIDC_TILE_COUNT] = {
-    {0, 0, 0, 0, 0, 0},
-    {128, 128, 2, 2, 1, 2},   // VIDC_TILE_128x128
-    {128, 64, 2, 2, 1, 3},    // VIDC_TILE_128x64
-    {64, 128, 2, 2, 1, 3},    // VIDC_TILE_64x128
-    {64, 64, 2, 2, 1, 4},     // VIDC_TILE_64x64
-    {64, 64, 2, 2, 2, 3},     // VIDC_TILE_64x64_K2   (8 waves)
-    {32, 64, 1, 2, 2, 3},     // VIDC_TILE_32x64_K2
-    {32, 32, 1, 1, 4, 3},     // VIDC_TILE_32x32_K4
-    {32, 128, 1, 4, 1, 4},    // VIDC_TILE_32x128
-    {32, 32, 1, 1, 8, 2},     // VIDC_TILE_32x32_K8   (8 waves)
-    {32, 64, 1, 2, 2, 5},     // VIDC_TILE_32x64_K2_D5  deeper rings for the DMA-latency-bound small layers
-    {32, 32, 1, 1, 4, 4},     // VIDC_TILE_32x32_K4_D4
-    {32, 128, 1, 4, 1, 6},    // VIDC_TILE_32x128_D6
-    {64, 64, 2, 2, 2, 4},     // VIDC_TILE_64x64_K2_D4
-    // ---- with loader waves (SPEC = 1): same tiles, DMA issued by NW extra waves ----
-    {32, 64, 1, 2, 2, 3},     // VIDC_TILE_32x64_K2_L
-    {32, 64, 1, 2, 2, 5},     // VIDC_TILE_32x64_K2_D5_L
-    {32, 32, 1, 1, 4, 4},     // VIDC_TILE_32x32_K4_D4_L
-    {64, 64, 2, 2, 1, 4},     // VIDC_TILE_64x64_L
-    {64, 64, 2, 2, 2, 4},     // VIDC_TILE_64x64_K2_D4_L   (16 waves)
-    {64, 128, 2, 2, 1, 3},    // VIDC_TILE_64x128_L
-    {128, 64, 2, 2, 1, 3},    // VIDC_TILE_128x64_L
-    // ---- more, narrower weight tiles in flight for the M = 320 layers (HBM-cold weights stream at ~25 B/clk per distinct tile) ----
-    {64, 32, 2, 1, 2, 3},     // VIDC_TILE_64x32_K2
-    {64, 32, 2, 1, 2, 5},     // VIDC_TILE_64x32_K2_D5
-    {64, 32, 2, 1, 2, 5},     // VIDC_TILE_64x32_K2_D5_L
-    // ---- 64x64 wave tiles: 0.67 KB of LDS fragment reads per MFMA instead of 1 KB ----
-    {128, 128, 2, 2, 1, 3},   // VIDC_TILE_128x128_D3
-    {128, 128, 2, 2, 1, 3},   // VIDC_TILE_128x128_D3_L
-    {256, 128, 4, 2, 1, 3},   // VIDC_TILE_256x128   (8 waves, 144 KB of LDS)
-    {128, 256, 2, 4, 1, 3},   // VIDC_TILE_128x256
-    // ---- 2-deep rings: 32-48 KB of LDS, so that >= 3 workgroups (of one or of several streams' launches) share a CU ----
-    {32, 64, 1, 2, 2, 2},     // VIDC_TILE_32x64_K2_D2   48 KB
-    {64, 64, 2, 2, 1, 2},     // VIDC_TILE_64x64_D2      32 KB
-    {32, 32, 1, 1, 4, 2},     // VIDC_TILE_32x32_K4_D2   64 KB
-    {64, 128, 2, 2, 1, 2},    // VIDC_TILE_64x128_D2     48 KB
-    {64, 32, 2, 1, 2, 2},     // VIDC_TILE_64x32_K2_D2   48 KB
-    // ---- loader waves + pipelined fragment reads (SPEC = 2): every ds_read in the shadow of an MFMA, across the stage barrier ----
-    {128, 128, 2, 2, 1, 4},   // VIDC_TILE_128x128_D4_P  128 KB
-    {128, 128, 2, 2, 1, 3},   // VIDC_TILE_128x128_D3_P   96 KB
-    {64, 64, 2, 2, 1, 4},     // VIDC_TILE_64x64_D4_P     64 KB (32x32 wave tiles)
-    {128, 64, 2, 2, 1, 4},    // VIDC_TILE_128x64_D4_P    96 KB (64x32 wave tiles)
-    {64, 64, 2, 2, 2, 4},     // VIDC_TILE_64x64_K2_D4_P 128 KB (16 waves)
-    {64, 32, 2, 1, 2, 5},     // VIDC_TILE_64x32_K2_D5_P 120 KB
-    {32, 64, 1, 2, 2, 5},     // VIDC_TILE_32x64_K2_D5_P 120 KB
-    // ---- csrc/wgemm.hip: one workgroup streams a chunk of groups of a few-row grouped GEMM through one continuous ring ----
-    {96, 32, 3, 1, 2, 2},     // VIDC_TILE_G96x32_STREAM  77 KB
-    {96, 64, 3, 2, 2, 3},     // VIDC_TILE_G96x64_STREAM3 145 KB
-    {16, 32, 1, 2, 1, 2},     // VIDC_TILE_WINO4_FUSED    144 KB (16 tiles x 32 channels x all 36 positions: csrc/wfused.hip)
+// ---- the tilings: csrc/conv_tiles.def, one row per id ---------------------------------------------------------------------------
+enum : int { F32 = 1 << VIDC_PREC_FP32, X3 = 1 << VIDC_PREC_BF16X3, B16 = 1 << VIDC_PREC_BF16, MX8 = 1 << VIDC_PREC_MXFP8 };      // a row's `precisions`
+#define VIDC_CONV_TILE(id, name, BM, BN, WMW, WNW, WKW, NS, SPEC, KIND, PRECS, PLANNER) {name, BM, BN, WMW, WNW, WKW, NS, SPEC, VIDC_TILE_KIND_##KIND, PRECS, PLANNER},
+constexpr vidc_tile_info kTiles[] = {
+#include "conv_tiles.def"
 };
-constexpr int kFirstLoaderTile = VIDC_TILE_32x64_K2_L;
+#undef VIDC_CONV_TILE
+#define VIDC_CONV_TILE(id, ...) id,
+constexpr int kTileIds[] = {
+#include "conv_tiles.def"
+};
+#undef VIDC_CONV_TILE
+constexpr bool tile_rows_in_id_order() {
+    for (int t = 0; t < VIDC_TILE_COUNT; ++t)
+        if (kTileIds[t] != t) return false;
+    return true;
+}
+static_assert(sizeof(kTileIds) / sizeof(kTileIds[0]) == VIDC_TILE_COUNT, "conv_tiles.def: one row per id of enum vidc_conv_tile");
+static_assert(tile_rows_in_id_order(), "conv_tiles.def: a row's constant must equal its position");
+
+// (any id, also one validate() has not seen: vidc_conv2d_workspace_bytes)
+inline bool is_streamed(int tile) { return tile >= 0 && tile < VIDC_TILE_COUNT && kTiles[tile].kind == VIDC_TILE_KIND_STREAM; }
 
 template <int BM, int BN, int WMW, int WNW, int WKW, int NS, int PREC, int SPEC>
 int launch_tile_p(const ConvArgs& a, hipStream_t st) {
-    constexpr int NT = 64 * WMW * WNW * WKW * (SPEC ? 2 : 1);
-    constexpr size_t lds = (size_t)NS * ((BM + BN) * BK * WKW + (PREC == 3 ? 2 * 64 * WMW * WNW * WKW : 0)) * sizeof(float);
+    constexpr int NT = tile_threads(WMW, WNW, WKW, SPEC);
+    constexpr size_t lds = (size_t)NS * ring_slot_floats(BM, BN, WMW * WNW, WKW, PREC == 3) * sizeof(float);
     static bool attr_set[64] = {};   // per device (the attribute is per device function); benign race: idempotent
     int dev = 0;
     VIDC_HIP(hipGetDevice(&dev));
@@ -1061,16 +1035,23 @@ int launch_tile_p(const ConvArgs& a, hipStream_t st) {
     return VIDC_OK;
 }
 
-// MX: the tiling has an MXFP8 instance (validate() refuses precision 3 for the others)
-template <int BM, int BN, int WMW, int WNW, int WKW, int NS, int SPEC = 0, bool MX = false>
-int launch_tile(const ConvArgs& a, hipStream_t st, int precision) {
-    if constexpr (MX) {
-        if (precision == VIDC_PREC_MXFP8) return launch_tile_p<BM, BN, WMW, WNW, WKW, NS, 3, SPEC>(a, st);
+// One row of conv_tiles.def behind the dispatch switch: an MFMA row instantiates the kernel for the precisions of its mask and no other
+// (validate() refuses MXFP8 for a row without that instance), the other kinds go to their own files.
+template <int BM, int BN, int WMW, int WNW, int WKW, int NS, int SPEC, int KIND, int PRECS>
+int launch_tile(const vidc_conv_desc& dd, const ConvArgs& a, hipStream_t st) {
+    if constexpr (KIND == VIDC_TILE_KIND_MFMA) {
+        if constexpr (PRECS & MX8) if (dd.precision == VIDC_PREC_MXFP8) return launch_tile_p<BM, BN, WMW, WNW, WKW, NS, 3, SPEC>(a, st);
+        if constexpr (PRECS & X3) if (dd.precision == VIDC_PREC_BF16X3) return launch_tile_p<BM, BN, WMW, WNW, WKW, NS, 1, SPEC>(a, st);
+        if constexpr (PRECS & B16) if (dd.precision == VIDC_PREC_BF16) return launch_tile_p<BM, BN, WMW, WNW, WKW, NS, 2, SPEC>(a, st);
+        if constexpr (PRECS & F32) if (dd.precision == VIDC_PREC_FP32) return launch_tile_p<BM, BN, WMW, WNW, WKW, NS, 0, SPEC>(a, st);
+        VIDC_REQUIRE(false, VIDC_ERR_SHAPE, "conv: tiling %s has no instance for precision %d", kTiles[dd.tile].name, dd.precision);
+    } else if constexpr (KIND == VIDC_TILE_KIND_STREAM) {
+        return vidc::launch_wgemm_stream(dd, st);
+    } else if constexpr (KIND == VIDC_TILE_KIND_WINOGRAD) {
+        return vidc::launch_wino4_fused(dd, st);
+    } else {
+        VIDC_REQUIRE(false, VIDC_ERR_SHAPE, "conv: bad tile");
     }
-    VIDC_REQUIRE(precision != VIDC_PREC_MXFP8, VIDC_ERR_SHAPE, "conv: no MXFP8 instance of this tiling");
-    return precision == VIDC_PREC_BF16X3 ? launch_tile_p<BM, BN, WMW, WNW, WKW, NS, 1, SPEC>(a, st)
-           : precision == VIDC_PREC_BF16 ? launch_tile_p<BM, BN, WMW, WNW, WKW, NS, 2, SPEC>(a, st)
-                                         : launch_tile_p<BM, BN, WMW, WNW, WKW, NS, 0, SPEC>(a, st);
 }
 
 int validate(const vidc_conv_desc* d) {
@@ -1099,8 +1080,8 @@ int validate(const vidc_conv_desc* d) {
         VIDC_REQUIRE(d->ldx % 32 == 0, VIDC_ERR_SHAPE, "conv: MXFP8 needs ldx = a multiple of 128 channels (ldx %% 32 == 0), got %d", d->ldx);
         VIDC_REQUIRE(!(d->flags & (VIDC_STATS_OUT | VIDC_SPLIT_OUT | VIDC_X_PLANAR_GROUPS)), VIDC_ERR_SHAPE,
                      "conv: MXFP8 does not support STATS_OUT, SPLIT_OUT or X_PLANAR_GROUPS");
-        VIDC_REQUIRE(d->tile == VIDC_TILE_AUTO || (d->tile > VIDC_TILE_128x128 && d->tile <= VIDC_TILE_64x64_K2_D4), VIDC_ERR_SHAPE,
-                     "conv: MXFP8 runs the tilings 2 .. 13 only (no loader-wave, pipelined, streamed or Winograd tile), got %d", d->tile);
+        VIDC_REQUIRE(d->tile == VIDC_TILE_AUTO || (kTiles[d->tile].precisions & MX8), VIDC_ERR_SHAPE,
+                     "conv: tiling %s (%d) has no MXFP8 instance (no loader-wave, pipelined, streamed or Winograd tile has one)", kTiles[d->tile].name, d->tile);
     }
     VIDC_REQUIRE(!(d->flags & VIDC_MXFP8_OUT) || (d->precision == VIDC_PREC_MXFP8 && d->y_split), VIDC_ERR_SHAPE,
                  "conv: MXFP8_OUT needs VIDC_PREC_MXFP8 and y_split");
@@ -1108,7 +1089,7 @@ int validate(const vidc_conv_desc* d) {
     VIDC_REQUIRE(!(d->flags & VIDC_BF16_OUT) || (d->precision == VIDC_PREC_BF16 && d->y_split && d->ldy % 2 == 0 &&
                                                  !(d->flags & (VIDC_SPLIT_OUT | VIDC_MXFP8_OUT | VIDC_STATS_OUT))),
                  VIDC_ERR_SHAPE, "conv: BF16_OUT needs VIDC_PREC_BF16, y_split and an even ldy, without SPLIT_OUT / MXFP8_OUT / STATS_OUT");
-    VIDC_REQUIRE(d->splitk == 1 || d->workspace || d->tile == VIDC_TILE_G96x32_STREAM || d->tile == VIDC_TILE_G96x64_STREAM3, VIDC_ERR_NULL, "conv: split-K needs a workspace");
+    VIDC_REQUIRE(d->splitk == 1 || d->workspace || is_streamed(d->tile), VIDC_ERR_NULL, "conv: split-K needs a workspace");
     VIDC_REQUIRE(!(d->flags & VIDC_SPLIT_OUT) || (d->y_split && d->Cout % 32 == 0 && d->ldy % 32 == 0), VIDC_ERR_NULL,
                  "conv: SPLIT_OUT needs y_split and Cout, ldy multiples of 32");
     VIDC_REQUIRE(!(d->flags & VIDC_NO_F32_OUT) || (d->flags & (VIDC_SPLIT_OUT | VIDC_MXFP8_OUT | VIDC_BF16_OUT)), VIDC_ERR_SHAPE,
@@ -1135,7 +1116,7 @@ int make_args(const vidc_conv_desc& dd, ConvArgs& a) {
     a.groups = dd.groups; a.dil = dd.dilation > 1 ? dd.dilation : 1; a.x_gs = dd.x_gs; a.w_gs = dd.w_gs; a.y_gs = dd.y_gs; a.r_gs = dd.r_gs; a.p_gs = dd.p_gs;
     a.M = dd.B * dd.Ho * dd.Wo; a.K = dd.KH * dd.KW * dd.Cin; a.ksteps = a.K / BK;
     a.splitk = dd.splitk;
-    const TileInfo ti = kTiles[dd.tile];
+    const vidc_tile_info& ti = kTiles[dd.tile];
     a.tiles_m = (a.M + ti.bm - 1) / ti.bm;
     a.tiles_n = (a.Cout + ti.bn - 1) / ti.bn;
     {
@@ -1165,9 +1146,10 @@ extern "C" int vidc_conv2d_plan(vidc_conv_desc* d) {
     const int n_cu = 256;
     double best = 1e30;
     int best_tile = VIDC_TILE_64x64, best_sk = 1;
-    for (int t = 1; t < kFirstLoaderTile; ++t) {      // loader-wave variants are chosen by the measured table only
-        if (t == VIDC_TILE_128x128 && d->precision == VIDC_PREC_MXFP8) continue;      // (no MXFP8 instance: its registers spill)
-        const TileInfo ti = kTiles[t];
+    VIDC_REQUIRE(d->precision >= VIDC_PREC_FP32 && d->precision <= VIDC_PREC_MXFP8, VIDC_ERR_SHAPE, "conv plan: unknown precision %d", d->precision);
+    for (int t = 0; t < VIDC_TILE_COUNT; ++t) {
+        const vidc_tile_info& ti = kTiles[t];
+        if (!ti.planner || !(ti.precisions >> d->precision & 1)) continue;
         if (ti.bn > d->Cout && ti.bn > 64) continue;
         const long long tm = (M + ti.bm - 1) / ti.bm, tn = (d->Cout + ti.bn - 1) / ti.bn;
         const int nw = ti.wmw * ti.wnw * ti.wkw;
@@ -1189,7 +1171,7 @@ extern "C" int vidc_conv2d_plan(vidc_conv_desc* d) {
 }
 
 extern "C" size_t vidc_conv2d_workspace_bytes(const vidc_conv_desc* d) {
-    if (!d || d->splitk <= 1 || d->tile == VIDC_TILE_G96x32_STREAM || d->tile == VIDC_TILE_G96x64_STREAM3) return 0;      // (streamed tile: splitk = its number of group chunks, no partials)
+    if (!d || d->splitk <= 1 || is_streamed(d->tile)) return 0;      // (streamed tile: splitk = its number of group chunks, no partials)
     return ((size_t)VIDC_SPLITK_COUNTERS + (size_t)d->splitk * d->groups * d->B * d->Ho * d->Wo * d->Cout) * sizeof(float);
 }
 
@@ -1207,51 +1189,19 @@ extern "C" int vidc_conv2d_bn_act(const vidc_conv_desc* d, vidc_stream_t stream)
     if (rc != VIDC_OK) return rc;
     hipStream_t st = vidc::as_stream(stream);
     switch (dd.tile) {
-        case VIDC_TILE_128x128:  rc = launch_tile<128, 128, 2, 2, 1, 2>(a, st, dd.precision); break;      // (MXFP8: spills, no instance)
-        case VIDC_TILE_128x64:   rc = launch_tile<128, 64, 2, 2, 1, 3, 0, true>(a, st, dd.precision); break;
-        case VIDC_TILE_64x128:   rc = launch_tile<64, 128, 2, 2, 1, 3, 0, true>(a, st, dd.precision); break;
-        case VIDC_TILE_64x64:    rc = launch_tile<64, 64, 2, 2, 1, 4, 0, true>(a, st, dd.precision); break;
-        case VIDC_TILE_64x64_K2: rc = launch_tile<64, 64, 2, 2, 2, 3, 0, true>(a, st, dd.precision); break;
-        case VIDC_TILE_32x64_K2: rc = launch_tile<32, 64, 1, 2, 2, 3, 0, true>(a, st, dd.precision); break;
-        case VIDC_TILE_32x32_K4: rc = launch_tile<32, 32, 1, 1, 4, 3, 0, true>(a, st, dd.precision); break;
-        case VIDC_TILE_32x128:   rc = launch_tile<32, 128, 1, 4, 1, 4, 0, true>(a, st, dd.precision); break;
-        case VIDC_TILE_32x32_K8: rc = launch_tile<32, 32, 1, 1, 8, 2, 0, true>(a, st, dd.precision); break;
-        case VIDC_TILE_32x64_K2_D5: rc = launch_tile<32, 64, 1, 2, 2, 5, 0, true>(a, st, dd.precision); break;
-        case VIDC_TILE_32x32_K4_D4: rc = launch_tile<32, 32, 1, 1, 4, 4, 0, true>(a, st, dd.precision); break;
-        case VIDC_TILE_32x128_D6:   rc = launch_tile<32, 128, 1, 4, 1, 6, 0, true>(a, st, dd.precision); break;
-        case VIDC_TILE_64x64_K2_D4: rc = launch_tile<64, 64, 2, 2, 2, 4, 0, true>(a, st, dd.precision); break;
-        case VIDC_TILE_32x64_K2_L:     rc = launch_tile<32, 64, 1, 2, 2, 3, 1>(a, st, dd.precision); break;
-        case VIDC_TILE_32x64_K2_D5_L:  rc = launch_tile<32, 64, 1, 2, 2, 5, 1>(a, st, dd.precision); break;
-        case VIDC_TILE_32x32_K4_D4_L:  rc = launch_tile<32, 32, 1, 1, 4, 4, 1>(a, st, dd.precision); break;
-        case VIDC_TILE_64x64_L:        rc = launch_tile<64, 64, 2, 2, 1, 4, 1>(a, st, dd.precision); break;
-        case VIDC_TILE_64x64_K2_D4_L:  rc = launch_tile<64, 64, 2, 2, 2, 4, 1>(a, st, dd.precision); break;
-        case VIDC_TILE_64x128_L:       rc = launch_tile<64, 128, 2, 2, 1, 3, 1>(a, st, dd.precision); break;
-        case VIDC_TILE_128x64_L:       rc = launch_tile<128, 64, 2, 2, 1, 3, 1>(a, st, dd.precision); break;
-        case VIDC_TILE_64x32_K2:       rc = launch_tile<64, 32, 2, 1, 2, 3>(a, st, dd.precision); break;
-        case VIDC_TILE_64x32_K2_D5:    rc = launch_tile<64, 32, 2, 1, 2, 5>(a, st, dd.precision); break;
-        case VIDC_TILE_64x32_K2_D5_L:  rc = launch_tile<64, 32, 2, 1, 2, 5, 1>(a, st, dd.precision); break;
-        case VIDC_TILE_128x128_D3:     rc = launch_tile<128, 128, 2, 2, 1, 3>(a, st, dd.precision); break;
-        case VIDC_TILE_128x128_D3_L:   rc = launch_tile<128, 128, 2, 2, 1, 3, 1>(a, st, dd.precision); break;
-        case VIDC_TILE_256x128:        rc = launch_tile<256, 128, 4, 2, 1, 3>(a, st, dd.precision); break;
-        case VIDC_TILE_128x256:        rc = launch_tile<128, 256, 2, 4, 1, 3>(a, st, dd.precision); break;
-        case VIDC_TILE_32x64_K2_D2:    rc = launch_tile<32, 64, 1, 2, 2, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_64x64_D2:       rc = launch_tile<64, 64, 2, 2, 1, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_32x32_K4_D2:    rc = launch_tile<32, 32, 1, 1, 4, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_64x128_D2:      rc = launch_tile<64, 128, 2, 2, 1, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_64x32_K2_D2:    rc = launch_tile<64, 32, 2, 1, 2, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_128x128_D4_P:   rc = launch_tile<128, 128, 2, 2, 1, 4, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_128x128_D3_P:   rc = launch_tile<128, 128, 2, 2, 1, 3, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_64x64_D4_P:     rc = launch_tile<64, 64, 2, 2, 1, 4, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_128x64_D4_P:    rc = launch_tile<128, 64, 2, 2, 1, 4, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_64x64_K2_D4_P:  rc = launch_tile<64, 64, 2, 2, 2, 4, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_64x32_K2_D5_P:  rc = launch_tile<64, 32, 2, 1, 2, 5, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_32x64_K2_D5_P:  rc = launch_tile<32, 64, 1, 2, 2, 5, 2>(a, st, dd.precision); break;
-        case VIDC_TILE_G96x32_STREAM:
-        case VIDC_TILE_G96x64_STREAM3: rc = vidc::launch_wgemm_stream(dd, st); break;
-        case VIDC_TILE_WINO4_FUSED:    rc = vidc::launch_wino4_fused(dd, st); break;
-        default: VIDC_REQUIRE(false, VIDC_ERR_SHAPE, "conv: bad tile");
+#define VIDC_CONV_TILE(id, name, BM, BN, WMW, WNW, WKW, NS, SPEC, KIND, PRECS, PLANNER) \
+        case id: rc = launch_tile<BM, BN, WMW, WNW, WKW, NS, SPEC, VIDC_TILE_KIND_##KIND, PRECS>(dd, a, st); break;
+#include "conv_tiles.def"
+#undef VIDC_CONV_TILE
     }
     return rc;
+}
+
+extern "C" int vidc_conv_tile_info(int tile, vidc_tile_info* out) {
+    VIDC_REQUIRE(out, VIDC_ERR_NULL, "vidc_conv_tile_info: null pointer");
+    VIDC_REQUIRE(tile >= 0 && tile < VIDC_TILE_COUNT, VIDC_ERR_SHAPE, "vidc_conv_tile_info: unknown tile id %d", tile);
+    *out = kTiles[tile];
+    return VIDC_OK;
 }
 
 extern "C" int vidc_split_bf16x3(const float* x, void* y, long long rows, int C, int ldx, vidc_stream_t stream) {
