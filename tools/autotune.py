@@ -119,7 +119,7 @@ def main():
     ap.add_argument("--only-missing", action="store_true", help="keep the committed table and measure only signatures it lacks")
     ap.add_argument("--split-charge", type=float, default=0.25,
                     help="fraction of the standalone split-kernel time charged to a bf16x3 conv (most splits are fused into the\n"
-                         "producing conv epilogue by engine.Program._fuse_splits, so the default charges little)")
+                         "producing conv epilogue by engine.Program._fuse_images, so the default charges little)")
     a = ap.parse_args()
     dev = torch.device("cuda")
     lib = L.lib()

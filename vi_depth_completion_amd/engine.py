@@ -7,6 +7,7 @@ Layout: activations are NHWC fp32.  A "grouped" tensor (G > 1) keeps the G group
 one [B,H,W,G*C] buffer, so the rgb/normal/depth pyramids of ModifiedFPN run as one grouped launch per
 layer and `torch.cat((rgb, normal, depth), dim=1)` (depth_completion.py:151-152) costs nothing.
 """
+import collections
 import ctypes as C
 import json
 import os
@@ -76,20 +77,19 @@ class WeightStore:
         return self.sd()[key]
 
     def packed(self, keys, dry_run=False, precision=0):
-        """[G][Cout][KH][KW][Cin] fp32 (precision 0) or the split-bf16 image of the same bytes (precision 1), packed by
-        the C kernels; precision 2: [G][Cout * K bf16 values], the plain-bf16 rows (64 channels per K unit) in float32-typed storage; precision 3: [G][Cout * K * 33 / 32 bytes], the MXFP8 images (include/vidc.h) in float32-typed storage."""
+        """The weights of the G groups `keys` packed by the C kernels for FORMATS[precision], in float32-typed storage [G][Cout][welems]:
+        [KH][KW][Cin] fp32, the split-bf16 image of the same bytes, K bf16 values (64 channels per K unit), or the K * 33 / 32 bytes of
+        the MXFP8 images (include/vidc.h)."""
         ck = ("w", precision) + tuple(keys)
         if ck not in self._cache:
             ws = [self.sd()[k + ".weight"].contiguous() for k in keys]
             co, ci, kh, kw = ws[0].shape
-            per_group = {L.PREC_MXFP8: kh * kw * ci // 128 * 33, L.PREC_BF16: kh * kw * ci // 2}.get(precision, kh * kw * ci)
-            out = torch.empty((len(ws), co, per_group), dtype=torch.float32, device=ws[0].device)
+            fmt = FORMATS[precision]
+            out = torch.empty((len(ws), co, fmt.welems(kh * kw * ci)), dtype=torch.float32, device=ws[0].device)
             for g, w in enumerate(ws):
                 assert tuple(w.shape) == (co, ci, kh, kw)
                 if not dry_run:
-                    fn = {L.PREC_BF16X3: L.lib().vidc_pack_conv_weight_bf16x3, L.PREC_BF16: L.lib().vidc_pack_conv_weight_bf16,
-                          L.PREC_MXFP8: L.lib().vidc_pack_conv_weight_mxfp8}.get(precision, L.lib().vidc_pack_conv_weight)
-                    L.check(fn(L.ptr(w), L.ptr(out[g]), co, ci, kh, kw, L.current_stream()), "pack")
+                    L.check(getattr(L.lib(), fmt.pack)(L.ptr(w), L.ptr(out[g]), co, ci, kh, kw, L.current_stream()), "pack")
             if dry_run:
                 return out
             self._cache[ck] = out
@@ -284,6 +284,48 @@ def conv_signature(d):
     return "M%d_N%d_K%d_k%ds%d_G%d" % (d.B * d.Ho * d.Wo, d.Cout, d.KH * d.KW * d.Cin, d.KH, d.stride, d.groups)
 
 
+# One row per conv operand format (VIDC_PREC_* of include/vidc.h); everything this file knows about a format is in its row.
+#   name, pack, welems: the display name; the C entry point that packs a weight; the float32-typed elements of one packed group of
+#                       K = KH * KW * Cin values.
+# The activation side of the three reduced formats -- the image of an fp32 tensor that such a conv reads (Program.image):
+#   kind, op          : the recorded op that makes the image, and its vidc_op_kind
+#   unit              : channels of a K unit; a row of an image holds whole units
+#   esz               : bytes per channel of the image's T, whose ld / ch_off count such channels
+#   elems             : float32-typed buffer elements of the image of `rows` pixels of `c` channels in `g` groups
+#   sliceable         : a channel slice of an image, at a multiple of `unit`, is the image of that slice
+#   folded            : the groups are channel slices of one row of C * G channels; otherwise every group is a plane pair of its own
+#   out_flag, out_key : the conv flag that makes a producer's epilogue write the image, and the recorded key of that image
+#   out_gs, out_esz   : in a conv descriptor d with out_flag, the elements from one group's image to the next, and the bytes of one
+Format = collections.namedtuple("Format", "name pack welems kind op unit esz elems sliceable folded out_flag out_key out_gs out_esz",
+                                defaults=(None,) * 11)
+FORMATS = {
+    L.PREC_FP32: Format("fp32", "vidc_pack_conv_weight", lambda k: k),
+    L.PREC_BF16X3: Format("bf16x3", "vidc_pack_conv_weight_bf16x3", lambda k: k,          # a unit is [32 x hi | 32 x lo]: the 128 bytes of 32 floats
+                          kind="split", op=L.OP_SPLIT, unit=32, esz=4, elems=lambda rows, c, g: rows * c * g, sliceable=True, folded=True,
+                          out_flag=L.SPLIT_OUT, out_key="split_out", out_gs=lambda d: d.y_gs, out_esz=4),
+    L.PREC_MXFP8: Format("mxfp8", "vidc_pack_conv_weight_mxfp8", lambda k: k // 128 * 33,  # per group a plane of e4m3 bytes, then its scales: 33 bytes per 32
+                         kind="quant", op=L.OP_QUANT, unit=128, esz=4, elems=lambda rows, c, g: -(-g * rows * c * 33 // 128), sliceable=False,
+                         folded=False, out_flag=L.MXFP8_OUT, out_key="mx_out", out_gs=lambda d: d.B * d.Ho * d.Wo * d.Cout * 33 // 128, out_esz=4),
+    L.PREC_BF16: Format("bf16", "vidc_pack_conv_weight_bf16", lambda k: k // 2,            # dense rows of bf16 values: 64 channels are 128 bytes
+                        kind="cast", op=L.OP_CAST, unit=64, esz=2, elems=lambda rows, c, g: rows * c * g // 2, sliceable=True, folded=True,
+                        out_flag=L.BF16_OUT, out_key="bf16_out", out_gs=lambda d: d.y_gs, out_esz=2),
+}
+IMAGE_FORMATS = {f.kind: f for f in FORMATS.values() if f.kind}      # in the order Program._fuse_images folds them: split, quant, cast
+OP_KINDS = dict({"conv": L.OP_CONV, "stem": L.OP_STEM, "maxpool": L.OP_MAXPOOL, "upsample": L.OP_UPSAMPLE, "head": L.OP_HEAD,
+                 "warp_params": L.OP_WARP_PARAMS, "warp_fwd": L.OP_WARP_FWD, "warp_inv": L.OP_WARP_INV, "avgpool": L.OP_AVGPOOL,
+                 "normalize": L.OP_NORMALIZE, "det_im2col": L.OP_DET_IM2COL, "mask": L.OP_MASK, "wino_in": L.OP_WINO_IN,
+                 "wino_out": L.OP_WINO_OUT, "nearest2x": L.OP_NEAREST2X, "copy": L.OP_COPY}, **{f.kind: f.op for f in IMAGE_FORMATS.values()})
+# precision mode -> (the direct convs it takes out of the mixed mode's choice, the format they run in)
+MODE_LAYERS = {"mxfp8": (mxfp8_layer, L.PREC_MXFP8), "bf16": (bf16_layer, L.PREC_BF16)}
+
+
+def _args(g, p=(), i=(), f=()):
+    """Fills the leading pointer / int / float arguments of a generic op (vidc_generic_args); the rest stay zero."""
+    for arr, vals in ((g.p, p), (g.i, i), (g.f, f)):
+        for j, v in enumerate(vals):
+            arr[j] = v
+
+
 class Program:
     """Records ops symbolically (buffers are integers), then `finalize()` plans memory and builds the C program."""
 
@@ -304,11 +346,10 @@ class Program:
         self.direct_flops = 0    # the executed layers in direct form (what self.flops was before the Winograd layers)
         self.ref_flops = 0       # the same layers in the reference's formulation (1x1 convs AFTER their upsample: SURVEY §8d)
         self._keep = []
-        self._split_cache = {}   # (buf, ch_off, channels) -> buffer id of the split-bf16 image
-        self._quant_cache = {}   # (buf, ch_off, channels, groups) -> the MXFP8 image (T)
-        self._cast_cache = {}    # (buf, ch_off, channels) -> (buffer id of the plain-bf16 image, its channels per row)
+        self._images = {}        # (buf, precision, ch_off, channels of a row, planes) -> the image (T) of that fp32 tensor in FORMATS[precision]
         self.cuts = []           # op indices where a new segment starts (see cut()); filled by finalize()
         self._cut_markers = []
+        self.n_fused_splits = self.n_fused_quants = self.n_fused_casts = self.n_fused_warps = 0      # image / warp ops folded by finalize()
         self.mode = mode if mode is not None else precision_mode()
         if self.mode not in ("fp32", "mixed", "mxfp8", "bf16"):
             raise ValueError("unknown precision mode %r (VIDC_PRECISION: fp32, mixed, mxfp8 or bf16)" % (self.mode,))
@@ -342,16 +383,14 @@ class Program:
         """Starts a new segment: the ops recorded so far and the ops that follow can be captured / launched separately
         (capture_segments / launch_segment), with host-enqueued work in between."""
         assert self.ops, "cut() before the first op"
-        self._cut_markers.append(self.ops[-1])      # identity of the last op of the segment (op indices shift in _fuse_splits)
+        self._cut_markers.append(self.ops[-1])      # identity of the last op of the segment (op indices shift in _fuse_images)
 
     def on_stream(self, sid, wait_mask=0):
         self.stream_id, self.wait_mask = sid, wait_mask
 
     def _written(self, t):
         """t's buffer is (re)written: its split / MXFP8 / bf16 images are stale."""
-        self._split_cache = {k: v for k, v in self._split_cache.items() if k[0] != t.buf}
-        self._quant_cache = {k: v for k, v in self._quant_cache.items() if k[0] != t.buf}
-        self._cast_cache = {k: v for k, v in self._cast_cache.items() if k[0] != t.buf}
+        self._images = {k: v for k, v in self._images.items() if k[0] != t.buf}
 
     def _emit(self, kind, reads, writes, **kw):
         kw.update(stream_id=self.stream_id, wait_mask=self.wait_mask)
@@ -379,11 +418,11 @@ class Program:
         if accumulate:
             flags |= L.ACCUM
         flops = 2 * self.B * Ho * Wo * co * ci * kh * kw * G
-        mx = self.mode == "mxfp8" and mxfp8_layer(keys[0], co, ci, flops)
-        bf = self.mode == "bf16" and bf16_layer(keys[0], co, ci, flops)
+        selects, reduced_prec = MODE_LAYERS.get(self.mode, (None, None))
+        reduced = selects is not None and selects(keys[0], co, ci, flops)
         wm = 0
         if residual is None and not accumulate:
-            wm = winograd_choice(self.B, x.H, x.W, co, ci, kh, kw, stride, padding, dilation, G, mode=self.winograd, precision=self.mode, reduced=mx or bf)
+            wm = winograd_choice(self.B, x.H, x.W, co, ci, kh, kw, stride, padding, dilation, G, mode=self.winograd, precision=self.mode, reduced=reduced)
         if wm:
             self.ref_flops += int(round(flops * ref_flops_scale))
             self.direct_flops += flops
@@ -399,17 +438,9 @@ class Program:
         self.flops += flops
         self.direct_flops += flops
         self.ref_flops += int(round(flops * ref_flops_scale))
-        # precision: measured table entry if there is one, else by size
         sig = conv_signature(L.conv_desc(self.B, x.H, x.W, ci, co, kh, kw, stride, padding, dilation, G))
-        prec = L.PREC_FP32
-        if mx:
-            prec = L.PREC_MXFP8
-        elif bf:
-            prec = L.PREC_BF16
-        elif self.mode in ("mixed", "mxfp8", "bf16"):
-            ent = tuning_table().get(sig)
-            prec = ent[2] if (ent is not None and len(ent) > 2) else default_precision(flops)
-        xin = {L.PREC_BF16X3: self.split, L.PREC_MXFP8: self.quant, L.PREC_BF16: self.cast}.get(prec, lambda t: t)(x)
+        prec = reduced_prec if reduced else self._table_precision(sig, flops)
+        xin = self.image(x, prec) if FORMATS[prec].kind else x
         self._emit("conv", [xin, residual, y if accumulate else None], [y], x=xin, y=y, keys=keys, precision=prec,
                    bn=_keys(bn) if bn is not None else None, bn2=_keys(bn2) if bn2 is not None else None,
                    residual=residual, flags=flags, stride=stride, pad=padding, geom=(co, ci, kh, kw, Ho, Wo), dilation=dilation, sig=sig)
@@ -425,10 +456,7 @@ class Program:
         gflops = 2 * tiles * a2 * G * co * ci
         self.flops += gflops
         sig = conv_signature(L.gemm_desc(tiles, ci, co, groups=a2 * G))
-        prec = L.PREC_FP32
-        if self.mode in ("mixed", "mxfp8", "bf16"):
-            ent = tuning_table().get(sig)
-            prec = ent[2] if (ent is not None and len(ent) > 2) else default_precision(gflops)
+        prec = self._table_precision(sig, gflops)
         V = T(self._new_buf(tiles * a2 * G * ci), 1, 1, tiles, ci, a2 * G)
         Mm = T(self._new_buf(tiles * a2 * G * co), 1, 1, tiles, co, a2 * G)
         self._emit("wino_in", [x], [V], x=x, v=V, m=m, cin=ci, split=int(prec == L.PREC_BF16X3))
@@ -449,51 +477,52 @@ class Program:
                    wino_fused=tiles, sig=conv_signature(L.gemm_desc(tiles, ci, co, groups=36 * len(keys))))      # (named by the products it executes)
         return y
 
+    def _table_precision(self, sig, flops):
+        """The operand format of a launch that the mode does not select itself (MODE_LAYERS): the entry of the measured table for its
+        signature if there is one, else by size -- in every mode but fp32."""
+        if self.mode == "fp32":
+            return L.PREC_FP32
+        ent = tuning_table().get(sig)
+        return ent[2] if (ent is not None and len(ent) > 2) else default_precision(flops)
+
+    def image(self, x, precision):
+        """The image of the fp32 activation tensor x in the operand format FORMATS[precision] -- split bf16, MXFP8 or plain bf16 -- made
+        once per tensor, by a launch of its own that finalize() folds into the producer of x where it can (_fuse_images).  Returns the
+        caller's view of it: a T of the format's esz whose ld / ch_off count channels of the image."""
+        fmt = FORMATS[precision]
+        ch, planes = (x.C * x.G, 1) if fmt.folded else (x.C, x.G)       # (grouped and channel-concatenated views share one folded image)
+        ck = (x.buf, precision, x.ch_off, ch, planes)
+        if ck not in self._images:
+            assert not x.nchw and x.esz == 4 and ch % fmt.unit == 0
+            if fmt.sliceable:
+                # a channel slice of a tensor whose image exists is a slice of that image: the layout keeps every unit (128 bytes) in
+                # place, so only ch_off (a multiple of the unit) moves
+                for (b0, p0, off0, ch0, _), img in self._images.items():
+                    if (b0, p0) == (x.buf, precision) and off0 <= x.ch_off and x.ch_off + ch <= off0 + ch0 and (x.ch_off - off0) % fmt.unit == 0:
+                        return T(img.buf, x.B, x.H, x.W, x.C, x.G, ld=img.ld, ch_off=x.ch_off - off0, esz=fmt.esz)
+            y = T(self._new_buf(fmt.elems(x.B * x.H * x.W, x.C, x.G)), x.B, x.H, x.W, x.C, x.G, ld=ch, esz=fmt.esz)
+            self._emit(fmt.kind, [x], [y], x=x, y=y)
+            self._images[ck] = y
+        return T(self._images[ck].buf, x.B, x.H, x.W, x.C, x.G, ld=ch, esz=fmt.esz)
+
     def split(self, x):
-        """Split-bf16 image of an fp32 activation tensor (same geometry / bytes), made once per tensor."""
-        ck = (x.buf, x.ch_off, x.C * x.G)
-        if ck not in self._split_cache:
-            assert not x.nchw and (x.C * x.G) % 32 == 0
-            # a channel slice of a tensor whose split image exists is a slice of that image: the split layout keeps every
-            # 32-channel unit in place ([32 x hi | 32 x lo] = the same 128 bytes), so only ch_off (a multiple of 32) moves
-            for (b0, off0, ch0), (sbuf, ld0) in self._split_cache.items():
-                if b0 == x.buf and off0 <= x.ch_off and x.ch_off + x.C * x.G <= off0 + ch0 and (x.ch_off - off0) % 32 == 0 and ld0 == ch0:
-                    return T(sbuf, x.B, x.H, x.W, x.C, x.G, ld=ld0, ch_off=x.ch_off - off0)
-            y = T(self._new_buf(self.B * x.H * x.W * x.C * x.G), x.B, x.H, x.W, x.C, x.G)
-            self._emit("split", [x], [y], x=x, y=y)
-            self._split_cache[ck] = (y.buf, x.C * x.G)
-        # same storage, the caller's view of it (grouped and channel-concatenated views share one split image)
-        sbuf, ld0 = self._split_cache[ck]
-        return T(sbuf, x.B, x.H, x.W, x.C, x.G, ld=ld0)
+        return self.image(x, L.PREC_BF16X3)
 
     def quant(self, x):
-        """MXFP8 image of an fp32 activation tensor (include/vidc.h: per group a data plane of rows of x.C e4m3 bytes, then its scale
-        plane), made once per tensor; as a program tensor its buffer holds G * rows * C * 33 / 32 bytes and `ld` = C."""
-        ck = (x.buf, x.ch_off, x.C, x.G)
-        if ck not in self._quant_cache:
-            assert not x.nchw and x.C % 128 == 0
-            rows = x.B * x.H * x.W
-            y = T(self._new_buf(-(-x.G * rows * x.C * 33 // 128)), x.B, x.H, x.W, x.C, x.G, ld=x.C)
-            self._emit("quant", [x], [y], x=x, y=y)
-            self._quant_cache[ck] = y
-        return self._quant_cache[ck]
+        return self.image(x, L.PREC_MXFP8)
 
     def cast(self, x):
-        """Plain-bf16 image of an fp32 activation tensor (vidc_cast_bf16: dense rows of x.C * x.G bf16 values, group g at channel g * x.C),
-        made once per tensor: the operand of the VIDC_PREC_BF16 convs.  Its T counts bf16 channels (esz = 2)."""
-        ck = (x.buf, x.ch_off, x.C * x.G)
-        if ck not in self._cast_cache:
-            assert not x.nchw and x.esz == 4 and (x.C * x.G) % 64 == 0
-            # a channel slice of a tensor whose image exists is a slice of that image: dense bf16 rows keep every 64-channel unit (128
-            # bytes) in place, so only ch_off (a multiple of 64) moves
-            for (b0, off0, ch0), (cbuf, ld0) in self._cast_cache.items():
-                if b0 == x.buf and off0 <= x.ch_off and x.ch_off + x.C * x.G <= off0 + ch0 and (x.ch_off - off0) % 64 == 0:
-                    return T(cbuf, x.B, x.H, x.W, x.C, x.G, ld=ld0, ch_off=x.ch_off - off0, esz=2)
-            y = T(self._new_buf(self.B * x.H * x.W * x.C * x.G // 2), x.B, x.H, x.W, x.C, x.G, esz=2)
-            self._emit("cast", [x], [y], x=x, y=y)
-            self._cast_cache[ck] = (y.buf, x.C * x.G)
-        cbuf, ld0 = self._cast_cache[ck]
-        return T(cbuf, x.B, x.H, x.W, x.C, x.G, ld=ld0, esz=2)
+        return self.image(x, L.PREC_BF16)
+
+    def level_image(self, t):
+        """ONE image of a pyramid level for the decoders of this mode, which read channel slices of it: split bf16 in the mixed and mxfp8
+        modes (written by the producing conv's epilogue; a split launch behind an MXFP8 producer), plain bf16 in the bf16 mode where the
+        level has whole units (the producing conv's VIDC_BF16_OUT), none in fp32."""
+        if self.mode == "bf16":
+            if (t.C * t.G) % FORMATS[L.PREC_BF16].unit == 0:
+                self.image(t, L.PREC_BF16)
+        elif self.mode != "fp32":
+            self.image(t, L.PREC_BF16X3)
 
     def linear(self, x, key, relu=False):
         """nn.Linear on `x.view(B, -1)` of the reference's NCHW tensor (surface_normal_dorn.py:23-24), as a 1x1 conv over the
@@ -614,179 +643,167 @@ class Program:
         self._emit("copy", [src], [dst], src=src, dst=dst)
 
     # ---- planning ----------------------------------------------------------------------------------------
-    def _fuse_splits(self):
-        """A split op whose input was just produced by a fused conv -- or by a stem / max-pool / upsample kernel -- is folded into
-        that producer (VIDC_SPLIT_OUT / the y_split argument of the glue kernels); when nothing else reads the fp32 result
-        the producer does not store it at all (VIDC_NO_F32_OUT, VIDC_UP_NO_F32_OUT, y = NULL)."""
-        n = len(self.ops)
-        drop = set()
-        for i, (kind, _r, _w, kw) in enumerate(self.ops):
-            if kind != "split":
-                continue
-            xs = kw["x"]
-            j = next((t for t in range(i - 1, -1, -1) if xs.buf in self.ops[t][2]), None)
-            if j is None or self.ops[j][0] not in ("conv", "maxpool", "upsample", "stem", "wino_out"):
-                continue
-            pkind, pk = self.ops[j][0], self.ops[j][3]
-            y = pk["y"]
-            if pkind == "stem":
-                # G launches write the channel slices of one tensor: all of them get the image of the whole tensor
-                writers = [t for t in range(j + 1) if self.ops[t][0] == "stem" and self.ops[t][3]["y"].buf == y.buf]
-                if xs.ch_off != 0 or xs.C * xs.G != y.C * y.G or y.ld != y.C * y.G or y.ld % 32 or y.C % 32 or \
-                        any(self.ops[t][3].get("split_out") is not None for t in writers) or len(writers) != y.G:
+    def _last_writer(self, i, buf):
+        return next((t for t in range(i - 1, -1, -1) if buf in self.ops[t][2]), None)
+
+    def _cut_between(self, marks, j, i):
+        """A segment boundary between op j and op i (marks: the ids of the cut markers): what a fold moves from i to j must not depend on
+        which segments ran."""
+        return any(id(self.ops[t]) in marks for t in range(j, i))
+
+    def _attach(self, t, fmt, img):
+        """Op t writes `img`, the image of its result in the format fmt, as well."""
+        kind, _r, writes, kw = self.ops[t]
+        kw[fmt.out_key] = img
+        if kind in ("conv", "wino_out"):
+            kw["flags"] |= fmt.out_flag
+        writes.append(img.buf)
+
+    def _fold_split(self, i, kw, marks):
+        """A split whose input was just produced by fused convs, max-pool, upsample or Winograd output kernels (VIDC_SPLIT_OUT / the y_split
+        argument of the glue kernels) or by the stem launches of a grouped stem output.  Not behind a conv of another reduced format,
+        which writes its own image."""
+        fmt, xs = IMAGE_FORMATS["split"], kw["x"]
+        j = self._last_writer(i, xs.buf)
+        if j is None or self.ops[j][0] not in ("conv", "maxpool", "upsample", "stem", "wino_out"):
+            return False
+        if self.ops[j][0] == "stem":
+            # G launches write the channel slices of one tensor: all of them get the image of the whole tensor
+            y = self.ops[j][3]["y"]
+            writers = [t for t in range(j + 1) if self.ops[t][0] == "stem" and self.ops[t][3]["y"].buf == y.buf]
+            if xs.ch_off != 0 or xs.C * xs.G != y.C * y.G or y.ld != y.C * y.G or y.ld % fmt.unit or y.C % fmt.unit or \
+                    any(self.ops[t][3].get(fmt.out_key) is not None for t in writers) or len(writers) != y.G:
+                return False
+            for t in writers:
+                self._attach(t, fmt, kw["y"])
+            return True
+        # general case: the tensor is written by one producer, or slice by slice by several (a concat buffer filled by a conv and
+        # an upsample, say); every producer writes its slice of the split image.  The slices must tile the split's channel range.
+        last = {}                                        # channel slice -> its LAST writer (earlier ones are superseded)
+        foreign = False
+        for t in range(i):
+            if xs.buf in self.ops[t][2]:
+                if self.ops[t][0] not in ("conv", "maxpool", "upsample", "wino_out"):
+                    foreign = True
                     continue
-                for t in writers:
-                    self.ops[t][3]["split_out"] = kw["y"]
-                    self.ops[t][2].append(kw["y"].buf)
-                drop.add(i)
-                continue
-            # general case: the tensor is written by one producer, or slice by slice by several (a concat buffer filled by a conv and
-            # an upsample, say); every producer writes its slice of the split image.  The slices must tile the split's channel range.
-            last = {}                                        # channel slice -> its LAST writer (earlier ones are superseded)
-            foreign = False
-            for t in range(i):
-                if xs.buf in self.ops[t][2]:
-                    if self.ops[t][0] not in ("conv", "maxpool", "upsample", "wino_out"):
-                        foreign = True
-                        continue
-                    yt = self.ops[t][3]["y"]
-                    if yt.buf == xs.buf:
-                        last[(yt.ch_off, yt.C * yt.G)] = t
-            writers = sorted(last.values())
-            lo, hi = xs.ch_off, xs.ch_off + xs.C * xs.G
-            ok = bool(writers) and not foreign and xs.ld % 32 == 0 and lo % 32 == 0
-            cover = []
-            for t in writers:
                 yt = self.ops[t][3]["y"]
-                ok = ok and yt.ld == xs.ld and yt.ch_off % 32 == 0 and (yt.C * yt.G) % 32 == 0 and lo <= yt.ch_off and \
-                    yt.ch_off + yt.C * yt.G <= hi and self.ops[t][3].get("split_out") is None and \
-                    self.ops[t][3].get("precision") not in (L.PREC_MXFP8, L.PREC_BF16)      # (an MXFP8 / plain-bf16 conv writes no split image)
-                cover.append((yt.ch_off, yt.ch_off + yt.C * yt.G))
-            cover.sort()
-            ok = ok and cover[0][0] == lo and cover[-1][1] == hi and all(cover[k][1] == cover[k + 1][0] for k in range(len(cover) - 1))
-            if not ok:
-                continue
-            simg = kw["y"]                                   # the split image: compact, ld = xs.C * xs.G
-            for t in writers:
-                yt = self.ops[t][3]["y"]
-                self.ops[t][3]["split_out"] = T(simg.buf, yt.B, yt.H, yt.W, yt.C, yt.G, ld=simg.C * simg.G, ch_off=yt.ch_off - lo)
-                if self.ops[t][0] in ("conv", "wino_out"):
-                    self.ops[t][3]["flags"] |= L.SPLIT_OUT
-                self.ops[t][2].append(simg.buf)
-            drop.add(i)
-        for j, (kind, _r, _w, kw) in enumerate(self.ops):
-            if kind in ("conv", "maxpool", "upsample", "stem", "wino_out") and kw.get("split_out") is not None and kw["y"].buf not in self.pinned:
-                yb = kw["y"].buf
-                used = any(t not in drop and yb in self.ops[t][1] for t in range(j + 1, n))
-                # a later writer of the same buffer that accumulates into it needs the fp32 values too (reads cover that); a
-                # later plain writer of ANOTHER slice of the buffer (stem groups) does not
-                if not used:
-                    if kind in ("conv", "wino_out"):
-                        kw["flags"] |= L.NO_F32_OUT
-                    elif kind == "upsample":
-                        kw["flags"] |= L.UP_NO_F32_OUT
-                    else:
-                        kw["no_f32"] = True
-        self.n_fused_splits = len(drop)
-        self.ops = [op for i, op in enumerate(self.ops) if i not in drop]
+                if yt.buf == xs.buf:
+                    last[(yt.ch_off, yt.C * yt.G)] = t
+        writers = sorted(last.values())
+        lo, hi = xs.ch_off, xs.ch_off + xs.C * xs.G
+        ok = bool(writers) and not foreign and xs.ld % fmt.unit == 0 and lo % fmt.unit == 0
+        cover = []
+        for t in writers:
+            yt, pk = self.ops[t][3]["y"], self.ops[t][3]
+            ok = ok and yt.ld == xs.ld and yt.ch_off % fmt.unit == 0 and (yt.C * yt.G) % fmt.unit == 0 and lo <= yt.ch_off and \
+                yt.ch_off + yt.C * yt.G <= hi and pk.get(fmt.out_key) is None and \
+                FORMATS[pk.get("precision", L.PREC_FP32)].out_key in (None, fmt.out_key)
+            cover.append((yt.ch_off, yt.ch_off + yt.C * yt.G))
+        cover.sort()
+        ok = ok and cover[0][0] == lo and cover[-1][1] == hi and all(cover[k][1] == cover[k + 1][0] for k in range(len(cover) - 1))
+        if not ok:
+            return False
+        simg = kw["y"]                                   # the split image: compact, ld = xs.C * xs.G
+        for t in writers:
+            yt = self.ops[t][3]["y"]
+            self._attach(t, fmt, T(simg.buf, yt.B, yt.H, yt.W, yt.C, yt.G, ld=simg.C * simg.G, ch_off=yt.ch_off - lo))
+        return True
 
-    def _fuse_quants(self):
-        """A quant op whose input is the whole output of one MXFP8 conv is folded into that conv (VIDC_MXFP8_OUT: its epilogue writes
-        the image); when nothing else reads the fp32 result the conv does not store it (VIDC_NO_F32_OUT).  Every other producer -- the
-        max-pool, an upsample, Winograd outputs, the stem, a conv of another precision, several producers of one tensor, a channel
-        slice -- is followed by the stand-alone quant launch."""
-        n = len(self.ops)
-        drop = set()
-        for i, (kind, _r, _w, kw) in enumerate(self.ops):
-            if kind != "quant":
-                continue
-            xs = kw["x"]
-            writers = [t for t in range(i) if xs.buf in self.ops[t][2]]
-            if len(writers) != 1 or self.ops[writers[0]][0] != "conv":
-                continue
-            j = writers[0]
-            pk = self.ops[j][3]
-            y = pk["y"]
-            if pk["precision"] != L.PREC_MXFP8 or pk.get("mx_out") is not None or y.buf != xs.buf or \
-                    (y.ch_off, y.C, y.G, y.ld) != (xs.ch_off, xs.C, xs.G, xs.ld) or y.ch_off != 0 or y.ld != y.C * y.G:
-                continue
-            pk["mx_out"] = kw["y"]
-            pk["flags"] |= L.MXFP8_OUT
-            self.ops[j][2].append(kw["y"].buf)
-            drop.add(i)
-        for j, (kind, _r, _w, kw) in enumerate(self.ops):
-            if kind == "conv" and kw.get("mx_out") is not None and kw["y"].buf not in self.pinned:
-                yb = kw["y"].buf
-                if not any(t not in drop and yb in self.ops[t][1] for t in range(j + 1, n)):
-                    kw["flags"] |= L.NO_F32_OUT
-        self.n_fused_quants = len(drop)
-        self.ops = [op for i, op in enumerate(self.ops) if i not in drop]
+    def _fold_quant(self, i, kw, marks):
+        """A quant whose input is the whole output of one MXFP8 conv, the tensor's only writer (VIDC_MXFP8_OUT: its epilogue writes the
+        image).  Every other producer -- the max-pool, an upsample, Winograd outputs, the stem, a conv of another precision, several
+        producers of one tensor, a channel slice -- is followed by the stand-alone quant launch."""
+        fmt, xs = IMAGE_FORMATS["quant"], kw["x"]
+        writers = [t for t in range(i) if xs.buf in self.ops[t][2]]
+        if len(writers) != 1 or self.ops[writers[0]][0] != "conv":
+            return False
+        pk = self.ops[writers[0]][3]
+        y = pk["y"]
+        if FORMATS[pk["precision"]] is not fmt or pk.get(fmt.out_key) is not None or y.buf != xs.buf or \
+                (y.ch_off, y.C, y.G, y.ld) != (xs.ch_off, xs.C, xs.G, xs.ld) or y.ch_off != 0 or y.ld != y.C * y.G:
+            return False
+        self._attach(writers[0], fmt, kw["y"])
+        return True
 
-    def _fuse_casts(self):
-        """A cast op whose input is the whole output of one VIDC_PREC_BF16 conv -- the last writer of the tensor before the cast -- is folded
-        into that conv (VIDC_BF16_OUT: its epilogue writes the image); when nothing else reads the fp32 result the conv does not store it
-        (VIDC_NO_F32_OUT; the output of a Bottleneck's last conv is the next block's residual and keeps its store).  Every other producer --
-        the max-pool, an upsample, the stem, a conv of another precision, producers of channel slices of a concat buffer -- is followed by
-        the stand-alone cast launch."""
+    def _fold_cast(self, i, kw, marks):
+        """A cast whose input is the whole output of one VIDC_PREC_BF16 conv, the last writer of the tensor before the cast and in the
+        same segment (VIDC_BF16_OUT: its epilogue writes the image); not a Winograd GEMM.  Every other producer -- the max-pool, an
+        upsample, the stem, a conv of another precision, producers of channel slices of a concat buffer -- is followed by the stand-alone
+        cast launch."""
+        fmt, xs = IMAGE_FORMATS["cast"], kw["x"]
+        j = self._last_writer(i, xs.buf)
+        if j is None or self.ops[j][0] != "conv":
+            return False
+        pk = self.ops[j][3]
+        y = pk["y"]
+        if FORMATS[pk["precision"]] is not fmt or pk.get(fmt.out_key) is not None or pk.get("wino") or y.buf != xs.buf or \
+                (y.ch_off, y.C * y.G, y.ld) != (xs.ch_off, xs.C * xs.G, xs.ld) or y.ch_off != 0 or y.ld != y.C * y.G or \
+                (y.B, y.H, y.W) != (xs.B, xs.H, xs.W) or self._cut_between(marks, j, i):
+            return False
+        self._attach(j, fmt, kw["y"])
+        return True
+
+    def _fuse_images(self):
+        """An image op (split / quant / cast) is folded into the producer(s) of its input where the format's rule (_fold_<kind>) allows:
+        their epilogues write the image.  A producer whose fp32 result nobody else reads then does not store it at all (VIDC_NO_F32_OUT,
+        VIDC_UP_NO_F32_OUT, y = NULL; the output of a Bottleneck's last conv is the next block's residual and keeps its store)."""
+        marks = {id(mk) for mk in self._cut_markers}
         n = len(self.ops)
-        drop = set()
+        order = list(IMAGE_FORMATS)
+        drop = {}                    # index of a folded image op -> the place of its format in the fold order
         for i, (kind, _r, _w, kw) in enumerate(self.ops):
-            if kind != "cast":
-                continue
-            xs = kw["x"]
-            j = next((t for t in range(i - 1, -1, -1) if xs.buf in self.ops[t][2]), None)
-            if j is None or self.ops[j][0] != "conv":
-                continue
-            pk = self.ops[j][3]
-            y = pk["y"]
-            if pk["precision"] != L.PREC_BF16 or pk.get("bf16_out") is not None or pk.get("wino") or y.buf != xs.buf or \
-                    (y.ch_off, y.C * y.G, y.ld) != (xs.ch_off, xs.C * xs.G, xs.ld) or y.ch_off != 0 or y.ld != y.C * y.G or \
-                    (y.B, y.H, y.W) != (xs.B, xs.H, xs.W):
-                continue
-            if any(id(self.ops[t]) in {id(mk) for mk in self._cut_markers} for t in range(j, i)):      # (a segment boundary in between: the
-                continue                                                                                 #  image must not depend on which segments ran)
-            pk["bf16_out"] = kw["y"]
-            pk["flags"] |= L.BF16_OUT
-            self.ops[j][2].append(kw["y"].buf)
-            drop.add(i)
+            if kind in IMAGE_FORMATS and getattr(self, "_fold_" + kind)(i, kw, marks):
+                drop[i] = order.index(kind)
         for j, (kind, _r, _w, kw) in enumerate(self.ops):
-            if kind == "conv" and kw.get("bf16_out") is not None and kw["y"].buf not in self.pinned:
-                yb = kw["y"].buf
-                if not any(t not in drop and yb in self.ops[t][1] for t in range(j + 1, n)):
+            place = next((k for k, fmt in enumerate(IMAGE_FORMATS.values()) if kw.get(fmt.out_key) is not None), None)
+            if place is None or kw["y"].buf in self.pinned:
+                continue
+            # A later writer of the same buffer that accumulates into it needs the fp32 values too (reads cover that); a later plain
+            # writer of ANOTHER slice of the buffer (stem groups) does not.  The formats fold one after the other -- all splits, then
+            # all quants, then all casts -- so a folded image op of a LATER format still counts as a reader of this producer's result.
+            yb = kw["y"].buf
+            if not any(yb in self.ops[t][1] and drop.get(t, len(order)) > place for t in range(j + 1, n)):
+                if kind in ("conv", "wino_out"):
                     kw["flags"] |= L.NO_F32_OUT
-        self.n_fused_casts = len(drop)
+                elif kind == "upsample":
+                    kw["flags"] |= L.UP_NO_F32_OUT
+                else:
+                    kw["no_f32"] = True
+        self.n_fused_splits, self.n_fused_quants, self.n_fused_casts = (sum(1 for v in drop.values() if v == k) for k in range(len(order)))
         self.ops = [op for i, op in enumerate(self.ops) if i not in drop]
 
     def _fuse_warp_into_stem(self):
         """A stem conv whose input is the output of a forward warp that nothing else reads gathers its input through the warp itself
         (vidc_stem_conv3x3s2_warped: the tap sets of warp_fwd_kernel, bit for bit) and the warp launch + the warped image go away
         (VERDICT r4 item 9).  Not when the warped image has another reader (the use_mask branch, surface_normal.py:150-162) or is an output."""
+        marks = {id(mk) for mk in self._cut_markers}
         drop = set()
         for i, (kind, reads, _w, kw) in enumerate(self.ops):
             if kind != "stem" or kw["x"].C != 3:
                 continue
             xb = kw["x"].buf
-            j = next((t for t in range(i - 1, -1, -1) if xb in self.ops[t][2]), None)
+            j = self._last_writer(i, xb)
             if j is None or self.ops[j][0] != "warp_fwd" or xb in self.pinned:
                 continue
             if any(t != i and t not in drop and xb in self.ops[t][1] for t in range(len(self.ops))):
                 continue
-            if any(id(self.ops[t]) in {id(mk) for mk in self._cut_markers} for t in range(j, i)):      # (a segment boundary in between)
+            if self._cut_between(marks, j, i):
                 continue
             wkw = self.ops[j][3]
             kw["warp"] = {"x": wkw["x"], "p": wkw["p"], "intr": wkw["intr"], "ac": wkw["ac"]}
             self.ops[i] = (kind, [b for b in reads if b != xb] + [wkw["x"].buf, wkw["p"].buf], _w, kw)
             drop.add(j)
-        if drop:
-            self._cut_markers = [mk for mk in self._cut_markers]      # (markers are op identities: the dropped warp ops are never markers, checked above)
-            self.ops = [op for t, op in enumerate(self.ops) if t not in drop]
+        self.ops = [op for t, op in enumerate(self.ops) if t not in drop]      # (the dropped warp ops are never cut markers, checked above)
         self.n_fused_warps = len(drop)
 
-    def _conv_desc(self, kw, addr, dry_run):
+    def _conv_desc(self, kw, dry_run):
         """The vidc_conv_desc of a recorded conv (L.conv_desc / L.gemm_desc) with its tiling, and the op's display name."""
         x, y, keys, f = kw["x"], kw["y"], kw["keys"], kw["flags"]
         co, ci, kh, kwid, Ho, Wo = kw["geom"]
         prec, wm, wf, sig = kw["precision"], kw.get("wino", 0), kw.get("wino_fused", 0), kw["sig"]
+
+        def addr(t):
+            return self._addr(t) or None
         if wm:          # (m+2)^2 transform-domain GEMMs per group of the layer, identity epilogue shared by all of them
             wp = self.ws.packed_winograd(list(keys), wm, dry_run, prec)
             s1, b1 = self.ws.identity_affine(co, wp.device)
@@ -797,14 +814,13 @@ class Program:
             wp = self.ws.packed_winograd_fused(list(keys), dry_run) if wf else self.ws.packed(list(keys), dry_run, prec)
             s1, b1 = self.ws.affine(list(keys), list(kw["bn"]) if kw["bn"] is not None else None)
             s2, b2 = self.ws.affine([None] * len(keys), list(kw["bn2"])) if kw["bn2"] is not None else (None, None)
-            r, so, mo, bo = kw["residual"], kw.get("split_out"), kw.get("mx_out"), kw.get("bf16_out")
+            r = kw["residual"]
             d = L.conv_desc(x.B, x.H, x.W, ci, co, kh, kwid, kw["stride"], kw["pad"], kw["dilation"], len(keys), Ho, Wo, x.ld, y.ld, prec,
                             x=addr(x), w=wp.data_ptr(), y=addr(y), scale1=s1.data_ptr(), shift1=b1.data_ptr(),
                             scale2=s2.data_ptr() if s2 is not None else None, shift2=b2.data_ptr() if b2 is not None else None,
-                            relu1=f & L.RELU1, relu2=f & L.RELU2, residual=addr(r) if r is not None else None, ldr=r.ld if r is not None else None,
-                            relu3=f & L.RELU3, accumulate=f & L.ACCUM, split_out=addr(so) if so is not None else None,
-                            mx_out=addr(mo) if mo is not None else None, bf16_out=addr(bo) if bo is not None else None,
-                            no_f32_out=f & L.NO_F32_OUT, wino_fused=bool(wf))
+                            relu1=f & L.RELU1, relu2=f & L.RELU2, residual=addr(r), ldr=r.ld if r is not None else None,
+                            relu3=f & L.RELU3, accumulate=f & L.ACCUM, no_f32_out=f & L.NO_F32_OUT, wino_fused=bool(wf),
+                            **{fmt.out_key: addr(kw.get(fmt.out_key)) for fmt in IMAGE_FORMATS.values()})
         self._keep += [t for t in (wp, s1, b1, s2, b2) if t is not None]
         if prec == L.PREC_MXFP8:        # no measured MXFP8 entries: the planner's tiling
             L.plan(d)
@@ -817,8 +833,7 @@ class Program:
             ent = tuning_table().get(sig)
             L.plan(d, None if ent is None else (ent[0], ent[1]) if len(ent) < 5 or prec == ent[2] else (ent[3], ent[4]))
         form = "@wino4f" if wf else ("@wino%d" % wm if wm else "")
-        pname = {L.PREC_FP32: "fp32", L.PREC_BF16X3: "bf16x3", L.PREC_BF16: "bf16", L.PREC_MXFP8: "mxfp8"}[prec]
-        return d, "conv:%s%s:%s:sk%d:%s %s flags=0x%x" % (keys[0], form, L.TILE_NAMES[d.tile], d.splitk, pname, sig, d.flags)
+        return d, "conv:%s%s:%s:sk%d:%s %s flags=0x%x" % (keys[0], form, L.TILE_NAMES[d.tile], d.splitk, FORMATS[prec].name, sig, d.flags)
 
     def _plan_buffers(self):
         n = len(self.buf_elems)
@@ -858,6 +873,108 @@ class Program:
                 free.append((storage[b].numel(), storage[b]))
         return storage
 
+    # ---- lowering: _lower_<kind>(g, kw) fills the generic arguments g of the recorded op kw and returns its display name ---------------
+    def _addr(self, t, extra=0):
+        """Device address of the program tensor t (+ `extra` of its channels); 0 for no tensor."""
+        return 0 if t is None else self.storage[t.buf].data_ptr() + t.esz * (t.ch_off + extra)
+
+    def _lower_image(self, g, kw, fmt):
+        """split / quant / cast: 64-bit row count, the channels of a row, the row stride of x, and the groups of a format that keeps them as planes."""
+        x = kw["x"]
+        rows, dims = x.B * x.H * x.W, ((x.C * x.G,) if fmt.folded else (x.C, x.G))
+        _args(g, (self._addr(x), self._addr(kw["y"])), (rows & 0xFFFFFFFF, rows >> 32, dims[0], x.ld) + dims[1:])
+        return "%s:%s" % (fmt.kind, "x".join("%d" % v for v in (rows,) + dims))
+
+    def _lower_stem(self, g, kw):
+        x, y, wf = kw["x"], kw["y"], kw.get("warp")
+        w = self.ws.raw(kw["key"] + ".weight").contiguous()
+        self._keep.append(w)
+        _args(g, (self._addr(x), w.data_ptr(), 0 if kw.get("no_f32") else self._addr(y, kw["g"] * y.C), self._addr(kw.get("split_out"))),
+              (x.B, x.C, x.H, x.W, y.C, y.ld, int(kw["relu"]), kw["g"] * y.C))
+        if wf is not None:             # the input is gathered through the forward warp: x = the unwarped image, p[4] = the parameter records
+            g.p[0], g.p[4] = self._addr(wf["x"]), self._addr(wf["p"])
+            g.f[0], g.f[1], g.i[8] = wf["intr"].cx, wf["intr"].cy, wf["ac"]
+        return "stem:" + kw["key"] + ("+warp" if wf is not None else "")
+
+    def _lower_maxpool(self, g, kw):
+        x, y = kw["x"], kw["y"]
+        _args(g, (self._addr(x), 0 if kw.get("no_f32") else self._addr(y), self._addr(kw.get("split_out"))), (x.B, x.H, x.W, x.C * x.G, x.ld, y.ld))
+        return "maxpool"
+
+    def _lower_upsample(self, g, kw):
+        x, y = kw["x"], kw["y"]
+        _args(g, (self._addr(x), self._addr(y), self._addr(kw.get("split_out"))),
+              (x.B, x.H, x.W, (x.C if kw.get("sum_groups") else x.C * x.G), x.ld, y.H, y.W, y.ld, kw["flags"]))
+        return "upsample:%dx%dx%d->%dx%d" % (x.H, x.W, x.C * x.G, y.H, y.W)
+
+    def _lower_head(self, g, kw):
+        x, low, y = kw["x"], kw["low"], kw["y"]
+        w = self.ws.raw(kw["key"] + ".weight").reshape(y.C, -1).contiguous()
+        b = self.ws.raw(kw["key"] + ".bias").contiguous()
+        self._keep += [w, b]
+        _args(g, (self._addr(x), w.data_ptr(), b.data_ptr(), self._addr(low), self._addr(y)),
+              (x.B, x.H, x.W, x.C * x.G, x.ld, y.C, kw["pad"], y.H, y.W, int(kw["relu"])))
+        return "head:" + kw["key"]
+
+    def _lower_warp_params(self, g, kw):
+        it = kw["intr"]
+        _args(g, [self._addr(kw[k]) for k in ("g", "a", "kinv", "p")], (self.B, it.W, it.H), (it.fx, it.fy, it.cx, it.cy))
+        return "warp_params"
+
+    def _lower_warp_fwd(self, g, kw):
+        x, it = kw["x"], kw["intr"]
+        _args(g, (self._addr(x), self._addr(kw["p"]), self._addr(kw["y"])), (x.B, x.C, x.H, x.W, kw["ac"]), (it.cx, it.cy))
+        return "warp_fwd"
+
+    def _lower_warp_inv(self, g, kw):
+        x, it = kw["x"], kw["intr"]
+        _args(g, (self._addr(x), self._addr(kw["p"]), self._addr(kw["y"])), (x.B, x.H, x.W, kw["ac"], kw["norm"]), (it.cx, it.cy))
+        return "warp_inv_rot_norm"
+
+    def _lower_avgpool(self, g, kw):
+        x, y = kw["x"], kw["y"]
+        _args(g, (self._addr(x), self._addr(y)), (x.B, x.H, x.W, x.C * x.G, x.ld) + tuple(kw["geom"]) + (y.ld,))
+        return "avgpool"
+
+    def _lower_normalize(self, g, kw):
+        x = kw["x"]
+        _args(g, (self._addr(x), self._addr(kw["y"])), (x.B, x.C, x.H * x.W))
+        return "normalize"
+
+    def _lower_det_im2col(self, g, kw):
+        _args(g, (self._addr(kw["x"]), self._addr(kw["y"])), (kw["x"].B,) + tuple(kw["geom"]), kw["mean"])
+        return "det_im2col"
+
+    def _lower_mask(self, g, kw):
+        x, y, im = kw["x"], kw["y"], kw["image"]
+        _args(g, (self._addr(x), self._addr(im), self._addr(y)), (x.B, x.H, x.W, x.C * x.G, x.ld, y.ld, im.H, im.W))
+        return "mask_scale"
+
+    def _lower_wino_in(self, g, kw):
+        x, v = kw["x"], kw["v"]
+        _args(g, (self._addr(x), self._addr(v)), (x.B, x.H, x.W, x.C * x.G, x.ld, kw["cin"], kw["m"], kw["split"], v.ld))
+        return "wino_in:F%d:%dx%dx%d" % (kw["m"], x.H, x.W, x.C * x.G)
+
+    def _lower_wino_out(self, g, kw):
+        mm, y, keys = kw["mm"], kw["y"], kw["keys"]
+        s1, b1 = self.ws.affine(list(keys), list(kw["bn"]) if kw["bn"] is not None else None)
+        s2, b2 = self.ws.affine([None] * len(keys), list(kw["bn2"])) if kw["bn2"] is not None else (None, None)
+        self._keep += [t for t in (s1, b1, s2, b2) if t is not None]
+        _args(g, (self._addr(mm), 0 if kw["flags"] & L.NO_F32_OUT else self._addr(y), self._addr(kw.get("split_out")), s1.data_ptr(), b1.data_ptr(),
+                  L.ptr(s2) or 0, L.ptr(b2) or 0), (y.B, y.H, y.W, y.C * y.G, kw["cout"], y.ld, kw["m"], kw["flags"], mm.ld))
+        return "wino_out:F%d:%dx%dx%d" % (kw["m"], y.H, y.W, y.C * y.G)
+
+    def _lower_nearest2x(self, g, kw):
+        x, y = kw["x"], kw["y"]
+        _args(g, (self._addr(x), self._addr(y)), (x.B, x.H, x.W, x.C * x.G, x.ld, y.ld))
+        return "nearest2x"
+
+    def _lower_copy(self, g, kw):
+        src, dst = kw["src"], kw["dst"]
+        nbytes = min(self.buf_elems[src.buf], self.buf_elems[dst.buf]) * 4
+        _args(g, (self._addr(src), self._addr(dst)), (nbytes & 0xFFFFFFFF, nbytes >> 32))
+        return "copy"
+
     def finalize(self, dry_run=False):
         """Plans buffers and builds the C op array.  dry_run=True stops before any HIP call (host-logic tests on CPU)."""
         lib = L.lib()
@@ -865,191 +982,31 @@ class Program:
         # frames round 5 saw with it were an execution defect of a packed-fp32 instruction beside bf16 MFMAs, not this kernel's loads: DESIGN 4.5.)
         if os.environ.get("VIDC_FUSE_WARP", "0") == "1":
             self._fuse_warp_into_stem()
-        else:
-            self.n_fused_warps = 0
         if os.environ.get("VIDC_FUSE_SPLIT", "1") == "1":
-            self._fuse_splits()
-            self._fuse_quants()
-            self._fuse_casts()
+            self._fuse_images()
         self.cuts = [next(i for i, op in enumerate(self.ops) if op is mk) + 1 for mk in self._cut_markers]
         assert len(self.cuts) < L.MAX_SEGMENTS and self.cuts == sorted(set(self.cuts))
-        storage = self._plan_buffers()
-        self.storage = storage
-        self.bytes_allocated = sum({t.data_ptr(): t.numel() * 4 for t in storage if t is not None}.values())
-
-        def addr(t, extra=0):
-            return storage[t.buf].data_ptr() + t.esz * (t.ch_off + extra)
-
-        ops = (L.Op * sum(1 for _ in self.ops))()
+        self.storage = self._plan_buffers()
+        self.bytes_allocated = sum({t.data_ptr(): t.numel() * 4 for t in self.storage if t is not None}.values())
+        ops = (L.Op * len(self.ops))()
         ws_need = {}
         ws_ops = []              # the convs that need a split-K workspace
         self.op_names = []
-        for i, (kind, _r, _w, kw) in enumerate(self.ops):
-            op = ops[i]
-            op.stream_id, op.wait_mask = kw["stream_id"], kw["wait_mask"]
-            g = op.u.g
+        for op, (kind, _r, _w, kw) in zip(ops, self.ops):
+            if kind not in OP_KINDS:
+                raise ValueError(kind)
+            op.kind, op.stream_id, op.wait_mask = OP_KINDS[kind], kw["stream_id"], kw["wait_mask"]
             if kind == "conv":
-                op.kind = L.OP_CONV
-                op.u.conv, name = self._conv_desc(kw, addr, dry_run)
+                op.u.conv, name = self._conv_desc(kw, dry_run)
                 need = lib.vidc_conv2d_workspace_bytes(C.byref(op.u.conv))
                 if need:
                     ws_need[op.stream_id] = max(ws_need.get(op.stream_id, 0), need)
                     ws_ops.append(op)
-                self.op_names.append(name)
-            elif kind == "stem":
-                x, y = kw["x"], kw["y"]
-                w = self.ws.raw(kw["key"] + ".weight").contiguous()
-                self._keep.append(w)
-                op.kind = L.OP_STEM
-                g.p[0], g.p[1], g.p[2] = addr(x), w.data_ptr(), (0 if kw.get("no_f32") else addr(y, kw["g"] * y.C))
-                for j, v in enumerate((x.B, x.C, x.H, x.W, y.C, y.ld, int(kw["relu"]), kw["g"] * y.C)):
-                    g.i[j] = v
-                if kw.get("split_out") is not None:
-                    g.p[3] = addr(kw["split_out"])
-                wf = kw.get("warp")
-                if wf is not None:             # the input is gathered through the forward warp: x = the unwarped image, p[4] = the parameter records
-                    g.p[0], g.p[4] = addr(wf["x"]), addr(wf["p"])
-                    g.f[0], g.f[1], g.i[8] = wf["intr"].cx, wf["intr"].cy, wf["ac"]
-                self.op_names.append("stem:" + kw["key"] + ("+warp" if wf is not None else ""))
-            elif kind == "maxpool":
-                x, y = kw["x"], kw["y"]
-                op.kind = L.OP_MAXPOOL
-                g.p[0], g.p[1] = addr(x), (0 if kw.get("no_f32") else addr(y))
-                for j, v in enumerate((x.B, x.H, x.W, x.C * x.G, x.ld, y.ld)):
-                    g.i[j] = v
-                if kw.get("split_out") is not None:
-                    g.p[2] = addr(kw["split_out"])
-                self.op_names.append("maxpool")
-            elif kind == "upsample":
-                x, y = kw["x"], kw["y"]
-                op.kind = L.OP_UPSAMPLE
-                g.p[0], g.p[1] = addr(x), addr(y)
-                for j, v in enumerate((x.B, x.H, x.W, (x.C if kw.get("sum_groups") else x.C * x.G), x.ld, y.H, y.W, y.ld, kw["flags"])):
-                    g.i[j] = v
-                if kw.get("split_out") is not None:
-                    g.p[2] = addr(kw["split_out"])
-                self.op_names.append("upsample:%dx%dx%d->%dx%d" % (x.H, x.W, x.C * x.G, y.H, y.W))
-            elif kind == "head":
-                x, low, y = kw["x"], kw["low"], kw["y"]
-                w = self.ws.raw(kw["key"] + ".weight").reshape(y.C, -1).contiguous()
-                b = self.ws.raw(kw["key"] + ".bias").contiguous()
-                self._keep += [w, b]
-                op.kind = L.OP_HEAD
-                g.p[0], g.p[1], g.p[2], g.p[3], g.p[4] = addr(x), w.data_ptr(), b.data_ptr(), addr(low), addr(y)
-                for j, v in enumerate((x.B, x.H, x.W, x.C * x.G, x.ld, y.C, kw["pad"], y.H, y.W, int(kw["relu"]))):
-                    g.i[j] = v
-                self.op_names.append("head:" + kw["key"])
-            elif kind == "warp_params":
-                it = kw["intr"]
-                op.kind = L.OP_WARP_PARAMS
-                g.p[0], g.p[1], g.p[2], g.p[3] = addr(kw["g"]), addr(kw["a"]), addr(kw["kinv"]), addr(kw["p"])
-                g.i[0], g.i[1], g.i[2] = self.B, it.W, it.H
-                g.f[0], g.f[1], g.f[2], g.f[3] = it.fx, it.fy, it.cx, it.cy
-                self.op_names.append("warp_params")
-            elif kind == "warp_fwd":
-                x, it = kw["x"], kw["intr"]
-                op.kind = L.OP_WARP_FWD
-                g.p[0], g.p[1], g.p[2] = addr(x), addr(kw["p"]), addr(kw["y"])
-                for j, v in enumerate((x.B, x.C, x.H, x.W, kw["ac"])):
-                    g.i[j] = v
-                g.f[0], g.f[1] = it.cx, it.cy
-                self.op_names.append("warp_fwd")
-            elif kind == "warp_inv":
-                x, it = kw["x"], kw["intr"]
-                op.kind = L.OP_WARP_INV
-                g.p[0], g.p[1], g.p[2] = addr(x), addr(kw["p"]), addr(kw["y"])
-                for j, v in enumerate((x.B, x.H, x.W, kw["ac"], kw["norm"])):
-                    g.i[j] = v
-                g.f[0], g.f[1] = it.cx, it.cy
-                self.op_names.append("warp_inv_rot_norm")
-            elif kind == "split":
-                x, y = kw["x"], kw["y"]
-                rows = x.B * x.H * x.W
-                op.kind = L.OP_SPLIT
-                g.p[0], g.p[1] = addr(x), addr(y)
-                g.i[0], g.i[1], g.i[2], g.i[3] = rows & 0xFFFFFFFF, rows >> 32, x.C * x.G, x.ld
-                self.op_names.append("split:%dx%d" % (rows, x.C * x.G))
-            elif kind == "quant":
-                x, y = kw["x"], kw["y"]
-                rows = x.B * x.H * x.W
-                op.kind = L.OP_QUANT
-                g.p[0], g.p[1] = addr(x), addr(y)
-                g.i[0], g.i[1], g.i[2], g.i[3], g.i[4] = rows & 0xFFFFFFFF, rows >> 32, x.C, x.ld, x.G
-                self.op_names.append("quant:%dx%dx%d" % (rows, x.C, x.G))
-            elif kind == "cast":
-                x, y = kw["x"], kw["y"]
-                rows = x.B * x.H * x.W
-                op.kind = L.OP_CAST
-                g.p[0], g.p[1] = addr(x), addr(y)
-                g.i[0], g.i[1], g.i[2], g.i[3] = rows & 0xFFFFFFFF, rows >> 32, x.C * x.G, x.ld
-                self.op_names.append("cast:%dx%d" % (rows, x.C * x.G))
-            elif kind == "avgpool":
-                x, y = kw["x"], kw["y"]
-                op.kind = L.OP_AVGPOOL
-                g.p[0], g.p[1] = addr(x), addr(y)
-                for j, v in enumerate((x.B, x.H, x.W, x.C * x.G, x.ld) + tuple(kw["geom"]) + (y.ld,)):
-                    g.i[j] = v
-                self.op_names.append("avgpool")
-            elif kind == "normalize":
-                x, y = kw["x"], kw["y"]
-                op.kind = L.OP_NORMALIZE
-                g.p[0], g.p[1] = addr(x), addr(y)
-                g.i[0], g.i[1], g.i[2] = x.B, x.C, x.H * x.W
-                self.op_names.append("normalize")
-            elif kind == "det_im2col":
-                x, y = kw["x"], kw["y"]
-                op.kind = L.OP_DET_IM2COL
-                g.p[0], g.p[1] = addr(x), addr(y)
-                for j, v in enumerate((x.B,) + tuple(kw["geom"])):
-                    g.i[j] = v
-                g.f[0], g.f[1], g.f[2] = kw["mean"]
-                self.op_names.append("det_im2col")
-            elif kind == "mask":
-                x, y, im = kw["x"], kw["y"], kw["image"]
-                op.kind = L.OP_MASK
-                g.p[0], g.p[1], g.p[2] = addr(x), addr(im), addr(y)
-                for j, v in enumerate((x.B, x.H, x.W, x.C * x.G, x.ld, y.ld, im.H, im.W)):
-                    g.i[j] = v
-                self.op_names.append("mask_scale")
-            elif kind == "wino_in":
-                x, v = kw["x"], kw["v"]
-                op.kind = L.OP_WINO_IN
-                g.p[0], g.p[1] = addr(x), addr(v)
-                for j, val in enumerate((x.B, x.H, x.W, x.C * x.G, x.ld, kw["cin"], kw["m"], kw["split"], v.ld)):
-                    g.i[j] = val
-                self.op_names.append("wino_in:F%d:%dx%dx%d" % (kw["m"], x.H, x.W, x.C * x.G))
-            elif kind == "wino_out":
-                mm, y = kw["mm"], kw["y"]
-                keys = kw["keys"]
-                s1, b1 = self.ws.affine(list(keys), list(kw["bn"]) if kw["bn"] is not None else None)
-                self._keep += [s1, b1]
-                op.kind = L.OP_WINO_OUT
-                g.p[0], g.p[1], g.p[3], g.p[4] = addr(mm), (0 if kw["flags"] & L.NO_F32_OUT else addr(y)), s1.data_ptr(), b1.data_ptr()
-                if kw.get("split_out") is not None:
-                    g.p[2] = addr(kw["split_out"])
-                if kw["bn2"] is not None:
-                    s2, b2 = self.ws.affine([None] * len(keys), list(kw["bn2"]))
-                    g.p[5], g.p[6] = s2.data_ptr(), b2.data_ptr()
-                    self._keep += [s2, b2]
-                for j, val in enumerate((y.B, y.H, y.W, y.C * y.G, kw["cout"], y.ld, kw["m"], kw["flags"], mm.ld)):
-                    g.i[j] = val
-                self.op_names.append("wino_out:F%d:%dx%dx%d" % (kw["m"], y.H, y.W, y.C * y.G))
-            elif kind == "nearest2x":
-                x, y = kw["x"], kw["y"]
-                op.kind = L.OP_NEAREST2X
-                g.p[0], g.p[1] = addr(x), addr(y)
-                for j, v in enumerate((x.B, x.H, x.W, x.C * x.G, x.ld, y.ld)):
-                    g.i[j] = v
-                self.op_names.append("nearest2x")
-            elif kind == "copy":
-                src, dst = kw["src"], kw["dst"]
-                nbytes = min(self.buf_elems[src.buf], self.buf_elems[dst.buf]) * 4
-                op.kind = L.OP_COPY
-                g.p[0], g.p[1] = addr(src), addr(dst)
-                g.i[0], g.i[1] = nbytes & 0xFFFFFFFF, nbytes >> 32
-                self.op_names.append("copy")
+            elif kind in IMAGE_FORMATS:
+                name = self._lower_image(op.u.g, kw, IMAGE_FORMATS[kind])
             else:
-                raise ValueError(kind)
+                name = getattr(self, "_lower_" + kind)(op.u.g, kw)
+            self.op_names.append(name)
         # split-K workspaces (one per stream id so concurrent convs never share partials); zeroed once: their heads hold the
         # per-tile ticket counters of the fused split-K reduction, which every launch leaves at zero (include/vidc.h)
         self.workspaces = {sid: torch.zeros(nb // 4 + 4, dtype=torch.float32, device=self.device) for sid, nb in ws_need.items()}
@@ -1127,7 +1084,7 @@ class Program:
                 continue
             grouped = (kind in ("conv", "wino_out") and len(kw["keys"]) == groups) or (kind in ("maxpool", "wino_in") and kw["x"].G == groups)
             # (a split launch of its own -- VIDC_FUSE_SPLIT=0 -- over a grouped tensor has no row stride for its image: it runs whole in every variant)
-            if grouped or keep_ungrouped or (kind in ("split", "quant", "cast") and kw["x"].G == groups):
+            if grouped or keep_ungrouped or (kind in IMAGE_FORMATS and kw["x"].G == groups):
                 picked.append(i)
         ops = (L.Op * len(picked))()
         for j, i in enumerate(picked):
@@ -1136,12 +1093,11 @@ class Program:
             if kind == "conv" and len(kw["keys"]) == groups:
                 d = ops[j].u.conv
                 a2 = (kw["wino"] + 2) ** 2 if kw.get("wino") else 1        # Winograd GEMMs: (m+2)^2 launch groups per group of the layer
-                for field, gs in (("x", d.x_gs), ("w", d.w_gs), ("y", d.y_gs), ("scale1", d.p_gs), ("shift1", d.p_gs), ("scale2", d.p_gs),
-                                  ("shift2", d.p_gs), ("residual", d.r_gs), ("y_split", d.y_gs)):     # every operand is 4 bytes per element
-                    v = getattr(d, field)                                                              # (a split-bf16 unit = 32 x (hi, lo))
-                    if field == "y_split" and d.flags & L.MXFP8_OUT:                                  # (MXFP8 image: one plane pair per group)
-                        gs = d.B * d.Ho * d.Wo * d.Cout * 33 // 128
-                    esz = 2 if field == "y_split" and d.flags & L.BF16_OUT else 4                     # (bf16 image: two bytes per channel)
+                strides = [("x", d.x_gs, 4), ("w", d.w_gs, 4), ("y", d.y_gs, 4), ("scale1", d.p_gs, 4), ("shift1", d.p_gs, 4), ("scale2", d.p_gs, 4),
+                           ("shift2", d.p_gs, 4), ("residual", d.r_gs, 4)]                           # these operands are 4 bytes per element
+                strides += [("y_split", fmt.out_gs(d), fmt.out_esz) for fmt in IMAGE_FORMATS.values() if d.flags & fmt.out_flag]
+                for field, gs, esz in strides:
+                    v = getattr(d, field)
                     if v:
                         setattr(d, field, v + esz * g_lo * gs * a2)
                 d.groups = (g_hi - g_lo) * a2

@@ -84,13 +84,8 @@ def build_frame_program(sn, dc, B, H, W, device, dry_run=False, weights=None):
     xw = prog.warp_fwd(x, params, wp, wp.align_corners)
     levels = sn.resnet_pyramids.emit(prog, [xw, img, nrm, dep],
                                      engine.K(("sn/resnet_pyramids.", "dc/resnet_rgb.", "dc/resnet_normal.", "dc/resnet_depth.")))
-    if prog.mode in ("mixed", "mxfp8"):
-        for t in levels:             # ONE split image per level, written by the producing conv's epilogue (a split launch behind an MXFP8
-            prog.split(t)            # producer); the next pyramid stage and both (bf16x3) decoders read (channel slices of) it
-    elif prog.mode == "bf16":
-        for t in levels:             # the same in the bf16 mode: ONE bf16 image per level (the producing conv's VIDC_BF16_OUT), whose channel
-            if (t.C * t.G) % 64 == 0:            # slices the decoders read (group offsets are multiples of 64 channels)
-                prog.cast(t)
+    for t in levels:                 # ONE image per level in the mode's format: the next pyramid stage and both decoders read (channel
+        prog.level_image(t)          # slices of) it
     sn_levels = [T(t.buf, t.B, t.H, t.W, t.C, 1, t.ld, t.ch_off) for t in levels]
     dc_levels = [T(t.buf, t.B, t.H, t.W, 3 * t.C, 1, t.ld, t.ch_off + t.C) for t in levels]
     if sn.use_mask:                  # surface_normal.py:150-162
