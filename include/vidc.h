@@ -308,6 +308,14 @@ int vidc_upsample_bilinear_ac(const float* x, float* y, int B, int h, int w, int
 int vidc_avgpool2d(const float* x, float* y, int B, int H, int W, int C, int ldx, int kh, int kw, int sh, int sw, int ph, int pw, int ldy,
                    vidc_stream_t stream);
 
+/* Backward of vidc_avgpool2d: dy NHWC [B][Ho][Wo][ldy] -> dx NHWC [B][H][W][ldx], the gradient of the pool's input (FullImageEncoder's
+ * AvgPool2d(8, 8, padding=(1, 0)), networks/surface_normal_dorn.py:10, when the encoder is trained).  The same (kh, kw, sh, sw, ph, pw), ldx / ldy
+ * and floor output size as the forward; count_include_pad=True, so every window divides by kh*kw.  Gather form: dx[b,y,x,c] = the sum of
+ * dy[b,oy,ox,c] / (kh*kw) over the windows that contain (y, x), oy then ox ascending -- overlapping windows add up, pixels no window covers get
+ * 0, and the result is bit-identical from run to run.  C, ldx, ldy multiples of 4; dy and dx 16-byte aligned.  (csrc/train.hip) */
+int vidc_avgpool2d_backward(const float* dy, float* dx, int B, int H, int W, int C, int ldx, int kh, int kw, int sh, int sw, int ph, int pw, int ldy,
+                            vidc_stream_t stream);
+
 /* torch.nn.functional.normalize(x, dim=1) on NCHW [B][C][HW] (networks/surface_normal_dorn.py:154). */
 int vidc_normalize_nchw(const float* x, float* y, int B, int C, int HW, vidc_stream_t stream);
 
@@ -655,6 +663,15 @@ int vidc_zero_stuff(const float* dy, float* z, int B, int Ho, int Wo, int C, int
 size_t vidc_conv_wgrad_scratch_bytes(int B, int Ho, int Wo, int Cout, int Cin, int KH, int KW);
 int vidc_conv_wgrad(const float* dy, const float* x, float* dw_oihw, int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout, int lddy,
                     int KH, int KW, int stride, int pad, void* scratch, vidc_stream_t stream);
+/* vidc_conv_wgrad of a DILATED conv (the ASPP branches Conv2d(2048, 512, 3, padding=d, dilation=d), d = 6 / 12 / 18,
+ * networks/surface_normal_dorn.py:45-68): tap (kh, kw) reads x[oy*stride - pad + kh*dilation, ox*stride - pad + kw*dilation], zero outside the image;
+ * Ho = (H + 2 pad - dilation (KH - 1) - 1) / stride + 1, Wo likewise.  The same kernel, the same fixed-order reduction (no floating-point atomics)
+ * and the same constraints as vidc_conv_wgrad; dilation = 1 gives that entry's bits.  scratch: vidc_conv_wgrad_dilated_scratch_bytes (the size does
+ * not depend on the dilation).  The DATA gradient of a dilated stride-1 conv needs no entry of its own: it is vidc_conv2d_bn_act of dY on the
+ * vidc_pack_conv_weight_dgrad weights with the same dilation and pad' = dilation (KH - 1) - pad. */
+size_t vidc_conv_wgrad_dilated_scratch_bytes(int B, int Ho, int Wo, int Cout, int Cin, int KH, int KW);
+int vidc_conv_wgrad_dilated(const float* dy, const float* x, float* dw_oihw, int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout, int lddy,
+                            int KH, int KW, int stride, int pad, int dilation, void* scratch, vidc_stream_t stream);
 /* wgrad as a GEMM on the conv kernel: dW[co][tap][ci] = sum_m dY^T[co][m] * Xt[tap*C + ci][m] is the 1x1 case of vidc_conv2d_bn_act with
  * "activations" = the rows of dY^T and "weights" = the rows of Xt (both K-contiguous, K = pixels).  vidc_im2col_transposed writes
  * xt[(tap*C + c)][m] = x[b, oy*s - p + kh, ox*s - p + kw, c] (0 outside the image and for m >= B*Ho*Wo; rows Mp long, Mp % 32 == 0);
@@ -664,6 +681,10 @@ int vidc_conv_wgrad(const float* dy, const float* x, float* dw_oihw, int B, int 
  * can be written straight into the parameter's .grad.  vidc_wgrad_permute (tap-major order): dw_oihw[co][ci][tap] = tmp[co][tap*Cin + ci]. */
 int vidc_im2col_transposed(const float* x, float* xt, int B, int H, int W, int C, int ldx, int Ho, int Wo, int KH, int KW, int stride, int pad,
                            int Mp, int split, vidc_stream_t stream);
+/* vidc_im2col_transposed for a dilated conv (networks/surface_normal_dorn.py:45-68): xt[(tap*C + c)][m] = x[b, oy*s - p + kh*dilation,
+ * ox*s - p + kw*dilation, c]; every `split` value of that entry (0, 1, 2 and + 4), the same kernels; dilation = 1 gives that entry's bits. */
+int vidc_im2col_transposed_dilated(const float* x, float* xt, int B, int H, int W, int C, int ldx, int Ho, int Wo, int KH, int KW, int stride, int pad,
+                                   int dilation, int Mp, int split, vidc_stream_t stream);
 /* The right operand of a 1x1 / stride-1 conv's weight-gradient GEMM in the plain-bf16 mode from the bf16 operand copy the forward read:
  * dense bf16 rows x[M][C] -> xt[C][Mp] (zeros for m >= M, Mp % 64 == 0, C % 8 == 0).  Same bits as vidc_im2col_transposed(split = 2) of
  * the fp32 tensor the copy was rounded from. */

@@ -194,6 +194,9 @@ SIGNATURES = {
     "vidc_conv_wgrad_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
     "vidc_conv_wgrad": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vidc_im2col_transposed": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "vidc_conv_wgrad_dilated_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+    "vidc_conv_wgrad_dilated": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "vidc_im2col_transposed_dilated": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "vidc_wgrad_permute": (C.c_int, [_vp, _vp, _i, _i, _i, _vp]),
     "vidc_transpose_bf16": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _vp]),
     "vidc_im2col_transposed_bf16": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
@@ -209,6 +212,7 @@ SIGNATURES = {
     "vidc_maxpool3x3s2": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vidc_upsample_bilinear_ac": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vidc_avgpool2d": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "vidc_avgpool2d_backward": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "vidc_normalize_nchw": (C.c_int, [_vp, _vp, _i, _i, _i, _vp]),
     "vidc_head_conv1x1_upsample": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "vidc_plane_scratch_bytes": (C.c_size_t, [_i, _i, _i]),

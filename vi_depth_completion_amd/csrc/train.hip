@@ -567,6 +567,36 @@ upsample_bwd4_kernel(const float* __restrict__ dy, float* __restrict__ dx, int B
     *reinterpret_cast<float4*>(dx + (unsigned)((b * h + ii) * w + jj) * (unsigned)lddx + c) = make_float4(acc[0], acc[1], acc[2], acc[3]);
 }
 
+// ---- nn.AvgPool2d(k, stride, padding), count_include_pad=True, backward (surface_normal_dorn.py:10), gather form -----------------------
+// Forward (pointwise.hip): y[b,oy,ox,c] = (sum of the window's pixels inside the image) / (kh*kw).  One thread owns dx[b,y,x,c..c+3] and adds
+// dy[b,oy,ox,c..c+3] / (kh*kw) over the windows that contain (y, x), oy then ox ascending: overlapping windows (stride < kernel) add up,
+// a pixel no window covers (rows / columns past the last whole window) gets 0, and the order is fixed, so the result is bit-reproducible.
+// 16-byte loads and stores along C; the kernel moves |dx| + |dy| bytes and does nothing else.
+__global__ void __launch_bounds__(TT)
+avgpool_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int B, int H, int W, int C, int lddx, int kh, int kw, int sh, int sw, int ph,
+                   int pw, int Ho, int Wo, int lddy) {
+    const int q = C >> 2;
+    const long long i = (long long)blockIdx.x * TT + threadIdx.x;
+    if (i >= (long long)B * H * W * q) return;
+    const int c = (int)(i % q) * 4;
+    long long p = i / q;
+    const int xx = (int)(p % W); p /= W;
+    const int yy = (int)(p % H);
+    const int b = (int)(p / H);
+    // window oy covers rows oy*sh - ph .. oy*sh - ph + kh - 1:  (yy + ph - kh + 1) / sh rounded up <= oy <= (yy + ph) / sh rounded down
+    const int ty = yy + ph, tx = xx + pw;
+    const int oy0 = ty >= kh ? (ty - kh + sh) / sh : 0, oy1 = min(Ho - 1, ty / sh);
+    const int ox0 = tx >= kw ? (tx - kw + sw) / sw : 0, ox1 = min(Wo - 1, tx / sw);
+    const float d = (float)(kh * kw);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int oy = oy0; oy <= oy1; ++oy)
+        for (int ox = ox0; ox <= ox1; ++ox) {
+            const float4 g = *reinterpret_cast<const float4*>(dy + ((size_t)(b * Ho + oy) * Wo + ox) * lddy + c);
+            acc.x += g.x / d; acc.y += g.y / d; acc.z += g.z / d; acc.w += g.w / d;
+        }
+    *reinterpret_cast<float4*>(dx + ((size_t)(b * H + yy) * W + xx) * lddx + c) = acc;
+}
+
 // ---- 1x1 head conv with Cout <= 4 output channels and any padding: backward ---------------------------------------------------------
 // (depth_completion.py:141-147: Conv2d(192, 1, 1, padding=1); surface_normal.py:143: Conv2d(64, 3, 1))
 // g_low: [B*Cout][h+2p][w+2p] planes (the layout of vidc_head_conv1x1_upsample's lowres); x: NHWC [B][h][w][C]; wgt: [Cout][C].
@@ -909,7 +939,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // One wave = a 64 x 64 (co, ci) register tile (2 x 2 MFMA tiles: 4 loads feed 4 MFMAs); a workgroup = 4 waves = 128 co x 128 ci.
 __global__ void __launch_bounds__(256)
 wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ x, int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout, int lddy,
-             int KH, int KW, int stride, int pad, int rows_per_chunk, float* __restrict__ partial /* [chunk][tap][Cout][Cin] */) {
+             int KH, int KW, int stride, int pad, int dil, int rows_per_chunk, float* __restrict__ partial /* [chunk][tap][Cout][Cin] */) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
     const int taps = KH * KW;
     const int ci_tiles = (Cin + 127) / 128;
@@ -941,7 +971,7 @@ wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ x, int B, i
             while (oy >= Ho) { oy -= Ho; ++b; }
             a[t][0] = a[t][1] = bv[t][0] = bv[t][1] = 0.f;
             if (m < m_hi) {
-                const int iy = oy * stride - pad + kh, ix = ox * stride - pad + kw;
+                const int iy = oy * stride - pad + kh * dil, ix = ox * stride - pad + kw * dil;      // (dil: the tap spacing of a dilated conv)
                 const bool inside = (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
                 const int xo = ((b * H + iy) * W + ix) * ldx;
 #pragma unroll
@@ -994,11 +1024,12 @@ wgrad_final_kernel(const float* __restrict__ partial, int n_chunks, int taps, in
 // the 1x1 case of conv_mfma.hip (activations = rows of dY^T, weights = rows of Xt), which runs at several times the rate of the
 // direct kernel above (LDS-tiled, split-K, fp32 or bf16x3).  This kernel builds the operands: xt[(tap*C + c)][m] = x[b, oy*s - p + kh,
 // ox*s - p + kw, c] (0 outside the image and for m >= M; rows are Mp = M rounded up to 32 long), through a 32x32 LDS transpose so that
-// both the NHWC reads and the row writes are 128-byte coalesced.  With KH = KW = 1, s = 1, p = 0 it is the transpose of dY.  split != 0 writes
+// both the NHWC reads and the row writes are 128-byte coalesced.  With KH = KW = 1, s = 1, p = 0 it is the transpose of dY.  dil: the tap
+// spacing of a dilated conv (x[.., oy*s - p + kh*dil, ox*s - p + kw*dil, ..]; 1 = the plain conv).  split != 0 writes
 // the rows in the split-bf16 operand format of the bf16x3 mode directly (vidc_split_bf16x3's layout; same bytes per row).
 __global__ void __launch_bounds__(256)
 im2col_t_kernel(const float* __restrict__ x, float* __restrict__ xt, int B, int H, int W, int C, int ldx, int Ho, int Wo, int KH, int KW, int stride,
-                int pad, int M, int Mp, int split) {
+                int pad, int dil, int M, int Mp, int split) {
     __shared__ float tile[32][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int m0 = blockIdx.x * 32, c0 = blockIdx.y * 32, tap = blockIdx.z;
@@ -1012,7 +1043,7 @@ im2col_t_kernel(const float* __restrict__ x, float* __restrict__ xt, int B, int 
         float v = 0.f;
         if (m < M && c < C) {
             const int ox = m % Wo, q = m / Wo, oy = q % Ho, b = q / Ho;
-            const int iy = oy * stride - pad + kh, ix = ox * stride - pad + kw;
+            const int iy = oy * stride - pad + kh * dil, ix = ox * stride - pad + kw * dil;
             if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = x[((size_t)(b * H + iy) * W + ix) * ldx + c];
         }
         tile[ty + 8 * r][tx] = v;
@@ -1043,7 +1074,7 @@ im2col_t_kernel(const float* __restrict__ x, float* __restrict__ xt, int B, int 
 // the 4 x 16 lanes of a wave hit 64 different banks in both phases.
 __global__ void __launch_bounds__(256)
 im2col_t64_kernel(const float* __restrict__ x, float* __restrict__ xt, int B, int H, int W, int C, int ldx, int Ho, int Wo, int KH, int KW, int stride,
-                  int pad, int M, int Mp, int split) {
+                  int pad, int dil, int M, int Mp, int split) {
     __shared__ float tile[64][65];
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int m0 = blockIdx.x * 64, c0 = blockIdx.y * 64, tap = blockIdx.z;
@@ -1057,7 +1088,7 @@ im2col_t64_kernel(const float* __restrict__ x, float* __restrict__ xt, int B, in
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (m < M && c < C) {
             const int ox = m % Wo, q = m / Wo, oy = q % Ho, b = q / Ho;
-            const int iy = oy * stride - pad + kh, ix = ox * stride - pad + kw;
+            const int iy = oy * stride - pad + kh * dil, ix = ox * stride - pad + kw * dil;
             if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = *reinterpret_cast<const float4*>(x + ((size_t)(b * H + iy) * W + ix) * ldx + c);
         }
         float* t = &tile[ty + 16 * r][tx * 4];
@@ -1415,6 +1446,23 @@ extern "C" int vidc_upsample_bilinear_ac_backward(const float* dy, float* dx, in
     return VIDC_OK;
 }
 
+extern "C" int vidc_avgpool2d_backward(const float* dy, float* dx, int B, int H, int W, int C, int ldx, int kh, int kw, int sh, int sw, int ph, int pw,
+                                       int ldy, vidc_stream_t stream) {
+    VIDC_REQUIRE(dy && dx, VIDC_ERR_NULL, "vidc_avgpool2d_backward: null pointer");
+    VIDC_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= C && ldy >= C && kh > 0 && kw > 0 && sh > 0 && sw > 0 &&
+                     ph >= 0 && pw >= 0 && (long long)H + 2ll * ph >= kh && (long long)W + 2ll * pw >= kw && (long long)H + ph < (1ll << 30) &&
+                     (long long)W + pw < (1ll << 30) && (long long)kh * kw < (1ll << 24) && (long long)B * H < (1ll << 31),
+                 VIDC_ERR_SHAPE, "vidc_avgpool2d_backward: bad shape (as vidc_avgpool2d; C, ldx, ldy multiples of 4)");
+    VIDC_REQUIRE(((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0, VIDC_ERR_SHAPE,
+                 "vidc_avgpool2d_backward: dy and dx must be 16-byte aligned");
+    const int Ho = (H + 2 * ph - kh) / sh + 1, Wo = (W + 2 * pw - kw) / sw + 1;
+    VIDC_REQUIRE((long long)B * Ho < (1ll << 31), VIDC_ERR_SHAPE, "vidc_avgpool2d_backward: bad shape");
+    hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(blocks((long long)B * H * W * (C / 4))), dim3(TT), 0, vidc::as_stream(stream), dy, dx, B, H, W, C, ldx, kh, kw,
+                       sh, sw, ph, pw, Ho, Wo, ldy);
+    VIDC_CHECK_LAUNCH("avgpool_bwd_kernel");
+    return VIDC_OK;
+}
+
 extern "C" size_t vidc_head_backward_multi_scratch_bytes(int B, int h, int w, int C, int Cout, int pad) {
     if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || Cout <= 0 || pad < 0) return 0;
     const long long M = (long long)B * h * w, n = (long long)B * (h + 2 * pad) * (w + 2 * pad);
@@ -1581,14 +1629,18 @@ extern "C" size_t vidc_conv_wgrad_scratch_bytes(int B, int Ho, int Wo, int Cout,
     return (size_t)chunks * KH * KW * (size_t)Cout * Cin * sizeof(float);
 }
 
-extern "C" int vidc_conv_wgrad(const float* dy, const float* x, float* dw_oihw, int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout, int lddy,
-                               int KH, int KW, int stride, int pad, void* scratch, vidc_stream_t stream) {
-    VIDC_REQUIRE(dy && x && dw_oihw && scratch, VIDC_ERR_NULL, "vidc_conv_wgrad: null pointer");
-    VIDC_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH >= 1 && KW >= 1 && stride >= 1 && pad >= 0 && ldx >= Cin && lddy >= Cout,
-                 VIDC_ERR_SHAPE, "vidc_conv_wgrad: bad shape");
-    VIDC_REQUIRE(Ho == (H + 2 * pad - KH) / stride + 1 && Wo == (W + 2 * pad - KW) / stride + 1, VIDC_ERR_SHAPE, "vidc_conv_wgrad: Ho/Wo inconsistent");
+namespace {
+// vidc_conv_wgrad and vidc_conv_wgrad_dilated: one body, one kernel; dilation 1 launches exactly what the plain entry always launched.
+int conv_wgrad_launch(const char* what, const float* dy, const float* x, float* dw_oihw, int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout,
+                      int lddy, int KH, int KW, int stride, int pad, int dilation, void* scratch, vidc_stream_t stream) {
+    VIDC_REQUIRE(dy && x && dw_oihw && scratch, VIDC_ERR_NULL, "%s: null pointer", what);
+    VIDC_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH >= 1 && KW >= 1 && stride >= 1 && pad >= 0 && dilation >= 1 && ldx >= Cin && lddy >= Cout,
+                 VIDC_ERR_SHAPE, "%s: bad shape", what);
+    VIDC_REQUIRE((long long)dilation * (KH - 1) <= H + 2 * pad - 1 && (long long)dilation * (KW - 1) <= W + 2 * pad - 1 &&
+                     Ho == (H + 2 * pad - dilation * (KH - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dilation * (KW - 1) - 1) / stride + 1,
+                 VIDC_ERR_SHAPE, "%s: Ho/Wo inconsistent", what);
     VIDC_REQUIRE((long long)B * H * W * ldx < (1ll << 31) && (long long)B * Ho * Wo * lddy < (1ll << 31), VIDC_ERR_SHAPE,
-                 "vidc_conv_wgrad: tensors must stay below 2^31 elements (32-bit offsets)");
+                 "%s: tensors must stay below 2^31 elements (32-bit offsets)", what);
     hipStream_t st = vidc::as_stream(stream);
     const long long M = (long long)B * Ho * Wo;
     const int taps = KH * KW;
@@ -1596,28 +1648,60 @@ extern "C" int vidc_conv_wgrad(const float* dy, const float* x, float* dw_oihw, 
     const int chunks = (int)((M + rows - 1) / rows);
     float* partial = reinterpret_cast<float*>(scratch);
     hipLaunchKernelGGL(wgrad_kernel, dim3((Cout + 127) / 128, ((Cin + 127) / 128) * taps, chunks), dim3(256), 0, st, dy, x, B, H, W, Cin, ldx, Ho, Wo, Cout, lddy,
-                       KH, KW, stride, pad, rows, partial);
+                       KH, KW, stride, pad, dilation, rows, partial);
     hipLaunchKernelGGL(wgrad_final_kernel, dim3(blocks((long long)taps * Cout * Cin)), dim3(TT), 0, st, partial, chunks, taps, Cout, Cin, dw_oihw);
     VIDC_CHECK_LAUNCH("conv_wgrad");
     return VIDC_OK;
 }
+}
 
-extern "C" int vidc_im2col_transposed(const float* x, float* xt, int B, int H, int W, int C, int ldx, int Ho, int Wo, int KH, int KW, int stride, int pad,
-                                      int Mp, int split, vidc_stream_t stream) {
-    VIDC_REQUIRE(x && xt, VIDC_ERR_NULL, "vidc_im2col_transposed: null pointer");
+extern "C" int vidc_conv_wgrad(const float* dy, const float* x, float* dw_oihw, int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout, int lddy,
+                               int KH, int KW, int stride, int pad, void* scratch, vidc_stream_t stream) {
+    return conv_wgrad_launch("vidc_conv_wgrad", dy, x, dw_oihw, B, H, W, Cin, ldx, Ho, Wo, Cout, lddy, KH, KW, stride, pad, 1, scratch, stream);
+}
+
+// (the scratch does not depend on the dilation: the partials are [chunk][tap][Cout][Cin] of the same output pixels)
+extern "C" size_t vidc_conv_wgrad_dilated_scratch_bytes(int B, int Ho, int Wo, int Cout, int Cin, int KH, int KW) {
+    return vidc_conv_wgrad_scratch_bytes(B, Ho, Wo, Cout, Cin, KH, KW);
+}
+
+extern "C" int vidc_conv_wgrad_dilated(const float* dy, const float* x, float* dw_oihw, int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout, int lddy,
+                                       int KH, int KW, int stride, int pad, int dilation, void* scratch, vidc_stream_t stream) {
+    return conv_wgrad_launch("vidc_conv_wgrad_dilated", dy, x, dw_oihw, B, H, W, Cin, ldx, Ho, Wo, Cout, lddy, KH, KW, stride, pad, dilation, scratch, stream);
+}
+
+namespace {
+// vidc_im2col_transposed and vidc_im2col_transposed_dilated: one body, the same two kernels.
+int im2col_transposed_launch(const char* what, const float* x, float* xt, int B, int H, int W, int C, int ldx, int Ho, int Wo, int KH, int KW, int stride,
+                             int pad, int dilation, int Mp, int split, vidc_stream_t stream) {
+    VIDC_REQUIRE(x && xt, VIDC_ERR_NULL, "%s: null pointer", what);
     const long long M = (long long)B * Ho * Wo;
-    VIDC_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && ldx >= C && KH >= 1 && KW >= 1 && stride >= 1 && pad >= 0 && Mp >= M && Mp % 32 == 0 && M < (1ll << 31) &&
-                     (long long)KH * KW <= 65535 && split >= 0 && (split & 3) <= 2 && split < 8 && ((split & 3) != 2 || Mp % 64 == 0), VIDC_ERR_SHAPE,
-                 "vidc_im2col_transposed: bad shape (Mp = M rounded up to a multiple of 32; 64 for plain bf16 rows)");
+    VIDC_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && ldx >= C && KH >= 1 && KW >= 1 && stride >= 1 && pad >= 0 && dilation >= 1 && Mp >= M &&
+                     Mp % 32 == 0 && M < (1ll << 31) && (long long)KH * KW <= 65535 && split >= 0 && (split & 3) <= 2 && split < 8 && ((split & 3) != 2 || Mp % 64 == 0),
+                 VIDC_ERR_SHAPE, "%s: bad shape (Mp = M rounded up to a multiple of 32; 64 for plain bf16 rows)", what);
+    // (a tap's coordinate stays an int: the kernels test it against the image before they form an address)
+    VIDC_REQUIRE((long long)(Ho - 1) * stride + (long long)(KH - 1) * dilation < (1ll << 30) && (long long)(Wo - 1) * stride + (long long)(KW - 1) * dilation < (1ll << 30),
+                 VIDC_ERR_SHAPE, "%s: tap coordinates out of range", what);
     const bool wide = C % 4 == 0 && ldx % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(xt)) & 15) == 0;
     if (wide)
         hipLaunchKernelGGL(im2col_t64_kernel, dim3((Mp + 63) / 64, (C + 63) / 64, KH * KW), dim3(256), 0, vidc::as_stream(stream), x, xt, B, H, W, C, ldx, Ho, Wo,
-                           KH, KW, stride, pad, (int)M, Mp, split);
+                           KH, KW, stride, pad, dilation, (int)M, Mp, split);
     else
         hipLaunchKernelGGL(im2col_t_kernel, dim3(Mp / 32, (C + 31) / 32, KH * KW), dim3(256), 0, vidc::as_stream(stream), x, xt, B, H, W, C, ldx, Ho, Wo, KH, KW,
-                           stride, pad, (int)M, Mp, split);
+                           stride, pad, dilation, (int)M, Mp, split);
     VIDC_CHECK_LAUNCH("im2col_t_kernel");
     return VIDC_OK;
+}
+}
+
+extern "C" int vidc_im2col_transposed(const float* x, float* xt, int B, int H, int W, int C, int ldx, int Ho, int Wo, int KH, int KW, int stride, int pad,
+                                      int Mp, int split, vidc_stream_t stream) {
+    return im2col_transposed_launch("vidc_im2col_transposed", x, xt, B, H, W, C, ldx, Ho, Wo, KH, KW, stride, pad, 1, Mp, split, stream);
+}
+
+extern "C" int vidc_im2col_transposed_dilated(const float* x, float* xt, int B, int H, int W, int C, int ldx, int Ho, int Wo, int KH, int KW, int stride, int pad,
+                                              int dilation, int Mp, int split, vidc_stream_t stream) {
+    return im2col_transposed_launch("vidc_im2col_transposed_dilated", x, xt, B, H, W, C, ldx, Ho, Wo, KH, KW, stride, pad, dilation, Mp, split, stream);
 }
 
 extern "C" int vidc_im2col_transposed_bf16(const void* x_bf16, void* xt_bf16, int B, int H, int W, int C, int Ho, int Wo, int KH, int KW, int stride, int pad,

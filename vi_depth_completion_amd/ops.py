@@ -423,13 +423,24 @@ def pack_conv_weight_dgrad(w_oihw, precision=0):
     return out
 
 
-def conv_backward_data(dc, w_oihw, H, W, stride, pad, precision=0):
+def conv_backward_data(dc, w_oihw, H, W, stride, pad, precision=0, dilation=1):
     """dx NHWC (B,H,W,Cin) of a conv from the gradient dc of its raw output: vidc_zero_stuff (stride > 1) + the conv kernel on the
-    data-gradient weights, in the arithmetic of `precision` (the sequence DepthCompletionTrainer.conv records)."""
+    data-gradient weights, in the arithmetic of `precision` (the sequence DepthCompletionTrainer.conv records).  dilation > 1 (stride 1 only):
+    the same conv kernel with the same dilation and pad' = dilation * (k - 1) - pad."""
     _dev(dc, w_oihw)
     dc = dc.contiguous()
     co, ci, kh, kw = w_oihw.shape
     B, Ho, Wo, _c = dc.shape
+    if dilation != 1:
+        if dilation < 1 or stride != 1 or kh != kw or dilation * (kh - 1) - pad < 0:
+            raise RuntimeError("conv data gradient: unsupported geometry %dx%d stride %d pad %d dilation %d (a dilated conv must have stride 1, a square "
+                               "kernel and pad <= dilation * (k-1))" % (kh, kw, stride, pad, dilation))
+        if (Ho, Wo) != (H + 2 * pad - dilation * (kh - 1), W + 2 * pad - dilation * (kw - 1)):
+            raise RuntimeError("conv data gradient: dc is %dx%d, a %dx%d conv of dilation %d and pad %d over %dx%d gives %dx%d"
+                               % (Ho, Wo, kh, kw, dilation, pad, H, W, H + 2 * pad - dilation * (kh - 1), W + 2 * pad - dilation * (kw - 1)))
+        one, zero = torch.ones(ci, dtype=torch.float32, device=dc.device), torch.zeros(ci, dtype=torch.float32, device=dc.device)
+        return conv2d_bn_act(dc, pack_conv_weight_dgrad(w_oihw, precision), one, zero, kh, kw, stride=1, pad=dilation * (kh - 1) - pad, precision=precision,
+                             dilation=dilation)
     if kh != kw or kh - 1 - pad < 0 or (stride > 1 and 2 * pad > kh - 1):
         raise RuntimeError("conv data gradient: unsupported geometry %dx%d stride %d pad %d (square kernels, pad <= k-1, and pad <= (k-1)/2 when strided)"
                            % (kh, kw, stride, pad))
@@ -445,14 +456,20 @@ def conv_backward_data(dc, w_oihw, H, W, stride, pad, precision=0):
     return dx
 
 
-def conv_backward_weight(dc, x, w_shape, stride, pad):
-    """dw OIHW (fp32) from the gradient dc of the raw conv output and the conv's NHWC input (vidc_conv_wgrad)."""
+def conv_backward_weight(dc, x, w_shape, stride, pad, dilation=1):
+    """dw OIHW (fp32) from the gradient dc of the raw conv output and the conv's NHWC input (vidc_conv_wgrad; vidc_conv_wgrad_dilated when
+    dilation != 1)."""
     _dev(dc, x)
     dc, x = dc.contiguous(), x.contiguous()
     co, ci, kh, kw = w_shape
     B, H, W, _c = x.shape
     _b, Ho, Wo, _co = dc.shape
     dw = torch.empty((co, ci, kh, kw), dtype=torch.float32, device=x.device)
+    if dilation != 1:
+        sc = _scratch(L.lib().vidc_conv_wgrad_dilated_scratch_bytes(B, Ho, Wo, co, ci, kh, kw), x.device)
+        L.check(L.lib().vidc_conv_wgrad_dilated(L.ptr(dc), L.ptr(x), L.ptr(dw), B, H, W, ci, ci, Ho, Wo, co, co, kh, kw, stride, pad, dilation, L.ptr(sc),
+                                                L.current_stream()), "conv_wgrad_dilated")
+        return dw
     sc = _scratch(L.lib().vidc_conv_wgrad_scratch_bytes(B, Ho, Wo, co, ci, kh, kw), x.device)
     L.check(L.lib().vidc_conv_wgrad(L.ptr(dc), L.ptr(x), L.ptr(dw), B, H, W, ci, ci, Ho, Wo, co, co, kh, kw, stride, pad, L.ptr(sc), L.current_stream()),
             "conv_wgrad")
@@ -519,23 +536,56 @@ def upsample_bilinear_ac_backward(dy, size_in, y=None):
     return dx
 
 
+def avgpool2d(x, kernel, stride, padding):
+    """nn.AvgPool2d(kernel, stride, padding) with count_include_pad=True on NHWC (B,H,W,C), C % 4 == 0 (vidc_avgpool2d); kernel, stride and
+    padding are (h, w) pairs."""
+    _dev(x)
+    x = x.contiguous().float()
+    (kh, kw), (sh, sw), (ph, pw) = kernel, stride, padding
+    B, H, W, Cc = x.shape
+    if min(kh, kw, sh, sw) < 1 or min(ph, pw) < 0 or H + 2 * ph < kh or W + 2 * pw < kw:
+        raise RuntimeError("avgpool2d: bad geometry: kernel %s stride %s padding %s on a %dx%d map" % (kernel, stride, padding, H, W))
+    Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    y = torch.empty((B, Ho, Wo, Cc), dtype=torch.float32, device=x.device)
+    L.check(L.lib().vidc_avgpool2d(L.ptr(x), L.ptr(y), B, H, W, Cc, Cc, kh, kw, sh, sw, ph, pw, Cc, L.current_stream()), "avgpool2d")
+    return y
+
+
+def avgpool2d_backward(dy, size_in, kernel, stride, padding):
+    """dx NHWC (B,H,W,C) of avgpool2d from the gradient dy of its output; size_in = (H, W) (vidc_avgpool2d_backward)."""
+    _dev(dy)
+    dy = dy.contiguous().float()
+    (kh, kw), (sh, sw), (ph, pw) = kernel, stride, padding
+    B, Ho, Wo, Cc = dy.shape
+    H, W = size_in
+    if min(kh, kw, sh, sw) < 1 or min(ph, pw) < 0 or H + 2 * ph < kh or W + 2 * pw < kw or (Ho, Wo) != ((H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1):
+        raise RuntimeError("avgpool2d_backward: dy is %dx%d, which is not the pool of a %dx%d map with kernel %s stride %s padding %s"
+                           % (Ho, Wo, H, W, kernel, stride, padding))
+    dx = torch.empty((B, H, W, Cc), dtype=torch.float32, device=dy.device)
+    L.check(L.lib().vidc_avgpool2d_backward(L.ptr(dy), L.ptr(dx), B, H, W, Cc, Cc, kh, kw, sh, sw, ph, pw, Cc, L.current_stream()), "avgpool2d_backward")
+    return dx
+
+
 def head_conv1x1_upsample_backward(dy, x, w, pad, y=None):
-    """(dx NHWC, dw, dbias) of head_conv1x1_upsample for one output channel and pad 1 (vidc_head_backward_multi's Cout = 1, pad = 1); y: the forward output when relu."""
+    """(dx NHWC, dw, dbias (Cout,)) of head_conv1x1_upsample for up to four output channels and pad 0 or 1: vidc_relu_backward (y: the forward
+    output when relu), the upsample backward on the B * Cout one-channel planes, vidc_head_backward_multi."""
     _dev(dy, x, w, y)
     x = x.contiguous()
     B, h, wd, cin = x.shape
     w2 = w.reshape(w.shape[0], -1).contiguous().float()
-    if w2.shape[0] != 1 or pad != 1:
-        raise RuntimeError("head_conv1x1_upsample backward: one output channel and pad 1 only (got Cout %d, pad %d)" % (w2.shape[0], pad))
+    co = w2.shape[0]
+    if not 1 <= co <= 4 or pad not in (0, 1):
+        raise RuntimeError("head_conv1x1_upsample backward: 1 to 4 output channels and pad 0 or 1 only (got Cout %d, pad %d)" % (co, pad))
     dy = dy.contiguous().float()
     H, W = dy.shape[2], dy.shape[3]
+    ph, pw = h + 2 * pad, wd + 2 * pad
     g = relu_backward(dy, y) if y is not None else dy
-    g_low = torch.empty((B, h + 2, wd + 2), dtype=torch.float32, device=x.device)
-    L.check(L.lib().vidc_upsample_bilinear_ac_backward(L.ptr(g), L.ptr(g_low), B, h + 2, wd + 2, 1, 1, 1, H, W, L.current_stream()), "upsample_bilinear_ac_backward")
+    g_low = torch.empty((B * co, ph, pw), dtype=torch.float32, device=x.device)
+    L.check(L.lib().vidc_upsample_bilinear_ac_backward(L.ptr(g), L.ptr(g_low), B * co, ph, pw, 1, 1, 1, H, W, L.current_stream()), "upsample_bilinear_ac_backward")
     dx = torch.empty_like(x)
     dw = torch.empty(w.shape, dtype=torch.float32, device=x.device)
-    db = torch.empty((1,), dtype=torch.float32, device=x.device)
-    sc = _scratch(L.lib().vidc_head_backward_multi_scratch_bytes(B, h, wd, cin, 1, pad), x.device)
-    L.check(L.lib().vidc_head_backward_multi(L.ptr(g_low), L.ptr(x), L.ptr(w2), L.ptr(dx), L.ptr(dw), L.ptr(db), B, h, wd, cin, cin, cin, 1, pad, L.ptr(sc),
+    db = torch.empty((co,), dtype=torch.float32, device=x.device)
+    sc = _scratch(L.lib().vidc_head_backward_multi_scratch_bytes(B, h, wd, cin, co, pad), x.device)
+    L.check(L.lib().vidc_head_backward_multi(L.ptr(g_low), L.ptr(x), L.ptr(w2), L.ptr(dx), L.ptr(dw), L.ptr(db), B, h, wd, cin, cin, cin, co, pad, L.ptr(sc),
                                              L.current_stream()), "head_backward")
     return dx, dw, db

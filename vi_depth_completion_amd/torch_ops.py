@@ -16,6 +16,8 @@ the operators are the per-op surface for callers that compose the kernels with o
     torch.ops.vidc.maxpool3x3s2(x_nhwc)                                       torchvision ResNet.maxpool
     torch.ops.vidc.upsample_bilinear_ac(x_nhwc, Ho, Wo, relu)                 nn.UpsamplingBilinear2d (align_corners=True)
     torch.ops.vidc.head_conv1x1_upsample(x_nhwc, w, bias, pad, Ho, Wo, relu)  depth_completion.py:141-147 / surface_normal.py:140-145
+    torch.ops.vidc.conv2d_dilated_bn_act(x_nhwc, w_oihw, scale, shift, pad, dilation, relu, precision)   surface_normal_dorn.py:45-68 (the ASPP branches)
+    torch.ops.vidc.avgpool2d(x_nhwc, kh, kw, sh, sw, ph, pw)                  surface_normal_dorn.py:10 (nn.AvgPool2d, count_include_pad=True)
     torch.ops.vidc.plane_ransac_normal(normals, ids, slots, hyp_pix)          main.py:38-62 (+ the write-back of :157)
     torch.ops.vidc.plane_offset(homo, depth, slots, inlier_mask, counts, scratch)       main.py:68-101, 162-173
     torch.ops.vidc.plane_project_depth(homo, slots, inlier_mask, scratch, records, plane_depth)   main.py:110-127
@@ -24,16 +26,21 @@ the operators are the per-op surface for callers that compose the kernels with o
 (the host-side draws that feed them -- np.random.permutation / randint in the reference's order -- are plane.draw_normal_hypotheses
 and plane.draw_enrichment; plane.PlaneBlock is the composition the pipeline uses)
 
-Autograd.  The first eight operators (the warps, the convs and the glue) are differentiable: each has a backward registered with
+Autograd.  The first ten operators (the warps, the convs and the glue) are differentiable: each has a backward registered with
 `torch.library.register_autograd`, and each backward formula is itself a custom operator (`torch.ops.vidc.*_backward`, listed in
-BACKWARD_OPS) with a shape function, built from HIP kernels only -- the warp adjoints of csrc/warp.hip, vidc_affine_act_backward +
+BACKWARD_OPS and, for the two operators of SurfaceNormalDORN's scene-understanding module, DORN_BACKWARD_OPS) with a shape function, built
+from HIP kernels only -- the warp adjoints of csrc/warp.hip, vidc_affine_act_backward +
 zero-stuffing + the conv kernel on data-gradient weights + vidc_conv_wgrad for the convs (precision 0 and 1; Winograd forwards share the
 direct form's backward; the data gradient runs in exact fp32 except behind a Winograd forward at precision 1, where it runs in bf16x3 like
 the forward), the backward kernels of csrc/train.hip for the glue.  Gradients flow to images / activations, conv weights, the
 folded scale / shift and the head's bias; only those `ctx.needs_input_grad` asks for are computed, and nothing is saved when gradients are
 disabled.  `gravity` / `aligned` get no gradient (the warp record is built with cosf / atan2f / bbox min-max) and precision 3 (MXFP8) has no
-backward: requesting either raises.  The head's backward covers one output channel with pad 1 (vidc_head_backward).  Double backward is
-not supported.  The plane operators (`plane_*`, `enrich_scatter`) stay non-differentiable: they are RANSAC decisions and index scatters.
+backward: requesting either raises.  The dilated conv's backward is the direct form's with stride 1: the data gradient is the conv kernel on
+the data-gradient weights with the same dilation and pad' = dilation * (k - 1) - pad, the weight gradient vidc_conv_wgrad_dilated; avgpool2d's
+is vidc_avgpool2d_backward.  The head's backward covers up to four output channels with pad 0 or 1 (vidc_head_backward_multi on B * Cout
+one-channel planes: the depth head, surface_normal.py:143 and surface_normal_dorn.py:74-75).  With these a frozen-BatchNorm fine-tune of
+SurfaceNormalDORN composes from the operators (Dropout2d: F.dropout2d or a mask multiply in torch).  Double backward is not supported.
+The plane operators (`plane_*`, `enrich_scatter`) stay non-differentiable: they are RANSAC decisions and index scatters.
 """
 from typing import Optional, Tuple
 
@@ -94,6 +101,23 @@ def _(x_nhwc, w_oihw, scale, shift, stride, pad, relu, precision):
     return x_nhwc.new_empty((B, (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1, co))
 
 
+@torch.library.custom_op("vidc::conv2d_dilated_bn_act", mutates_args=(), device_types=_DEV)
+def conv2d_dilated_bn_act(x_nhwc: torch.Tensor, w_oihw: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, pad: int, dilation: int, relu: bool,
+                          precision: int) -> torch.Tensor:
+    """conv2d_bn_act for a dilated conv of stride 1 (the ASPP branches, surface_normal_dorn.py:45-68: Conv2d(2048, 512, 3, padding=d, dilation=d) +
+    BatchNorm2d(eval) + ReLU, d = 6 / 12 / 18): tap (kh, kw) reads x[oy - pad + kh * dilation, ox - pad + kw * dilation]; precision as there."""
+    pack = {1: _ops.pack_conv_weight_bf16x3, 2: _ops.pack_conv_weight_bf16, 3: _ops.pack_conv_weight_mxfp8}.get(precision, _ops.pack_conv_weight)
+    return _ops.conv2d_bn_act(x_nhwc, pack(w_oihw), scale, shift, w_oihw.shape[2], w_oihw.shape[3], stride=1, pad=pad, relu1=relu, precision=precision,
+                              dilation=dilation)
+
+
+@conv2d_dilated_bn_act.register_fake
+def _(x_nhwc, w_oihw, scale, shift, pad, dilation, relu, precision):
+    B, H, W, _c = x_nhwc.shape
+    co, _ci, kh, kw = w_oihw.shape
+    return x_nhwc.new_empty((B, H + 2 * pad - dilation * (kh - 1), W + 2 * pad - dilation * (kw - 1), co))
+
+
 @torch.library.custom_op("vidc::conv3x3_winograd", mutates_args=(), device_types=_DEV)
 def conv3x3_winograd(x_nhwc: torch.Tensor, w_oihw: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, m: int, relu: bool,
                      precision: int) -> torch.Tensor:
@@ -129,6 +153,18 @@ def maxpool3x3s2(x_nhwc: torch.Tensor) -> torch.Tensor:
 def _(x_nhwc):
     B, H, W, Cc = x_nhwc.shape
     return x_nhwc.new_empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc))
+
+
+@torch.library.custom_op("vidc::avgpool2d", mutates_args=(), device_types=_DEV)
+def avgpool2d(x_nhwc: torch.Tensor, kh: int, kw: int, sh: int, sw: int, ph: int, pw: int) -> torch.Tensor:
+    """nn.AvgPool2d((kh, kw), (sh, sw), (ph, pw)) with count_include_pad=True on NHWC (FullImageEncoder.global_pooling, surface_normal_dorn.py:10)."""
+    return _ops.avgpool2d(x_nhwc, (kh, kw), (sh, sw), (ph, pw))
+
+
+@avgpool2d.register_fake
+def _(x_nhwc, kh, kw, sh, sw, ph, pw):
+    B, H, W, Cc = x_nhwc.shape
+    return x_nhwc.new_empty((B, (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1, Cc))
 
 
 @torch.library.custom_op("vidc::upsample_bilinear_ac", mutates_args=(), device_types=_DEV)
@@ -330,6 +366,24 @@ def _warp_inv_backward(ctx, _grad_h, grad_z):
 torch.library.register_autograd("vidc::warp2dof_inv_rot_norm", _warp_inv_backward, setup_context=_warp_inv_setup)
 
 
+def _conv_backward_body(what, dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, stride, pad, dilation, relu, precision, need_x, need_w, need_affine,
+                        recompute_c):
+    """conv2d_bn_act_backward and conv2d_dilated_bn_act_backward (documented there)."""
+    dil = {} if dilation == 1 else {"dilation": dilation}
+    c_raw = None
+    if need_affine and (recompute_c or bool((scale == 0).any())):
+        if x_nhwc is None:
+            raise RuntimeError("%s: dscale of this conv needs the conv's input" % what)
+        c_raw = _ops.conv2d_bn_act(x_nhwc, _ops.pack_conv_weight(w_oihw), torch.ones_like(scale), torch.zeros_like(shift), w_oihw.shape[2],
+                                   w_oihw.shape[3], stride=stride, pad=pad, precision=0, **dil)
+    dc, dscale, dshift = _ops.affine_act_backward(dy, y, scale, shift, relu, c_raw, all_from_raw=recompute_c)
+    dx = _ops.conv_backward_data(dc, w_oihw, in_h, in_w, stride, pad, precision, **dil) if need_x else dy.new_empty(0)
+    if need_w and x_nhwc is None:
+        raise RuntimeError("%s: dw needs the conv's input" % what)
+    dw = _ops.conv_backward_weight(dc, x_nhwc, tuple(w_oihw.shape), stride, pad, **dil) if need_w else dy.new_empty(0)
+    return dx, dw, (dscale if need_affine else dy.new_empty(0)), (dshift if need_affine else dy.new_empty(0))
+
+
 @torch.library.custom_op("vidc::conv2d_bn_act_backward", mutates_args=(), device_types=_DEV)
 def conv2d_bn_act_backward(dy: torch.Tensor, x_nhwc: Optional[torch.Tensor], w_oihw: torch.Tensor, y: torch.Tensor, scale: torch.Tensor,
                            shift: torch.Tensor, in_h: int, in_w: int, stride: int, pad: int, relu: bool, precision: int, need_x: bool,
@@ -343,18 +397,8 @@ def conv2d_bn_act_backward(dy: torch.Tensor, x_nhwc: Optional[torch.Tensor], w_o
     recompute_c (the forward ran in bf16x3 or as Winograd, whose y is not an fp32-accurate image of c), and for channels whose scale is 0, c
     is read from a re-run of the conv in the direct fp32 form with an identity epilogue, so that dscale is an fp32 result like dw and dshift.
     x_nhwc is read by dw and by that re-run."""
-    c_raw = None
-    if need_affine and (recompute_c or bool((scale == 0).any())):
-        if x_nhwc is None:
-            raise RuntimeError("conv2d_bn_act_backward: dscale of this conv needs the conv's input")
-        c_raw = _ops.conv2d_bn_act(x_nhwc, _ops.pack_conv_weight(w_oihw), torch.ones_like(scale), torch.zeros_like(shift), w_oihw.shape[2],
-                                   w_oihw.shape[3], stride=stride, pad=pad, precision=0)
-    dc, dscale, dshift = _ops.affine_act_backward(dy, y, scale, shift, relu, c_raw, all_from_raw=recompute_c)
-    dx = _ops.conv_backward_data(dc, w_oihw, in_h, in_w, stride, pad, precision) if need_x else dy.new_empty(0)
-    if need_w and x_nhwc is None:
-        raise RuntimeError("conv2d_bn_act_backward: dw needs the conv's input")
-    dw = _ops.conv_backward_weight(dc, x_nhwc, tuple(w_oihw.shape), stride, pad) if need_w else dy.new_empty(0)
-    return dx, dw, (dscale if need_affine else dy.new_empty(0)), (dshift if need_affine else dy.new_empty(0))
+    return _conv_backward_body("conv2d_bn_act_backward", dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, stride, pad, 1, relu, precision, need_x, need_w,
+                               need_affine, recompute_c)
 
 
 @conv2d_bn_act_backward.register_fake
@@ -405,6 +449,45 @@ def _wino_backward(ctx, grad_y):
 
 
 torch.library.register_autograd("vidc::conv3x3_winograd", _wino_backward, setup_context=_wino_setup)
+
+
+@torch.library.custom_op("vidc::conv2d_dilated_bn_act_backward", mutates_args=(), device_types=_DEV)
+def conv2d_dilated_bn_act_backward(dy: torch.Tensor, x_nhwc: Optional[torch.Tensor], w_oihw: torch.Tensor, y: torch.Tensor, scale: torch.Tensor,
+                                   shift: torch.Tensor, in_h: int, in_w: int, pad: int, dilation: int, relu: bool, precision: int, need_x: bool,
+                                   need_w: bool, need_affine: bool, recompute_c: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dw, dscale, dshift) of conv2d_dilated_bn_act, as conv2d_bn_act_backward with stride 1: vidc_affine_act_backward -> dc; dx = the conv kernel
+    on the data-gradient weights over dc with the same dilation and pad' = dilation * (k - 1) - pad, in the arithmetic of `precision` (the
+    registration passes 0: the direct form's data gradient is exact fp32); dw = vidc_conv_wgrad_dilated in fp32; dscale's re-run of the conv
+    (recompute_c, or a zero scale) is dilated as well."""
+    return _conv_backward_body("conv2d_dilated_bn_act_backward", dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, 1, pad, dilation, relu, precision, need_x,
+                               need_w, need_affine, recompute_c)
+
+
+@conv2d_dilated_bn_act_backward.register_fake
+def _(dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, pad, dilation, relu, precision, need_x, need_w, need_affine, recompute_c):
+    empty = lambda: dy.new_empty(0)
+    return (dy.new_empty((dy.shape[0], in_h, in_w, w_oihw.shape[1])) if need_x else empty(), torch.empty_like(w_oihw) if need_w else empty(),
+            torch.empty_like(scale) if need_affine else empty(), torch.empty_like(shift) if need_affine else empty())
+
+
+def _dilated_setup(ctx, inputs, output):
+    x, w, scale, shift, pad, dilation, relu, precision = inputs
+    if w.shape[2] != w.shape[3] or dilation < 1 or dilation * (w.shape[2] - 1) - pad < 0:
+        raise RuntimeError("torch.ops.vidc.conv2d_dilated_bn_act: the backward covers square kernels with pad <= dilation * (k - 1) (got %dx%d, pad %d, "
+                           "dilation %d)" % (w.shape[2], w.shape[3], pad, dilation))
+    _conv_setup_common(ctx, "conv2d_dilated_bn_act", x, w, scale, shift, output, 1, pad, relu, precision, ctx.needs_input_grad)
+    in_h, in_w, _stride, pad_, *rest = ctx.args
+    ctx.args = (in_h, in_w, pad_, dilation) + tuple(rest)
+
+
+def _dilated_backward(ctx, grad_y):
+    x, w, y, scale, shift = ctx.saved_tensors
+    dx, dw, dscale, dshift = torch.ops.vidc.conv2d_dilated_bn_act_backward(grad_y, x, w, y, scale, shift, *ctx.args)
+    return (_none_if_empty(dx), _none_if_empty(dw), dscale.reshape(scale.shape) if ctx.needs_input_grad[2] else None,
+            dshift.reshape(shift.shape) if ctx.needs_input_grad[3] else None) + (None,) * 4
+
+
+torch.library.register_autograd("vidc::conv2d_dilated_bn_act", _dilated_backward, setup_context=_dilated_setup)
 
 
 @torch.library.custom_op("vidc::stem_conv3x3s2_backward", mutates_args=(), device_types=_DEV)
@@ -461,6 +544,29 @@ def _maxpool_backward(ctx, grad_y):
 torch.library.register_autograd("vidc::maxpool3x3s2", _maxpool_backward, setup_context=_maxpool_setup)
 
 
+@torch.library.custom_op("vidc::avgpool2d_backward", mutates_args=(), device_types=_DEV)
+def avgpool2d_backward(dy: torch.Tensor, in_h: int, in_w: int, kh: int, kw: int, sh: int, sw: int, ph: int, pw: int) -> torch.Tensor:
+    """dx NHWC (B, in_h, in_w, C) of avgpool2d (vidc_avgpool2d_backward: a deterministic gather)."""
+    return _ops.avgpool2d_backward(dy, (in_h, in_w), (kh, kw), (sh, sw), (ph, pw))
+
+
+@avgpool2d_backward.register_fake
+def _(dy, in_h, in_w, kh, kw, sh, sw, ph, pw):
+    return dy.new_empty((dy.shape[0], in_h, in_w, dy.shape[3]))
+
+
+def _avgpool_setup(ctx, inputs, output):
+    x, *geom = inputs
+    ctx.args = (x.shape[1], x.shape[2]) + tuple(geom)
+
+
+def _avgpool_backward(ctx, grad_y):
+    return (torch.ops.vidc.avgpool2d_backward(grad_y, *ctx.args),) + (None,) * 6
+
+
+torch.library.register_autograd("vidc::avgpool2d", _avgpool_backward, setup_context=_avgpool_setup)
+
+
 @torch.library.custom_op("vidc::upsample_bilinear_ac_backward", mutates_args=(), device_types=_DEV)
 def upsample_bilinear_ac_backward(dy: torch.Tensor, y: Optional[torch.Tensor], in_h: int, in_w: int) -> torch.Tensor:
     """dx of upsample_bilinear_ac; y: the forward output when its ReLU was applied (vidc_relu_backward first), else None."""
@@ -488,8 +594,8 @@ torch.library.register_autograd("vidc::upsample_bilinear_ac", _upsample_backward
 @torch.library.custom_op("vidc::head_conv1x1_upsample_backward", mutates_args=(), device_types=_DEV)
 def head_conv1x1_upsample_backward(dy: torch.Tensor, x_nhwc: torch.Tensor, w: torch.Tensor, y: Optional[torch.Tensor],
                                    pad: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """(dx NHWC, dw, dbias) of head_conv1x1_upsample: vidc_relu_backward (y given), vidc_upsample_bilinear_ac_backward, vidc_head_backward.
-    One output channel and pad 1 only."""
+    """(dx NHWC, dw, dbias (Cout,)) of head_conv1x1_upsample: vidc_relu_backward (y given), vidc_upsample_bilinear_ac_backward on the B * Cout
+    one-channel planes, vidc_head_backward_multi.  Up to four output channels, pad 0 or 1."""
     return _ops.head_conv1x1_upsample_backward(dy, x_nhwc, w, pad, y)
 
 
@@ -500,8 +606,8 @@ def _(dy, x_nhwc, w, y, pad):
 
 def _head_setup(ctx, inputs, output):
     x, w, bias, pad, _oh, _ow, relu = inputs
-    if w.shape[0] != 1 or pad != 1:
-        raise RuntimeError("torch.ops.vidc.head_conv1x1_upsample: the backward covers one output channel and pad 1 only (got Cout %d, pad %d)"
+    if not 1 <= w.shape[0] <= 4 or pad not in (0, 1):
+        raise RuntimeError("torch.ops.vidc.head_conv1x1_upsample: the backward covers 1 to 4 output channels and pad 0 or 1 only (got Cout %d, pad %d)"
                            % (w.shape[0], pad))
     ctx.save_for_backward(x, w, output if relu else None)
     ctx.pad, ctx.bias_shape = pad, bias.shape
@@ -519,5 +625,8 @@ torch.library.register_autograd("vidc::head_conv1x1_upsample", _head_backward, s
 
 BACKWARD_OPS = ("warp2dof_fwd_backward", "warp2dof_inv_rot_norm_backward", "conv2d_bn_act_backward", "stem_conv3x3s2_backward", "maxpool3x3s2_backward",
                 "upsample_bilinear_ac_backward", "head_conv1x1_upsample_backward")
+# the operators the scene-understanding module of SurfaceNormalDORN adds (a tuple of its own: BACKWARD_OPS keeps the seven of the first two networks)
+DORN_OPS = ("conv2d_dilated_bn_act", "avgpool2d")
+DORN_BACKWARD_OPS = ("conv2d_dilated_bn_act_backward", "avgpool2d_backward")
 OPS = ("plane_ransac_normal", "plane_offset", "plane_project_depth", "plane_finalize", "enrich_scatter", "warp2dof_fwd", "warp2dof_inv_rot_norm", "conv2d_bn_act",
-       "conv3x3_winograd", "stem_conv3x3s2", "maxpool3x3s2", "upsample_bilinear_ac", "head_conv1x1_upsample") + BACKWARD_OPS
+       "conv3x3_winograd", "stem_conv3x3s2", "maxpool3x3s2", "upsample_bilinear_ac", "head_conv1x1_upsample") + BACKWARD_OPS + DORN_OPS + DORN_BACKWARD_OPS
