@@ -734,6 +734,28 @@ size_t vidc_normal_l1_loss_scratch_bytes(int B, int H, int W);
 int vidc_normal_l1_loss(const float* pred, const float* normal_gt, const float* mask, int B, int H, int W, int normalize_prediction,
                         double* loss, double* count, double* angle, float* dpred, void* scratch, vidc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training SurfaceNormalDORN under autograd (networks/surface_normal_dorn.py in train() mode): nn.Dropout2d and the adjoint of
+ * vidc_normalize_nchw (csrc/dorn_train.hip).  Train-mode BatchNorm is vidc_bn_train_forward_add / vidc_bn_train_backward above.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The multipliers of nn.Dropout2d(p) (surface_normal_dorn.py:11, 70, 73): keep [B][C] fp32, one draw per (image, channel), each entry 0 or
+ * 1 / (1 - p) (computed in fp32).  Counter-based: entry i = b * C + c takes the first output word w of Philox4x32-10 under the key
+ * (seed & 0xffffffff, seed >> 32) at the counter (offset & 0xffffffff, i, offset >> 32, 0) -- for an offset below 2^32 that is (offset, i, 0, 0);
+ * u = (w >> 8) * 2^-24, and the entry is kept iff u >= p.  p = 0 gives all ones.  No device state and no host read: capturable, and the same
+ * (seed, offset) gives the same table.  p outside [0, 1) and B * C >= 2^31: VIDC_ERR_SHAPE. */
+int vidc_dropout2d_mask(float* keep, int B, int C, float p, unsigned long long seed, unsigned long long offset, vidc_stream_t stream);
+
+/* y[b,h,w,c] = x[b,h,w,c] * k[b][c] on NHWC rows: x [B * HW][ldx], y [B * HW][ldy] with C channels used (channel slices of a wider tensor:
+ * ldx, ldy > C; nothing outside the C channels is written), k [B][C].  The forward of Dropout2d with k = vidc_dropout2d_mask's table, and with
+ * dy in place of x its backward.  y may be x.  C, ldx, ldy multiples of 4; x, k, y 16-byte aligned. */
+int vidc_scale_image_channels(const float* x, const float* k, float* y, int B, int HW, int C, int ldx, int ldy, vidc_stream_t stream);
+
+/* The adjoint of vidc_normalize_nchw, as torch differentiates F.normalize(x, dim=1, eps=1e-12): x, dy (the gradient of the output), dx NCHW
+ * [B][C][HW].  With n = x / |x| per pixel: dx = (dy - n (n . dy)) / |x| where |x| >= eps, and dy / eps below it (the clamp passes no
+ * gradient) -- the rule and the fp64 inner arithmetic of vidc_normal_l1_loss's own normalisation. */
+int vidc_normalize_nchw_backward(const float* x, const float* dy, float* dx, int B, int C, int HW, vidc_stream_t stream);
+
 enum vidc_op_kind { VIDC_OP_CONV = 1, VIDC_OP_STEM = 2, VIDC_OP_MAXPOOL = 3, VIDC_OP_UPSAMPLE = 4, VIDC_OP_HEAD = 5,
                     VIDC_OP_WARP_PARAMS = 6, VIDC_OP_WARP_FWD = 7, VIDC_OP_WARP_INV = 8, VIDC_OP_COPY = 9, VIDC_OP_SPLIT = 10,
                     VIDC_OP_AVGPOOL = 11, VIDC_OP_NORMALIZE = 12, VIDC_OP_DET_IM2COL = 13, VIDC_OP_NEAREST2X = 14,

@@ -3,6 +3,10 @@
 ResNet-101 with the strides of layer3/layer4 removed (:119-125, features at 1/8 resolution) -> scene-understanding module (global
 encoder: AvgPool2d(8,8,(1,0)) -> Linear(40960,512) -> 1x1 conv -> broadcast; ASPP: 1x1 and three dilated 3x3 branches, dilation
 6/12/18; concat -> 1x1 -> 1x1 -> bilinear to the output size) -> F.normalize.  Dropout2d layers are identities in eval mode.
+
+Training: `forward_autograd(x)` is the reference's forward in train() mode (train-mode BatchNorm, the three Dropout2d layers) composed of the
+differentiable `torch.ops.vidc` operators on the module's own parameters, so the reference's loop (network_run.py:231-254: zero_grad, forward,
+loss.backward(), optimizer.step()) trains it; `eval()` afterwards re-folds the updated weights for the inference program.
 """
 import collections
 
@@ -75,12 +79,24 @@ class ResNet(nn.Module):
 
 
 class SurfaceNormalDORN(_HipModule):
+    _train_hint = ", or train the network with SurfaceNormalDORN.forward_autograd (torch.ops.vidc operators under autograd)"
+    DROPOUT_OFFSETS = {"encoder.dropout": 0, "concat_process.0": 1, "concat_process.3": 2}      # + 4 * dropout_step: the Philox offset of each layer's draw
+
     def __init__(self, output_size=(240, 320), pretrained=True, output_channel=3, training_mode="train_L2_loss"):
         super().__init__()
         self.output_size = output_size
         self.feature_extractor = ResNet(pretrained=pretrained)
         self.aspp_module = SceneUnderstandingModuleBN(output_channel=output_channel, mode=training_mode)
+        self.dropout_step = 0              # forward_autograd calls so far: advances the dropout offsets, so that two steps with one seed do not repeat masks
+        self._autograd_dirty = False       # forward_autograd ran since the inference weights were folded
         self._init_engine()
+
+    def train(self, mode=True):
+        super().train(mode)
+        if not mode and getattr(self, "_autograd_dirty", False):      # eval() after training steps: the folded weights and the programs are stale
+            self._invalidate()
+            self._autograd_dirty = False
+        return self
 
     def build_program(self, B, H, W, device, dry_run=False):
         prog = engine.Program(self._weights, device, B)
@@ -124,3 +140,85 @@ class SurfaceNormalDORN(_HipModule):
         prog.tensor(prog.inputs["image"]).copy_(x, non_blocking=True)
         self._execute(prog)
         return prog.tensor(prog.outputs["normals"]).clone()
+
+    # ---- training under autograd ---------------------------------------------------------------------------------------------------------
+    def forward_autograd(self, x, dropout_seed=None, precision=0, _keeps=None):
+        """The reference's forward in train() mode (surface_normal_dorn.py:18-30, 79-89, 130-154) from torch.ops.vidc operators only -- every conv a
+        conv2d_bn_act with scale 1 and its bias (or 0) as shift, every BatchNorm a batch_norm_train on the batch statistics (running statistics and
+        num_batches_tracked updated as torch does), the Bottleneck tail batch_norm_train(residual=identity, relu=True) -- on the module's own
+        parameters and buffers; views, permutes and torch.cat are the only torch glue.  Returns unit normals (B, 3, H, W) with a grad_fn.
+
+        dropout_seed: the 64-bit Philox key of the three Dropout2d draws (default: drawn from torch's default generator at call time); layer l of
+        call n draws at offset 4 * n + l (DROPOUT_OFFSETS, self.dropout_step).  precision: the convs' (0 exact fp32, 1 bf16x3).  _keeps (tests): the
+        three (B, C) keep tables to use instead of drawing them."""
+        if not x.is_cuda:
+            raise RuntimeError("SurfaceNormalDORN runs on the GPU only: there is no CPU/eager fallback")
+        if not self.training:
+            raise RuntimeError("SurfaceNormalDORN.forward_autograd is the train() mode forward; call .train() (eval(): forward)")
+        B, _c, H, W = x.shape
+        if (H, W) != tuple(self.output_size):
+            raise ValueError("SurfaceNormalDORN was built for %s inputs, got %s" % (tuple(self.output_size), (H, W)))
+        V = torch.ops.vidc
+        if dropout_seed is None:
+            dropout_seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        step, self.dropout_step = self.dropout_step, self.dropout_step + 1
+        self._autograd_dirty = True
+        consts, counters = {}, []
+
+        def const(n, v):
+            if (n, v) not in consts:
+                consts[(n, v)] = torch.full((n,), v, dtype=torch.float32, device=x.device)
+            return consts[(n, v)]
+
+        def conv(t, m, relu=False):
+            co = m.out_channels
+            shift = m.bias if m.bias is not None else const(co, 0.0)
+            if m.dilation[0] > 1:
+                return V.conv2d_dilated_bn_act(t, m.weight, const(co, 1.0), shift, m.padding[0], m.dilation[0], relu, precision)
+            return V.conv2d_bn_act(t, m.weight, const(co, 1.0), shift, m.stride[0], m.padding[0], relu, precision)
+
+        def bn(t, m, relu, residual=None):
+            if m.momentum is None or not m.track_running_stats:
+                raise RuntimeError("SurfaceNormalDORN.forward_autograd: BatchNorm2d with a momentum and running statistics only (the reference's)")
+            counters.append(m.num_batches_tracked)
+            return V.batch_norm_train(t, m.weight, m.bias, m.running_mean, m.running_var, m.momentum, m.eps, relu, residual)[0]
+
+        def dropout(t, name, i):
+            if _keeps is not None:
+                return V.scale_image_channels(t, _keeps[i])
+            m = self.aspp_module.get_submodule(name)
+            return V.dropout2d(t, m.p, dropout_seed, 4 * step + self.DROPOUT_OFFSETS[name])[0]
+
+        fe, sm = self.feature_extractor, self.aspp_module
+        stem = fe.conv1
+        t = V.stem_conv3x3s2(x, stem.conv1_1.weight, True)
+        t = bn(conv(t, stem.conv1_2), stem.bn_2, True)
+        t = bn(bn(conv(t, stem.conv1_3), stem.bn1_3, True), fe.bn1, True)
+        t = V.maxpool3x3s2(t)
+        for li in range(1, 5):
+            for blk in getattr(fe, "layer%d" % li):
+                u = bn(conv(t, blk.conv1), blk.bn1, True)
+                u = bn(conv(u, blk.conv2), blk.bn2, True)
+                idn = bn(conv(t, blk.downsample[0]), blk.downsample[1], False) if blk.downsample is not None else t
+                t = bn(conv(u, blk.conv3), blk.bn3, True, idn)
+        f = t                                                                                       # (B, H/8, W/8, 2048)
+        enc = sm.encoder
+        k, s, pd = enc.global_pooling.kernel_size, enc.global_pooling.stride, enc.global_pooling.padding
+        pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)
+        e = V.avgpool2d(f, *(pair(k) + pair(s) + pair(pd)))
+        e = dropout(e, "encoder.dropout", 0)
+        _b, eh, ew, ec = e.shape
+        fc = enc.global_fc.weight.view(-1, ec, eh, ew).permute(0, 2, 3, 1).reshape(-1, eh * ew * ec, 1, 1)      # (c, h, w) columns -> (h, w, c), as engine.linear
+        e = V.conv2d_bn_act(e.reshape(B, 1, 1, -1), fc, const(fc.shape[0], 1.0), enc.global_fc.bias, 1, 0, True, precision)
+        e = V.upsample_bilinear_ac(conv(e, enc.conv1), f.shape[1], f.shape[2], False)               # from 1x1: a broadcast
+        branches = [e]
+        for name in ("aspp1", "aspp2", "aspp3", "aspp4"):
+            a = getattr(sm, name)
+            u = bn(conv(f, a[0]), a[1], True)
+            branches.append(bn(conv(u, a[3]), a[4], True))
+        cp = sm.concat_process
+        h = dropout(torch.cat(branches, dim=3), "concat_process.0", 1)
+        h = dropout(conv(h, cp[1], relu=True), "concat_process.3", 2)
+        y = V.head_conv1x1_upsample(h, cp[4].weight, cp[4].bias, 0, H, W, False)
+        torch._foreach_add_(counters, 1)                                                            # every num_batches_tracked, one launch
+        return V.normalize_nchw(y)

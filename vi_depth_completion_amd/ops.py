@@ -589,3 +589,140 @@ def head_conv1x1_upsample_backward(dy, x, w, pad, y=None):
     L.check(L.lib().vidc_head_backward_multi(L.ptr(g_low), L.ptr(x), L.ptr(w2), L.ptr(dx), L.ptr(dw), L.ptr(db), B, h, wd, cin, cin, cin, co, pad, L.ptr(sc),
                                              L.current_stream()), "head_backward")
     return dx, dw, db
+
+
+# ---- train-mode BatchNorm, Dropout2d, F.normalize's adjoint, the normal loss (torch.ops.vidc's TRAIN_OPS) ---------------------------------
+def _rows(t):
+    """(tensor, M, C, ld) of NHWC rows for the row kernels: `t` itself when it is a dense tensor or a channel slice of one (unit channel stride,
+    rows `ld` floats apart, 16-byte aligned), else a dense copy."""
+    Cc = t.shape[-1]
+    M = t.numel() // Cc
+    ok = t.dtype == torch.float32 and t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and t.dim() >= 2
+    if ok and t.is_contiguous():
+        return t, M, Cc, Cc
+    if ok:
+        ld = t.stride(-2)
+        ok = ld >= Cc and ld % 4 == 0 and all(t.shape[i] == 1 or t.stride(i) == t.stride(i + 1) * t.shape[i + 1] for i in range(t.dim() - 2))
+    if not ok:
+        t = t.contiguous().float()
+        ld = Cc
+    return t, M, Cc, ld
+
+
+def batch_norm_train(x, gamma, beta, running_mean, running_var, momentum, eps, relu, residual=None):
+    """(y, save_mean, save_rstd): y = relu?(BatchNorm2d_train(x) + residual) on NHWC rows (x, residual: dense or channel slices); running_mean /
+    running_var are updated in place as nn.BatchNorm2d does (vidc_bn_train_forward_add)."""
+    _dev(x, gamma, beta, running_mean, running_var, residual)
+    x, M, Cc, ldx = _rows(x)
+    if not (gamma.numel() == beta.numel() == running_mean.numel() == running_var.numel() == Cc):
+        raise RuntimeError("batch_norm_train: %d channels, parameters of %d / %d / %d / %d" % (Cc, gamma.numel(), beta.numel(), running_mean.numel(), running_var.numel()))
+    if not (running_mean.is_contiguous() and running_var.is_contiguous() and running_mean.dtype == running_var.dtype == torch.float32):
+        raise RuntimeError("batch_norm_train: the running statistics are updated in place: dense float32 tensors")
+    r, ldr = None, 0
+    if residual is not None:
+        if residual.shape != x.shape:
+            raise RuntimeError("batch_norm_train: residual %s for x %s" % (tuple(residual.shape), tuple(x.shape)))
+        r, _m, _c, ldr = _rows(residual)
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    mean, rstd = torch.empty(Cc, dtype=torch.float32, device=x.device), torch.empty(Cc, dtype=torch.float32, device=x.device)
+    sc = _scratch(L.lib().vidc_train_scratch_bytes(M, Cc), x.device)
+    L.check(L.lib().vidc_bn_train_forward_add(L.ptr(x), L.ptr(y), M, Cc, ldx, Cc, L.ptr(gamma.contiguous().float()), L.ptr(beta.contiguous().float()),
+                                              L.ptr(running_mean), L.ptr(running_var), eps, momentum, int(relu), L.ptr(mean), L.ptr(rstd), None, L.ptr(r), ldr,
+                                              L.ptr(sc), L.current_stream()), "bn_train_forward")
+    return y, mean, rstd
+
+
+def batch_norm_train_backward(dy, x, y, gamma, save_mean, save_rstd, has_residual):
+    """(dx, dgamma, dbeta, dresidual) of batch_norm_train.  y: the forward output when a ReLU followed, else None.  With a residual the ReLU sits
+    behind the sum: vidc_relu_backward masks dy first, the masked gradient is dresidual and what the BatchNorm part starts from; without one the
+    mask is applied inside vidc_bn_train_backward and dresidual comes back empty."""
+    _dev(dy, x, y, gamma, save_mean, save_rstd)
+    x, M, Cc, ldx = _rows(x)
+    dy, _m, _c, lddy = _rows(dy)
+    lib, st = L.lib(), L.current_stream()
+    y_relu, ldy = None, 0
+    dres = dy.new_empty(0)
+    if y is not None:
+        y_relu, _m, _c, ldy = _rows(y)
+    if has_residual:
+        dres = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        L.check(lib.vidc_relu_backward(L.ptr(dy), L.ptr(y_relu), L.ptr(dres), M, Cc, lddy, ldy, Cc, 0, st), "relu_backward")      # (y None: a copy)
+        dy, lddy, y_relu, ldy = dres, Cc, None, 0
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    dgamma, dbeta = torch.empty(Cc, dtype=torch.float32, device=x.device), torch.empty(Cc, dtype=torch.float32, device=x.device)
+    sc = _scratch(lib.vidc_train_scratch_bytes(M, Cc), x.device)
+    L.check(lib.vidc_bn_train_backward(L.ptr(dy), L.ptr(x), L.ptr(y_relu), L.ptr(dx), M, Cc, lddy, ldx, ldy, Cc, L.ptr(gamma.contiguous().float()),
+                                       L.ptr(save_mean), L.ptr(save_rstd), L.ptr(dgamma), L.ptr(dbeta), None, L.ptr(sc), st), "bn_train_backward")
+    return dx, dgamma, dbeta, dres
+
+
+def dropout2d_mask(B, Cc, p, seed, offset, device):
+    """keep (B, C): 0 or 1 / (1 - p) per (image, channel), Philox4x32-10 at (seed, offset) (vidc_dropout2d_mask)."""
+    if not 0.0 <= p < 1.0:
+        raise RuntimeError("dropout2d: p must be in [0, 1), got %r" % (p,))
+    if seed < 0 or offset < 0:
+        raise RuntimeError("dropout2d: seed and offset are unsigned 64-bit values")
+    keep = torch.empty((B, Cc), dtype=torch.float32, device=device)
+    L.check(L.lib().vidc_dropout2d_mask(L.ptr(keep), B, Cc, p, seed, offset, L.current_stream()), "dropout2d_mask")
+    return keep
+
+
+def scale_image_channels(x, keep):
+    """y[b,h,w,c] = x[b,h,w,c] * keep[b][c] on NHWC (x: dense or a channel slice); vidc_scale_image_channels."""
+    _dev(x, keep)
+    B, Cc = x.shape[0], x.shape[-1]
+    if tuple(keep.shape) != (B, Cc):
+        raise RuntimeError("scale_image_channels: keep %s for x %s" % (tuple(keep.shape), tuple(x.shape)))
+    x, M, _c, ldx = _rows(x)
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    L.check(L.lib().vidc_scale_image_channels(L.ptr(x), L.ptr(keep.contiguous().float()), L.ptr(y), B, M // B, Cc, ldx, Cc, L.current_stream()),
+            "scale_image_channels")
+    return y
+
+
+def normalize_nchw(x):
+    """F.normalize(x, dim=1) on NCHW (vidc_normalize_nchw)."""
+    _dev(x)
+    x = x.contiguous().float()
+    B, Cc = x.shape[0], x.shape[1]
+    y = torch.empty_like(x)
+    L.check(L.lib().vidc_normalize_nchw(L.ptr(x), L.ptr(y), B, Cc, x.numel() // (B * Cc), L.current_stream()), "normalize_nchw")
+    return y
+
+
+def normalize_nchw_backward(x, dy):
+    """dx of normalize_nchw (vidc_normalize_nchw_backward)."""
+    _dev(x, dy)
+    x, dy = x.contiguous().float(), dy.contiguous().float()
+    B, Cc = x.shape[0], x.shape[1]
+    dx = torch.empty_like(x)
+    L.check(L.lib().vidc_normalize_nchw_backward(L.ptr(x), L.ptr(dy), L.ptr(dx), B, Cc, x.numel() // (B * Cc), L.current_stream()), "normalize_nchw_backward")
+    return dx
+
+
+def normal_l1_loss(pred, normal_gt, mask, normalize_prediction):
+    """(sums float64 (3,) = loss, count, angle; dpred NCHW) of the masked L1 normal loss: one vidc_normal_l1_loss call."""
+    _dev(pred, normal_gt, mask)
+    pred, gt, m = pred.contiguous().float(), normal_gt.contiguous().float(), mask.contiguous().float()
+    B, Cc, H, W = pred.shape
+    if Cc != 3 or gt.shape != pred.shape or m.numel() != B * H * W:
+        raise RuntimeError("normal_l1_loss: pred / normal_gt (B,3,H,W) and mask (B,[1,]H,W); got %s, %s, %s" % (tuple(pred.shape), tuple(gt.shape), tuple(mask.shape)))
+    sums = torch.empty(3, dtype=torch.float64, device=pred.device)
+    dpred = torch.empty_like(pred)
+    sc = _scratch(L.lib().vidc_normal_l1_loss_scratch_bytes(B, H, W), pred.device)
+    L.check(L.lib().vidc_normal_l1_loss(L.ptr(pred), L.ptr(gt), L.ptr(m), B, H, W, int(normalize_prediction), L.ptr(sums), L.ptr(sums[1:]), L.ptr(sums[2:]),
+                                        L.ptr(dpred), L.ptr(sc), L.current_stream()), "normal_l1_loss")
+    return sums, dpred
+
+
+def scale_by_scalar(x, s):
+    """x * s for a one-element device tensor s, as vidc_scale_image_channels over rows of four (the loss's upstream gradient times dpred)."""
+    _dev(x, s)
+    flat = x.contiguous().float().reshape(-1)
+    n = flat.numel()
+    if n % 4:
+        flat = torch.nn.functional.pad(flat, (0, 4 - n % 4))
+    k = s.reshape(1).float().expand(4).contiguous()
+    y = torch.empty_like(flat)
+    L.check(L.lib().vidc_scale_image_channels(L.ptr(flat), L.ptr(k), L.ptr(y), 1, flat.numel() // 4, 4, 4, 4, L.current_stream()), "scale_by_scalar")
+    return y[:n].reshape(x.shape)

@@ -38,8 +38,18 @@ disabled.  `gravity` / `aligned` get no gradient (the warp record is built with 
 backward: requesting either raises.  The dilated conv's backward is the direct form's with stride 1: the data gradient is the conv kernel on
 the data-gradient weights with the same dilation and pad' = dilation * (k - 1) - pad, the weight gradient vidc_conv_wgrad_dilated; avgpool2d's
 is vidc_avgpool2d_backward.  The head's backward covers up to four output channels with pad 0 or 1 (vidc_head_backward_multi on B * Cout
-one-channel planes: the depth head, surface_normal.py:143 and surface_normal_dorn.py:74-75).  With these a frozen-BatchNorm fine-tune of
-SurfaceNormalDORN composes from the operators (Dropout2d: F.dropout2d or a mask multiply in torch).  Double backward is not supported.
+one-channel planes: the depth head, surface_normal.py:143 and surface_normal_dorn.py:74-75).  Double backward is not supported.
+
+Training SurfaceNormalDORN (TRAIN_OPS / TRAIN_BACKWARD_OPS; SurfaceNormalDORN.forward_autograd composes them with the operators above):
+
+    torch.ops.vidc.batch_norm_train(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual=None) -> (y, save_mean, save_rstd)
+    torch.ops.vidc.dropout2d(x_nhwc, p, seed, offset) -> (y, keep)           nn.Dropout2d in train() mode, Philox4x32-10 per (image, channel)
+    torch.ops.vidc.scale_image_channels(x_nhwc, keep)                        y = x * keep[b][c]: Dropout2d for a given keep table; its own backward
+    torch.ops.vidc.normalize_nchw(x)                                         F.normalize(x, dim=1), surface_normal_dorn.py:154
+    torch.ops.vidc.normal_l1_loss(pred, normal_gt, mask, normalize_prediction) -> (loss, count, angle)     network_run.py:181-189
+
+batch_norm_train is nn.BatchNorm2d in train() mode (+ residual, + ReLU) on the trainers' kernels, updates the running statistics in place, and reads
+x in place when it is a channel slice; its backward, normalize_nchw's and the loss's are the custom operators of TRAIN_BACKWARD_OPS.
 The plane operators (`plane_*`, `enrich_scatter`) stay non-differentiable: they are RANSAC decisions and index scatters.
 """
 from typing import Optional, Tuple
@@ -623,6 +633,204 @@ def _head_backward(ctx, grad_y):
 torch.library.register_autograd("vidc::head_conv1x1_upsample", _head_backward, setup_context=_head_setup)
 
 
+# ---- training SurfaceNormalDORN: train-mode BatchNorm, Dropout2d, F.normalize, the normal loss ---------------------------------------------
+# batch_norm_train writes the running statistics in place, and torch.library.custom_op registers no autograd formula for an operator that mutates
+# an argument: it is defined through torch.library.define / impl -- the schema declares the two mutated arguments (what mutates_args would), the kernel
+# is registered for the GPU dispatch key only, and the Autograd key runs _BatchNormTrain, whose backward is the custom_op batch_norm_train_backward.
+torch.library.define("vidc::batch_norm_train", "(Tensor x_nhwc, Tensor gamma, Tensor beta, Tensor(a!) running_mean, Tensor(b!) running_var, float momentum, "
+                     "float eps, bool relu, Tensor? residual=None) -> (Tensor, Tensor, Tensor)")
+
+
+@torch.library.impl("vidc::batch_norm_train", "CUDA")
+def batch_norm_train(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual=None):
+    """(y, save_mean, save_rstd): y = relu?(nn.BatchNorm2d in train() mode (x) + residual) on NHWC; the batch statistics over the B*H*W rows in fp64,
+    save_mean / save_rstd (C,) kept for the backward; running_mean / running_var updated in place as nn.BatchNorm2d updates them (momentum, unbiased
+    variance).  x and residual may be channel slices of wider tensors.  vidc_bn_train_forward_add: the kernels of the trainers' BatchNorm."""
+    return _ops.batch_norm_train(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual)
+
+
+@torch.library.register_fake("vidc::batch_norm_train")
+def _(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual=None):
+    Cc = x_nhwc.shape[-1]
+    return x_nhwc.new_empty(x_nhwc.shape), x_nhwc.new_empty((Cc,)), x_nhwc.new_empty((Cc,))
+
+
+@torch.library.custom_op("vidc::batch_norm_train_backward", mutates_args=(), device_types=_DEV)
+def batch_norm_train_backward(dy: torch.Tensor, x_nhwc: torch.Tensor, y: Optional[torch.Tensor], gamma: torch.Tensor, save_mean: torch.Tensor,
+                              save_rstd: torch.Tensor, has_residual: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dgamma, dbeta, dresidual) of batch_norm_train; y: the forward output when its ReLU was applied, else None.  vidc_bn_train_backward, and
+    with a residual vidc_relu_backward first: the masked gradient is dresidual and what the BatchNorm part starts from (no residual: empty)."""
+    return _ops.batch_norm_train_backward(dy, x_nhwc, y, gamma, save_mean, save_rstd, has_residual)
+
+
+@batch_norm_train_backward.register_fake
+def _(dy, x_nhwc, y, gamma, save_mean, save_rstd, has_residual):
+    Cc = x_nhwc.shape[-1]
+    return (x_nhwc.new_empty(x_nhwc.shape), x_nhwc.new_empty((Cc,)), x_nhwc.new_empty((Cc,)),
+            x_nhwc.new_empty(x_nhwc.shape) if has_residual else x_nhwc.new_empty(0))
+
+
+class _BatchNormTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, relu, residual):
+        with torch._C._AutoDispatchBelowAutograd():
+            y, mean, rstd = torch.ops.vidc.batch_norm_train(x, gamma, beta, running_mean, running_var, momentum, eps, relu, residual)
+        ctx.save_for_backward(x, y if relu else None, gamma, mean, rstd)
+        ctx.has_residual = residual is not None
+        ctx.mark_non_differentiable(mean, rstd)
+        ctx.set_materialize_grads(False)
+        return y, mean, rstd
+
+    @staticmethod
+    def backward(ctx, grad_y, _grad_mean, _grad_rstd):
+        x, y, gamma, mean, rstd = ctx.saved_tensors
+        if grad_y is None:
+            return (None,) * 9
+        dx, dgamma, dbeta, dres = torch.ops.vidc.batch_norm_train_backward(grad_y, x, y, gamma, mean, rstd, ctx.has_residual)
+        need = ctx.needs_input_grad
+        return (dx if need[0] else None, dgamma.reshape(gamma.shape) if need[1] else None, dbeta.reshape(gamma.shape) if need[2] else None, None, None, None,
+                None, None, dres if (ctx.has_residual and need[8]) else None)
+
+
+@torch.library.impl("vidc::batch_norm_train", "Autograd")
+def _batch_norm_train_autograd(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual=None):
+    return _BatchNormTrain.apply(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual)
+
+
+@torch.library.custom_op("vidc::scale_image_channels", mutates_args=(), device_types=_DEV)
+def scale_image_channels(x_nhwc: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
+    """y[b,h,w,c] = x[b,h,w,c] * keep[b][c] (vidc_scale_image_channels): Dropout2d's forward for a given keep table, and its own backward."""
+    return _ops.scale_image_channels(x_nhwc, keep)
+
+
+@scale_image_channels.register_fake
+def _(x_nhwc, keep):
+    return x_nhwc.new_empty(x_nhwc.shape)
+
+
+def _scale_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[1])
+
+
+def _scale_backward(ctx, grad_y):
+    return torch.ops.vidc.scale_image_channels(grad_y, ctx.saved_tensors[0]), None      # (keep gets no gradient)
+
+
+torch.library.register_autograd("vidc::scale_image_channels", _scale_backward, setup_context=_scale_setup)
+
+
+@torch.library.custom_op("vidc::dropout2d", mutates_args=(), device_types=_DEV)
+def dropout2d(x_nhwc: torch.Tensor, p: float, seed: int, offset: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """nn.Dropout2d(p) in train() mode on NHWC: (y, keep) with keep (B, C) = 0 or 1 / (1 - p), one Philox4x32-10 draw per (image, channel) at
+    (seed, offset) (vidc_dropout2d_mask; torch's own random stream is not reproduced), y = x * keep (vidc_scale_image_channels)."""
+    keep = _ops.dropout2d_mask(x_nhwc.shape[0], x_nhwc.shape[-1], p, seed, offset, x_nhwc.device)
+    return _ops.scale_image_channels(x_nhwc, keep), keep
+
+
+@dropout2d.register_fake
+def _(x_nhwc, p, seed, offset):
+    return x_nhwc.new_empty(x_nhwc.shape), x_nhwc.new_empty((x_nhwc.shape[0], x_nhwc.shape[-1]))
+
+
+def _dropout_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+    ctx.mark_non_differentiable(output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _dropout_backward(ctx, grad_y, _grad_keep):
+    return (torch.ops.vidc.scale_image_channels(grad_y, ctx.saved_tensors[0]) if grad_y is not None else None), None, None, None
+
+
+torch.library.register_autograd("vidc::dropout2d", _dropout_backward, setup_context=_dropout_setup)
+
+
+@torch.library.custom_op("vidc::normalize_nchw", mutates_args=(), device_types=_DEV)
+def normalize_nchw(x: torch.Tensor) -> torch.Tensor:
+    """F.normalize(x, dim=1) on NCHW (vidc_normalize_nchw; surface_normal_dorn.py:154)."""
+    return _ops.normalize_nchw(x)
+
+
+@normalize_nchw.register_fake
+def _(x):
+    return x.new_empty(x.shape)
+
+
+@torch.library.custom_op("vidc::normalize_nchw_backward", mutates_args=(), device_types=_DEV)
+def normalize_nchw_backward(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
+    """dx of normalize_nchw (vidc_normalize_nchw_backward): (dy - n (n . dy)) / |x|, and dy / eps where |x| < eps = 1e-12, as torch's."""
+    return _ops.normalize_nchw_backward(x, dy)
+
+
+@normalize_nchw_backward.register_fake
+def _(x, dy):
+    return x.new_empty(x.shape)
+
+
+def _normalize_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0])
+
+
+def _normalize_backward(ctx, grad_y):
+    return torch.ops.vidc.normalize_nchw_backward(ctx.saved_tensors[0], grad_y)
+
+
+torch.library.register_autograd("vidc::normalize_nchw", _normalize_backward, setup_context=_normalize_setup)
+
+
+@torch.library.custom_op("vidc::normal_l1_loss_with_grad", mutates_args=(), device_types=_DEV)
+def normal_l1_loss_with_grad(pred: torch.Tensor, normal_gt: torch.Tensor, mask: torch.Tensor,
+                             normalize_prediction: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(loss, count, angle, dpred): normal_l1_loss with the gradient the same vidc_normal_l1_loss call wrote -- what normal_l1_loss saves for its backward."""
+    sums, dpred = _ops.normal_l1_loss(pred, normal_gt, mask, normalize_prediction)
+    s32 = sums.float()                       # the kernel's fp64 sums, rounded once
+    return s32[0:1].clone(), s32[1:2].clone(), s32[2:3].clone(), dpred
+
+
+@normal_l1_loss_with_grad.register_fake
+def _(pred, normal_gt, mask, normalize_prediction):
+    return pred.new_empty((1,)), pred.new_empty((1,)), pred.new_empty((1,)), pred.new_empty(pred.shape)
+
+
+@torch.library.custom_op("vidc::normal_l1_loss_backward", mutates_args=(), device_types=_DEV)
+def normal_l1_loss_backward(dpred: torch.Tensor, grad_loss: torch.Tensor) -> torch.Tensor:
+    """dpred * grad_loss (a one-element tensor read on the device: no host read), through vidc_scale_image_channels."""
+    return _ops.scale_by_scalar(dpred, grad_loss)
+
+
+@normal_l1_loss_backward.register_fake
+def _(dpred, grad_loss):
+    return dpred.new_empty(dpred.shape)
+
+
+def _normal_loss_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[3])
+    ctx.set_materialize_grads(False)
+    ctx.mark_non_differentiable(output[1], output[2], output[3])
+
+
+def _normal_loss_backward(ctx, grad_loss, _gc, _ga, _gd):
+    if grad_loss is None:
+        return None, None, None, None
+    return torch.ops.vidc.normal_l1_loss_backward(ctx.saved_tensors[0], grad_loss), None, None, None      # (normal_gt and mask get no gradient)
+
+
+torch.library.register_autograd("vidc::normal_l1_loss_with_grad", _normal_loss_backward, setup_context=_normal_loss_setup)
+
+# normal_l1_loss(pred, normal_gt, mask, normalize_prediction) -> (loss, count, angle): the first three outputs of normal_l1_loss_with_grad.  Registered for
+# every backend as that composition, so its shape function, its GPU-only dispatch and its autograd formula are that operator's.
+torch.library.define("vidc::normal_l1_loss", "(Tensor pred, Tensor normal_gt, Tensor mask, bool normalize_prediction) -> (Tensor, Tensor, Tensor)")
+
+
+@torch.library.impl("vidc::normal_l1_loss", "CompositeImplicitAutograd")
+def normal_l1_loss(pred, normal_gt, mask, normalize_prediction):
+    """(loss, count, angle), float32 tensors of one element rounded from vidc_normal_l1_loss's fp64 sums (network_run.py:181-189): loss = the masked L1
+    distance to F.normalize(normal_gt) per masked pixel, differentiable in pred (backward: dpred * grad_loss, dpred written by the forward's one kernel
+    call); count = the masked pixels, angle = the summed angular error in degrees: not differentiable."""
+    loss, count, angle, _dpred = torch.ops.vidc.normal_l1_loss_with_grad(pred, normal_gt, mask, normalize_prediction)
+    return loss, count, angle
+
+
 BACKWARD_OPS = ("warp2dof_fwd_backward", "warp2dof_inv_rot_norm_backward", "conv2d_bn_act_backward", "stem_conv3x3s2_backward", "maxpool3x3s2_backward",
                 "upsample_bilinear_ac_backward", "head_conv1x1_upsample_backward")
 # the operators the scene-understanding module of SurfaceNormalDORN adds (a tuple of its own: BACKWARD_OPS keeps the seven of the first two networks)
@@ -630,3 +838,7 @@ DORN_OPS = ("conv2d_dilated_bn_act", "avgpool2d")
 DORN_BACKWARD_OPS = ("conv2d_dilated_bn_act_backward", "avgpool2d_backward")
 OPS = ("plane_ransac_normal", "plane_offset", "plane_project_depth", "plane_finalize", "enrich_scatter", "warp2dof_fwd", "warp2dof_inv_rot_norm", "conv2d_bn_act",
        "conv3x3_winograd", "stem_conv3x3s2", "maxpool3x3s2", "upsample_bilinear_ac", "head_conv1x1_upsample") + BACKWARD_OPS + DORN_OPS + DORN_BACKWARD_OPS
+# what SurfaceNormalDORN.forward_autograd and its loss add (tuples of their own again); scale_image_channels is its own backward and dropout2d's
+TRAIN_OPS = ("batch_norm_train", "dropout2d", "scale_image_channels", "normalize_nchw", "normal_l1_loss", "normal_l1_loss_with_grad")
+TRAIN_BACKWARD_OPS = ("batch_norm_train_backward", "normalize_nchw_backward", "normal_l1_loss_backward")
+OPS = OPS + TRAIN_OPS + TRAIN_BACKWARD_OPS
