@@ -756,6 +756,22 @@ int vidc_scale_image_channels(const float* x, const float* k, float* y, int B, i
  * gradient) -- the rule and the fp64 inner arithmetic of vidc_normal_l1_loss's own normalisation. */
 int vidc_normalize_nchw_backward(const float* x, const float* dy, float* dx, int B, int C, int HW, vidc_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Training ModifiedFPN and SurfaceNormalPrediction under autograd (their forward_autograd; csrc/net_train.hip).  The networks' layers are the
+ * entries above; the depth half of `_network_loss` with its logged ratios is the one addition.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* `_network_loss` (network_run.py:165-179) for the depth network in one pass: pred, depth_gt [B][H*W] fp32 (B x 1 x H x W); valid = depth_gt > 0.
+ * *loss = sum over valid of |pred - depth_gt| / (H*W); dpred [B][H*W] = its gradient: sign(pred - depth_gt) / (H*W) on valid pixels (0 where
+ * pred == depth_gt), 0 elsewhere -- per pixel the fp32 expressions of vidc_masked_l1_loss, so dpred has that entry's bits.  *count = the number of
+ * valid pixels; ratios[5] = the number of valid pixels with max(pred / depth_gt, depth_gt / pred) < t for t = 1.05, 1.10, 1.25, 1.25^2, 1.25^3
+ * (GetDepthPrintableRatios, network_run.py:72-82): the fp32 quotients against the thresholds rounded to fp32, as torch compares an fp32 tensor
+ * with a Python scalar; pred == 0 gives inf, which is below no threshold.  Sums in fp64: one partial row per chunk of 1024 pixels, then one
+ * workgroup in a fixed order -- no atomics, no host read, the same bits on every run.  scratch: vidc_depth_l1_loss_scratch_bytes, 8-byte aligned. */
+size_t vidc_depth_l1_loss_scratch_bytes(int B, int H, int W);
+int vidc_depth_l1_loss(const float* pred, const float* depth_gt, int B, int H, int W, double* loss, double* count, double* ratios, float* dpred,
+                       void* scratch, vidc_stream_t stream);
+
 enum vidc_op_kind { VIDC_OP_CONV = 1, VIDC_OP_STEM = 2, VIDC_OP_MAXPOOL = 3, VIDC_OP_UPSAMPLE = 4, VIDC_OP_HEAD = 5,
                     VIDC_OP_WARP_PARAMS = 6, VIDC_OP_WARP_FWD = 7, VIDC_OP_WARP_INV = 8, VIDC_OP_COPY = 9, VIDC_OP_SPLIT = 10,
                     VIDC_OP_AVGPOOL = 11, VIDC_OP_NORMALIZE = 12, VIDC_OP_DET_IM2COL = 13, VIDC_OP_NEAREST2X = 14,

@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""One training step of ModifiedFPN (--net depth) or SurfaceNormalPrediction (--net normal) under autograd: forward_autograd + the loss operator +
+backward() + torch.optim.Adam.step(), the reference's loop (network_run.py:231-254), at batch 8, 240x320 -- eager, at precision 0 (exact fp32 convs) and 1
+(bf16x3 forward) -- with the matching trainer's captured step (DepthCompletionTrainer / SurfaceNormalTrainer, in the arithmetic VIDC_TRAIN_PRECISION selects)
+timed beside it in the same process on the same inputs.  Timed like tools/dorn_train_step_bench.py: `--warmup` untimed steps, then wall clock over `--steps`
+steps (host enqueue time and time to the last kernel), and by HIP events the three regions of an autograd step: forward + loss, backward, Adam.
+
+    python tools/net_train_step_bench.py --net depth --batch 8 --steps 5                          # one JSON line
+    python tools/net_train_step_bench.py --net normal --batch 8 --use-mask                        # SurfaceNormalPrediction(use_mask=True): autograd only
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o net -- python tools/net_train_step_bench.py --net depth --precisions 0 --no-trainer
+    python tools/net_train_step_bench.py --kernel-stats OUT/.../net_kernel_stats.csv              # the per-kernel share table of that run (no GPU needed)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+DTYPES = {0: "f32 (fp32 MFMA fwd / dgrad / wgrad)", 1: "f32+bf16x3 forward, fp32 dgrad / wgrad"}
+
+
+def timed(step, steps, warmup, events=None):
+    """(ms per step, host enqueue ms per step, losses) of `steps` calls of step(marks) after `warmup` untimed ones."""
+    import torch
+    warm = [round(float(step(None)), 6) for _ in range(warmup)]
+    losses = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(steps):
+        losses.append(step(events[i] if events is not None else None))
+    t_enq = time.perf_counter() - t0          # host time to enqueue the steps (the GPU runs behind it when the step is GPU-bound)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    return 1e3 * dt / steps, 1e3 * t_enq / steps, warm + [round(float(x), 6) for x in losses]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--net", choices=("depth", "normal"), default="depth")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--precisions", default="0,1", help="the convs' arithmetic of the autograd steps to time: 0 exact fp32, 1 bf16x3 (default: both)")
+    ap.add_argument("--use-mask", action="store_true", help="--net normal: SurfaceNormalPrediction(use_mask=True), which only the autograd step trains")
+    ap.add_argument("--no-trainer", action="store_true", help="skip the trainer's step (a profile of the autograd step alone)")
+    ap.add_argument("--kernel-stats", help="a rocprofv3 --kernel-trace --stats CSV of a run of this script: print its share table and exit")
+    args = ap.parse_args()
+    if args.kernel_stats:
+        from dorn_train_step_bench import share_table
+        return share_table(args.kernel_stats)
+    import torch
+    from vi_depth_completion_amd import synthetic as S
+    from vi_depth_completion_amd import torch_ops  # noqa: F401  (registers torch.ops.vidc)
+    from vi_depth_completion_amd.networks.depth_completion import ModifiedFPN
+    from vi_depth_completion_amd.networks.surface_normal import SurfaceNormalPrediction
+    from vi_depth_completion_amd.training import DepthCompletionTrainer, SurfaceNormalTrainer
+    V = torch.ops.vidc
+    dev = torch.device("cuda", 0)
+    B = args.batch
+    b = S.synthetic_batch(B, 240, 320, 1234)
+    image = b["image"].to(dev)
+    if args.net == "depth":
+        make = ModifiedFPN
+        inputs = (image, torch.nn.functional.normalize(image - 0.5, dim=1), b["sparse_depth"].to(dev))
+        target = (S.synthetic_ground_truth_depth(b["image"], 1234).to(dev),)
+        loss_of = lambda out: V.depth_l1_loss(out, *target)[0]
+    else:
+        make = lambda: SurfaceNormalPrediction(use_mask=args.use_mask)
+        inputs = (image, b["gravity"].to(dev), b["aligned_direction"].to(dev))
+        target = ((S.normal01(1234, "sn.gt", (B, 3, 240, 320)).float() * 1.7).to(dev), (S.uniform01(1234, "sn.mask", (B, 240, 320)) < 0.7).float().to(dev))
+        loss_of = lambda out: V.normal_l1_loss(out, *target, True)[0]
+
+    def network():
+        cnn = make().to(dev)
+        cnn.load_state_dict(S.seeded_state_dict(cnn.state_dict(), 1234))          # (drawn on the CPU: no generator kernels in a profile of the step)
+        return cnn.train()
+
+    result = {"metric": "%s autograd training step" % ("ModifiedFPN" if args.net == "depth" else "SurfaceNormalPrediction"), "unit": "ms/step", "n_gpus": 1,
+              "batch_per_gpu": B, "use_mask": bool(args.use_mask), "autograd": {}}
+    for precision in [int(p) for p in args.precisions.split(",") if p != ""]:
+        cnn = network()
+        optimizer = torch.optim.Adam(cnn.parameters(), lr=1e-4)
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(args.steps)]
+
+        def step(marks):
+            mark = (lambda i: marks[i].record()) if marks is not None else (lambda i: None)
+            mark(0)
+            optimizer.zero_grad()
+            loss = loss_of(cnn.forward_autograd(*inputs, precision=precision))
+            mark(1)
+            loss.backward()
+            mark(2)
+            optimizer.step()
+            mark(3)
+            return loss.detach()
+
+        torch.cuda.reset_peak_memory_stats()
+        with torch.enable_grad():
+            ms, enq, losses = timed(step, args.steps, args.warmup, ev)
+        region = lambda a, c: round(sum(e[a].elapsed_time(e[c]) for e in ev) / args.steps, 2)
+        result["autograd"][str(precision)] = {"ms_per_step": round(ms, 1), "frames_per_s": round(1e3 * B / ms, 1), "host_enqueue_ms_per_step": round(enq, 1),
+                                              "forward_loss_ms": region(0, 1), "backward_ms": region(1, 2), "adam_ms": region(2, 3), "dtype": DTYPES[precision],
+                                              "losses": losses, "peak_memory_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
+        del cnn, optimizer, step
+        torch.cuda.empty_cache()
+    if not args.no_trainer and not args.use_mask:
+        with torch.no_grad():
+            tr = (DepthCompletionTrainer if args.net == "depth" else SurfaceNormalTrainer)(network(), 1e-4)
+            ms, enq, losses = timed(lambda _marks: tr.step(*inputs, *target), args.steps, max(args.warmup, 3))      # (the trainer captures its graph in its third step)
+        result["trainer"] = {"ms_per_step": round(ms, 1), "frames_per_s": round(1e3 * B / ms, 1), "host_enqueue_ms_per_step": round(enq, 1),
+                             "precision": os.environ.get("VIDC_TRAIN_PRECISION", "fp32"), "losses": losses}
+        for p, r in result["autograd"].items():
+            r["vs_trainer"] = round(r["ms_per_step"] / result["trainer"]["ms_per_step"], 2)
+    result["config"] = "forward_autograd + %s + backward() + torch.optim.Adam.step(), eager, 320x240, synthetic" % ("depth_l1_loss" if args.net == "depth" else "normal_l1_loss")
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()

@@ -181,6 +181,8 @@ SIGNATURES = {
     "vidc_dropout2d_mask": (C.c_int, [_vp, _i, _i, _f, C.c_ulonglong, C.c_ulonglong, _vp]),
     "vidc_scale_image_channels": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "vidc_normalize_nchw_backward": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "vidc_depth_l1_loss_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
+    "vidc_depth_l1_loss": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vidc_head_backward_multi_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
     "vidc_head_backward_multi": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vidc_clock_stamp": (C.c_int, [_vp, _vp]),

@@ -1,0 +1,97 @@
+"""The train() mode forward of the ResNet-101 pyramid and of the four-branch decoder from differentiable `torch.ops.vidc` operators, shared by
+`SurfaceNormalPrediction.forward_autograd` and `ModifiedFPN.forward_autograd` (the reference's networks/surface_normal.py:10-55, 73-145 and
+networks/depth_completion.py:16-65, 75-147 as `cnn.train()` runs them).
+
+Every conv is a conv2d_bn_act with scale 1 and the conv's bias (or 0) as shift; every BatchNorm2d a batch_norm_train on the batch statistics that
+updates the module's running statistics in place; the Bottleneck tail is batch_norm_train(residual=identity, relu=True); z1 + z2 + z3 + z4 is add_rows.
+Unlike the inference program (fpn_decoder.emit_branch) nothing is reordered: a train-mode BatchNorm does not commute with the upsample in front of it.
+Activations are NHWC; the module's own parameters and buffers are read, so any torch.optim optimizer steps them.
+"""
+import torch
+import torch.nn as nn
+
+
+class Walk:
+    """One forward pass: the constants the convs share, and the num_batches_tracked counters its BatchNorms touched (`finish` bumps them in one
+    launch, as nn.BatchNorm2d does one by one)."""
+
+    def __init__(self, who, device, precision):
+        if precision not in (0, 1):
+            raise RuntimeError("%s.forward_autograd: precision 0 (exact fp32) or 1 (bf16x3); the other conv modes have no backward" % who)
+        self.who, self.device, self.precision = who, device, precision
+        self.V = torch.ops.vidc
+        self._consts, self._counters = {}, []
+
+    def const(self, n, v):
+        if (n, v) not in self._consts:
+            self._consts[(n, v)] = torch.full((n,), v, dtype=torch.float32, device=self.device)
+        return self._consts[(n, v)]
+
+    def conv(self, t, m, relu=False):
+        co = m.out_channels
+        shift = m.bias if m.bias is not None else self.const(co, 0.0)
+        return self.V.conv2d_bn_act(t, m.weight, self.const(co, 1.0), shift, m.stride[0], m.padding[0], relu, self.precision)
+
+    def bn(self, t, m, relu, residual=None):
+        if m.momentum is None or not m.track_running_stats:
+            raise RuntimeError("%s.forward_autograd: BatchNorm2d with a momentum and running statistics only (the reference's)" % self.who)
+        self._counters.append(m.num_batches_tracked)
+        return self.V.batch_norm_train(t, m.weight, m.bias, m.running_mean, m.running_var, m.momentum, m.eps, relu, residual)[0]
+
+    def pyramid(self, x_nchw, rp):
+        """ResNetPyramids.forward in train() mode: x NCHW -> [x1..x4] NHWC."""
+        stem = rp.conv1
+        t = self.V.stem_conv3x3s2(x_nchw, stem.conv1_1.weight, True)                      # no BatchNorm behind conv1_1 (the reference's)
+        t = self.bn(self.conv(t, stem.conv1_2), stem.bn_2, True)
+        t = self.bn(self.bn(self.conv(t, stem.conv1_3), stem.bn1_3, True), rp.bn1, True)
+        t = self.V.maxpool3x3s2(t)
+        levels = []
+        for li in range(1, 5):
+            for blk in getattr(rp, "layer%d" % li):
+                u = self.bn(self.conv(t, blk.conv1), blk.bn1, True)
+                u = self.bn(self.conv(u, blk.conv2), blk.bn2, True)
+                idn = self.bn(self.conv(t, blk.downsample[0]), blk.downsample[1], False) if blk.downsample is not None else t
+                t = self.bn(self.conv(u, blk.conv3), blk.bn3, True, idn)
+            levels.append(t)
+        return levels
+
+    def branch(self, seq, t, level, sizes):
+        """feature{level}_upsamping: Conv2d + BatchNorm2d + ReLU triples, and UpsamplingBilinear2d to the size of the next finer pyramid level of
+        this input (the sizes the inference program uses; the reference's literals are those of 240 x 320)."""
+        mods = list(seq)
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            if isinstance(m, nn.Conv2d):
+                assert isinstance(mods[i + 1], nn.BatchNorm2d) and isinstance(mods[i + 2], nn.ReLU)
+                t = self.bn(self.conv(t, m), mods[i + 1], True)
+                i += 3
+            elif isinstance(m, nn.UpsamplingBilinear2d):
+                level -= 1
+                t = self.V.upsample_bilinear_ac(t, sizes[level][0], sizes[level][1], False)
+                i += 1
+            else:
+                raise TypeError(type(m))
+        return t
+
+    def decoder(self, module, levels):
+        """z1 + z2 + z3 + z4 (in that order) of module.feature{1..4}_upsamping over the pyramid levels [x1..x4]."""
+        sizes = {i + 1: (t.shape[1], t.shape[2]) for i, t in enumerate(levels)}
+        z = None
+        for b in (1, 2, 3, 4):
+            zb = self.branch(getattr(module, "feature%d_upsamping" % b), levels[b - 1], b, sizes)
+            z = zb if z is None else self.V.add_rows(z, zb, False)
+        return z
+
+    def finish(self):
+        torch._foreach_add_(self._counters, 1)                                            # every num_batches_tracked, one launch
+
+
+def check_train_inputs(module, *tensors):
+    who = type(module).__name__
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError("%s runs on the GPU only: there is no CPU/eager fallback" % who)
+    if not module.training:
+        raise RuntimeError("%s.forward_autograd is the train() mode forward; call .train() (eval(): forward)" % who)
+    return who

@@ -2,11 +2,16 @@
 `forward(image, normal, incomplete_depth)` and the same 2031 state_dict keys.  The three ResNet-101 pyramids run
 as ONE grouped launch per layer (groups = rgb, normal, depth) writing channel slices of a shared buffer, so
 `combine_rgbdn` (torch.cat, :151-152) is free; the 3x-wide decoder follows.
+
+Training: `DepthCompletionTrainer` (training.py) is the fast captured step; `forward_autograd(image, normal, incomplete_depth)` is the reference's
+forward in train() mode composed of differentiable `torch.ops.vidc` operators on the module's own parameters, for the reference's own loop and any
+torch.optim optimizer (gradients reach `normal` and `incomplete_depth`); `eval()` afterwards re-folds the updated weights for the inference program.
 """
 import torch
 import torch.nn as nn
 
 from .. import engine
+from . import autograd_blocks
 from .backbone import ResNetPyramids
 from .fpn_decoder import build_branch, emit_decoder
 from .surface_normal import _HipModule
@@ -17,6 +22,9 @@ def count_parameters(model):
 
 
 class ModifiedFPN(_HipModule):
+    _train_hint = (", or train the network with vi_depth_completion_amd.training.DepthCompletionTrainer, or under autograd with "
+                   "ModifiedFPN.forward_autograd (torch.ops.vidc operators)")
+
     def __init__(self, resnet_arch=101):
         super().__init__()
         self.resnet_rgb = ResNetPyramids(in_channels=3, pretrained=True, resnet_arch=resnet_arch)
@@ -68,3 +76,26 @@ class ModifiedFPN(_HipModule):
 
     def forward(self, image, normal, incomplete_depth):
         return self.enqueue(image, normal, incomplete_depth).clone()
+
+    # ---- training under autograd ---------------------------------------------------------------------------------------------------------
+    def forward_autograd(self, image, normal, incomplete_depth, precision=0):
+        """The reference's forward in train() mode (depth_completion.py:154-165) from torch.ops.vidc operators only: the three pyramids of
+        networks/autograd_blocks.py (train-mode BatchNorm: running statistics and num_batches_tracked updated as torch does; the depth pyramid's stem has one
+        input channel), combine_rgbdn as torch.cat per level in NHWC, the 3x-wide decoder branches, add_rows, feature_concat.0 with its ReLU, the
+        one-channel head (pad 1, ReLU).  Returns the depth (B, 1, H, W) with a grad_fn; gradients reach normal and incomplete_depth (and image) when they
+        require them.  precision: the convs' (0 exact fp32, 1 bf16x3)."""
+        who = autograd_blocks.check_train_inputs(self, image, normal, incomplete_depth)
+        B, _c, H, W = image.shape
+        if tuple(normal.shape) != (B, 3, H, W) or tuple(incomplete_depth.shape) != (B, 1, H, W) or image.shape[1] != 3:
+            raise ValueError("%s: image and normal (B,3,H,W), incomplete_depth (B,1,H,W); got %s, %s, %s"
+                             % (who, tuple(image.shape), tuple(normal.shape), tuple(incomplete_depth.shape)))
+        V = torch.ops.vidc
+        walk = autograd_blocks.Walk(who, image.device, precision)
+        self._autograd_dirty = True
+        pyramids = [walk.pyramid(t, rp) for t, rp in ((image, self.resnet_rgb), (normal, self.resnet_normal), (incomplete_depth, self.resnet_depth))]
+        levels = [torch.cat(per_level, dim=3) for per_level in zip(*pyramids)]               # combine_rgbdn, NHWC
+        z = walk.decoder(self, levels)
+        h = walk.conv(z, self.feature_concat[0], relu=True)
+        y = V.head_conv1x1_upsample(h, self.feature_concat[2].weight, self.feature_concat[2].bias, 1, H, W, True)
+        walk.finish()
+        return y

@@ -1,6 +1,10 @@
 """Drop-in for the reference's `SurfaceNormalPrediction` (networks/surface_normal.py:57-171): same constructor,
 `forward(x, gravity_tensor, alignment_tensor)` and the same 759 state_dict keys, executed as one HIP program:
 warp -> ResNet-101 pyramid -> 4-branch decoder -> head -> inverse warp + R^T + L2-normalise.
+
+Training: `SurfaceNormalTrainer` (training.py) is the fast captured step; `forward_autograd(x, gravity, aligned)` is the reference's forward in train()
+mode composed of differentiable `torch.ops.vidc` operators on the module's own parameters (use_mask included), for the reference's own loop and any
+torch.optim optimizer; `eval()` afterwards re-folds the updated weights for the inference program.
 """
 import os
 
@@ -10,6 +14,7 @@ import torch.nn as nn
 
 from .. import engine
 from .backbone import ResNetPyramids
+from . import autograd_blocks
 from .fpn_decoder import build_branch, emit_decoder
 from .warping_2dof_alignment import Warping2DOFAlignment
 
@@ -18,6 +23,7 @@ class _HipModule(nn.Module):
     """Shared plumbing: derived-weight cache invalidation and per-batch-size program cache."""
 
     _train_hint = ""           # appended to the train-mode refusal of forward(): where the module's training step lives, if it has one
+    _autograd_dirty = False    # a forward_autograd ran since the inference weights were folded (the optimizer steps the parameters behind the module's back)
 
     def _init_engine(self):
         self._weights = engine.WeightStore(self)
@@ -29,6 +35,13 @@ class _HipModule(nn.Module):
         self._weights.invalidate()
         self._programs.clear()
         self._version += 1
+
+    def train(self, mode=True):
+        super().train(mode)
+        if not mode and self._autograd_dirty:      # eval() after training steps under autograd: the folded weights and the programs are stale
+            self._invalidate()
+            self._autograd_dirty = False
+        return self
 
     def _apply(self, fn, *a, **k):
         r = super()._apply(fn, *a, **k)
@@ -67,7 +80,8 @@ class _HipModule(nn.Module):
 
 
 class SurfaceNormalPrediction(_HipModule):
-    _train_hint = ", or train the network with vi_depth_completion_amd.training.SurfaceNormalTrainer"
+    _train_hint = (", or train the network with vi_depth_completion_amd.training.SurfaceNormalTrainer, or under autograd with "
+                   "SurfaceNormalPrediction.forward_autograd (torch.ops.vidc operators)")
 
     def __init__(self, output_size=(240, 320), in_channels=3, training_mode="train_L2_loss",
                  fc_img=np.array([0.5 * 577.87061, 0.5 * 580.25851]),
@@ -131,3 +145,31 @@ class SurfaceNormalPrediction(_HipModule):
 
     def forward(self, x, gravity_tensor, alignment_tensor):
         return self.enqueue(x, gravity_tensor, alignment_tensor).clone()
+
+    # ---- training under autograd ---------------------------------------------------------------------------------------------------------
+    def forward_autograd(self, x, gravity_tensor, alignment_tensor, precision=0):
+        """The reference's forward in train() mode (surface_normal.py:147-171) from torch.ops.vidc operators only: warp2dof_fwd, the pyramid and the four
+        decoder branches of networks/autograd_blocks.py (train-mode BatchNorm: running statistics and num_batches_tracked updated as torch does), with
+        use_mask feature_mask_scale on the four levels and on their sum (the mask is detached, as there), add_rows, feature_concat.0 with its ReLU, the
+        three-channel head, warp2dof_inv_rot_norm(normalize=True).  Returns unit normals (B, 3, H, W) with a grad_fn; the gradient reaches x when it
+        requires one.  gravity / aligned get no gradient.  precision: the convs' (0 exact fp32, 1 bf16x3)."""
+        who = autograd_blocks.check_train_inputs(self, x, gravity_tensor, alignment_tensor)
+        wp = self.warp_2dof_alignment
+        if tuple(x.shape[1:]) != (self.resnet_pyramids.channel, wp.H, wp.W):
+            raise ValueError("%s was built for %s inputs, got %s" % (who, (self.resnet_pyramids.channel, wp.H, wp.W), tuple(x.shape[1:])))
+        V = torch.ops.vidc
+        walk = autograd_blocks.Walk(who, x.device, precision)
+        self._autograd_dirty = True
+        geom = (wp.fx, wp.fy, wp.cx, wp.cy, wp.align_corners)
+        xw = V.warp2dof_fwd(x, gravity_tensor, alignment_tensor, *geom)[1]
+        levels = walk.pyramid(xw, self.resnet_pyramids)
+        if self.use_mask:
+            image = xw.detach()
+            levels = [V.feature_mask_scale(t, image) for t in levels]
+        z = walk.decoder(self, levels)
+        if self.use_mask:
+            z = V.feature_mask_scale(z, image)
+        h = walk.conv(z, self.feature_concat[0], relu=True)
+        y = V.head_conv1x1_upsample(h, self.feature_concat[2].weight, self.feature_concat[2].bias, 0, wp.H, wp.W, False)
+        walk.finish()
+        return V.warp2dof_inv_rot_norm(y, gravity_tensor, alignment_tensor, *geom, True)[1]

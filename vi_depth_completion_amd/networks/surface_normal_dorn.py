@@ -88,15 +88,7 @@ class SurfaceNormalDORN(_HipModule):
         self.feature_extractor = ResNet(pretrained=pretrained)
         self.aspp_module = SceneUnderstandingModuleBN(output_channel=output_channel, mode=training_mode)
         self.dropout_step = 0              # forward_autograd calls so far: advances the dropout offsets, so that two steps with one seed do not repeat masks
-        self._autograd_dirty = False       # forward_autograd ran since the inference weights were folded
         self._init_engine()
-
-    def train(self, mode=True):
-        super().train(mode)
-        if not mode and getattr(self, "_autograd_dirty", False):      # eval() after training steps: the folded weights and the programs are stale
-            self._invalidate()
-            self._autograd_dirty = False
-        return self
 
     def build_program(self, B, H, W, device, dry_run=False):
         prog = engine.Program(self._weights, device, B)

@@ -726,3 +726,57 @@ def scale_by_scalar(x, s):
     y = torch.empty_like(flat)
     L.check(L.lib().vidc_scale_image_channels(L.ptr(flat), L.ptr(k), L.ptr(y), 1, flat.numel() // 4, 4, 4, 4, L.current_stream()), "scale_by_scalar")
     return y[:n].reshape(x.shape)
+
+
+# ---- training ModifiedFPN / SurfaceNormalPrediction under autograd (torch.ops.vidc's NET_TRAIN_OPS) ------------------------------------------
+def depth_l1_loss(pred, depth_gt):
+    """(sums float64 (7,) = loss, count, ratios[5]; dpred shaped like pred) of the depth half of `_network_loss`: one vidc_depth_l1_loss call.  pred and
+    depth_gt (B,1,H,W) or (B,H,W)."""
+    _dev(pred, depth_gt)
+    pred, gt = pred.contiguous().float(), depth_gt.contiguous().float()
+    if pred.dim() < 2 or gt.numel() != pred.numel() or tuple(gt.shape[-2:]) != tuple(pred.shape[-2:]):
+        raise RuntimeError("depth_l1_loss: pred and depth_gt (B,1,H,W) or (B,H,W) of one size; got %s, %s" % (tuple(pred.shape), tuple(depth_gt.shape)))
+    H, W = pred.shape[-2:]
+    B = pred.numel() // (H * W)
+    sums = torch.empty(7, dtype=torch.float64, device=pred.device)
+    dpred = torch.empty_like(pred)
+    sc = _scratch(L.lib().vidc_depth_l1_loss_scratch_bytes(B, H, W), pred.device)
+    L.check(L.lib().vidc_depth_l1_loss(L.ptr(pred), L.ptr(gt), B, H, W, L.ptr(sums), L.ptr(sums[1:]), L.ptr(sums[2:]), L.ptr(dpred), L.ptr(sc),
+                                       L.current_stream()), "depth_l1_loss")
+    return sums, dpred
+
+
+def feature_mask_scale(x, image):
+    """x NHWC (B,h,w,C) (dense or a channel slice) times the use_mask mask of surface_normal.py:151-162: (r + g + b > 1e-2) of image NCHW (B,3,H,W),
+    nearest-resized to (h, w) (vidc_mask_scale; the mask is never stored)."""
+    _dev(x, image)
+    img = image.contiguous().float()
+    if x.dim() != 4 or img.dim() != 4 or img.shape[1] != 3 or img.shape[0] != x.shape[0]:
+        raise RuntimeError("feature_mask_scale: x NHWC (B,h,w,C) and image NCHW (B,3,H,W); got %s, %s" % (tuple(x.shape), tuple(image.shape)))
+    B, h, w, Cc = x.shape
+    x, _m, _c, ldx = _rows(x)
+    y = torch.empty((B, h, w, Cc), dtype=torch.float32, device=x.device)
+    L.check(L.lib().vidc_mask_scale(L.ptr(x), L.ptr(img), L.ptr(y), B, h, w, Cc, ldx, Cc, img.shape[2], img.shape[3], L.current_stream()), "mask_scale")
+    return y
+
+
+def add_rows(a, b, relu=False):
+    """relu?(a + b) on NHWC rows (a, b: dense or channel slices); vidc_add_rows."""
+    _dev(a, b)
+    if a.shape != b.shape:
+        raise RuntimeError("add_rows: a %s and b %s" % (tuple(a.shape), tuple(b.shape)))
+    a, M, Cc, lda = _rows(a)
+    b, _m, _c, ldb = _rows(b)
+    y = torch.empty(a.shape, dtype=torch.float32, device=a.device)
+    L.check(L.lib().vidc_add_rows(L.ptr(a), L.ptr(b), L.ptr(y), M, Cc, lda, ldb, Cc, int(relu), L.current_stream()), "add_rows")
+    return y
+
+
+def relu_backward_rows(dy, y):
+    """dy * (y > 0) on NHWC rows (dy, y: dense or channel slices) -> dense; vidc_relu_backward."""
+    _dev(dy, y)
+    dy, M, Cc, lddy = _rows(dy)
+    y, _m, _c, ldy = _rows(y)
+    out = torch.empty(dy.shape, dtype=torch.float32, device=dy.device)
+    L.check(L.lib().vidc_relu_backward(L.ptr(dy), L.ptr(y), L.ptr(out), M, Cc, lddy, ldy, Cc, 0, L.current_stream()), "relu_backward")
+    return out

@@ -51,6 +51,16 @@ Training SurfaceNormalDORN (TRAIN_OPS / TRAIN_BACKWARD_OPS; SurfaceNormalDORN.fo
 batch_norm_train is nn.BatchNorm2d in train() mode (+ residual, + ReLU) on the trainers' kernels, updates the running statistics in place, and reads
 x in place when it is a channel slice; its backward, normalize_nchw's and the loss's are the custom operators of TRAIN_BACKWARD_OPS.
 The plane operators (`plane_*`, `enrich_scatter`) stay non-differentiable: they are RANSAC decisions and index scatters.
+
+Training ModifiedFPN and SurfaceNormalPrediction (NET_TRAIN_OPS / NET_TRAIN_BACKWARD_OPS; their forward_autograd and networks/autograd_blocks.py compose them with
+the operators above):
+
+    torch.ops.vidc.depth_l1_loss(pred, depth_gt) -> (loss, count, ratios)    network_run.py:165-179 (+ GetDepthPrintableRatios, :72-82: depth_printable_ratios)
+    torch.ops.vidc.feature_mask_scale(x_nhwc, image_nchw)                    surface_normal.py:151-162 (the use_mask multiply; image gets no gradient)
+    torch.ops.vidc.add_rows(a, b, relu)                                      z1 + z2 + z3 + z4 of both decoders
+
+depth_l1_loss is one vidc_depth_l1_loss call (csrc/net_train.hip: loss, its gradient, the valid count and the five ratio counts, fp64 sums in a fixed two-level
+order) registered like normal_l1_loss; feature_mask_scale is vidc_mask_scale and its own backward; add_rows is vidc_add_rows, its backward vidc_relu_backward.
 """
 from typing import Optional, Tuple
 
@@ -842,3 +852,132 @@ OPS = ("plane_ransac_normal", "plane_offset", "plane_project_depth", "plane_fina
 TRAIN_OPS = ("batch_norm_train", "dropout2d", "scale_image_channels", "normalize_nchw", "normal_l1_loss", "normal_l1_loss_with_grad")
 TRAIN_BACKWARD_OPS = ("batch_norm_train_backward", "normalize_nchw_backward", "normal_l1_loss_backward")
 OPS = OPS + TRAIN_OPS + TRAIN_BACKWARD_OPS
+
+
+# ---- training ModifiedFPN and SurfaceNormalPrediction under autograd: the depth loss, the use_mask multiply, the decoder's sum -----------------------
+@torch.library.custom_op("vidc::depth_l1_loss_with_grad", mutates_args=(), device_types=_DEV)
+def depth_l1_loss_with_grad(pred: torch.Tensor, depth_gt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(loss, count, ratios, dpred): depth_l1_loss with the gradient the same vidc_depth_l1_loss call wrote -- what depth_l1_loss saves for its backward."""
+    sums, dpred = _ops.depth_l1_loss(pred, depth_gt)
+    s32 = sums.float()                       # the kernel's fp64 sums, rounded once (the counts are integers below 2^24 for any batch of 240 x 320 images)
+    return s32[0:1].clone(), s32[1:2].clone(), s32[2:7].clone(), dpred
+
+
+@depth_l1_loss_with_grad.register_fake
+def _(pred, depth_gt):
+    return pred.new_empty((1,)), pred.new_empty((1,)), pred.new_empty((5,)), pred.new_empty(pred.shape)
+
+
+@torch.library.custom_op("vidc::depth_l1_loss_backward", mutates_args=(), device_types=_DEV)
+def depth_l1_loss_backward(dpred: torch.Tensor, grad_loss: torch.Tensor) -> torch.Tensor:
+    """dpred * grad_loss (a one-element tensor read on the device: no host read), through vidc_scale_image_channels."""
+    return _ops.scale_by_scalar(dpred, grad_loss)
+
+
+@depth_l1_loss_backward.register_fake
+def _(dpred, grad_loss):
+    return dpred.new_empty(dpred.shape)
+
+
+def _depth_loss_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[3])
+    ctx.set_materialize_grads(False)
+    ctx.mark_non_differentiable(output[1], output[2], output[3])
+
+
+def _depth_loss_backward(ctx, grad_loss, _gc, _gr, _gd):
+    if grad_loss is None:
+        return None, None
+    return torch.ops.vidc.depth_l1_loss_backward(ctx.saved_tensors[0], grad_loss), None      # (depth_gt gets no gradient)
+
+
+torch.library.register_autograd("vidc::depth_l1_loss_with_grad", _depth_loss_backward, setup_context=_depth_loss_setup)
+
+# depth_l1_loss(pred, depth_gt) -> (loss, count, ratios): the first three outputs of depth_l1_loss_with_grad, registered as that composition like normal_l1_loss.
+torch.library.define("vidc::depth_l1_loss", "(Tensor pred, Tensor depth_gt) -> (Tensor, Tensor, Tensor)")
+
+
+@torch.library.impl("vidc::depth_l1_loss", "CompositeImplicitAutograd")
+def depth_l1_loss(pred, depth_gt):
+    """(loss (1,), count (1,), ratios (5,)), float32 tensors rounded from vidc_depth_l1_loss's fp64 sums: the depth half of `_network_loss`
+    (network_run.py:165-179) on pred, depth_gt (B,1,H,W).  loss = the L1 distance summed over depth_gt > 0, divided by H * W: differentiable in pred
+    (backward: dpred * grad_loss, dpred written by the forward's one kernel call).  count = the valid pixels, ratios = those of them with
+    max(pred / gt, gt / pred) below 1.05, 1.10, 1.25, 1.25^2, 1.25^3: not differentiable; depth_printable_ratios turns them into the reference's dictionary."""
+    loss, count, ratios, _dpred = torch.ops.vidc.depth_l1_loss_with_grad(pred, depth_gt)
+    return loss, count, ratios
+
+
+RATIO_KEYS = ("D_1.05", "D_1.10", "D_1.25", "D_1.56", "D_1.95")
+
+
+def depth_printable_ratios(count, ratios):
+    """GetDepthPrintableRatios (network_run.py:72-82) from depth_l1_loss's count and ratios (tensors or numbers; tensors are read to the host here):
+    {'D_1.05': round(100 * c / (n + 1e-7), 1), ...}."""
+    n = float(count.reshape(-1)[0]) if torch.is_tensor(count) else float(count)
+    cs = ratios.reshape(-1).tolist() if torch.is_tensor(ratios) else list(ratios)
+    if len(cs) != len(RATIO_KEYS):
+        raise ValueError("depth_printable_ratios: %d counts for %d thresholds" % (len(cs), len(RATIO_KEYS)))
+    return {k: round(100 * float(c) / (n + 1e-7), 1) for k, c in zip(RATIO_KEYS, cs)}
+
+
+@torch.library.custom_op("vidc::feature_mask_scale", mutates_args=(), device_types=_DEV)
+def feature_mask_scale(x_nhwc: torch.Tensor, image_nchw: torch.Tensor) -> torch.Tensor:
+    """x * F.interpolate((r + g + b > 1e-2) of image, (h, w), mode="nearest") on NHWC x (B,h,w,C) -- the use_mask multiply of surface_normal.py:151-162
+    (vidc_mask_scale; the mask is never stored).  x may be a channel slice.  Its own backward on dy; the reference detaches the mask: image gets no gradient."""
+    return _ops.feature_mask_scale(x_nhwc, image_nchw)
+
+
+@feature_mask_scale.register_fake
+def _(x_nhwc, image_nchw):
+    return x_nhwc.new_empty(x_nhwc.shape)
+
+
+def _mask_scale_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[1])
+
+
+def _mask_scale_backward(ctx, grad_y):
+    return torch.ops.vidc.feature_mask_scale(grad_y, ctx.saved_tensors[0]), None
+
+
+torch.library.register_autograd("vidc::feature_mask_scale", _mask_scale_backward, setup_context=_mask_scale_setup)
+
+
+@torch.library.custom_op("vidc::add_rows", mutates_args=(), device_types=_DEV)
+def add_rows(a: torch.Tensor, b: torch.Tensor, relu: bool) -> torch.Tensor:
+    """relu?(a + b) on NHWC tensors of one shape (vidc_add_rows): z1 + z2 + z3 + z4 of both decoders.  a and b may be channel slices."""
+    return _ops.add_rows(a, b, relu)
+
+
+@add_rows.register_fake
+def _(a, b, relu):
+    return a.new_empty(a.shape)
+
+
+@torch.library.custom_op("vidc::add_rows_backward", mutates_args=(), device_types=_DEV)
+def add_rows_backward(dy: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """dy * (y > 0) (vidc_relu_backward): the gradient of both summands of add_rows(a, b, relu=True), y its output."""
+    return _ops.relu_backward_rows(dy, y)
+
+
+@add_rows_backward.register_fake
+def _(dy, y):
+    return dy.new_empty(dy.shape)
+
+
+def _add_rows_setup(ctx, inputs, output):
+    ctx.save_for_backward(output if inputs[2] else None)
+
+
+def _add_rows_backward(ctx, grad_y):
+    y = ctx.saved_tensors[0]
+    g = grad_y if y is None else torch.ops.vidc.add_rows_backward(grad_y, y)      # (without a ReLU the sum hands grad_y itself to both summands)
+    return (g if ctx.needs_input_grad[0] else None), (g if ctx.needs_input_grad[1] else None), None
+
+
+torch.library.register_autograd("vidc::add_rows", _add_rows_backward, setup_context=_add_rows_setup)
+
+# what ModifiedFPN.forward_autograd, SurfaceNormalPrediction.forward_autograd and the depth loss add (tuples of their own once more); feature_mask_scale is its own backward
+NET_TRAIN_OPS = ("depth_l1_loss", "depth_l1_loss_with_grad", "feature_mask_scale", "add_rows")
+NET_TRAIN_BACKWARD_OPS = ("depth_l1_loss_backward", "add_rows_backward")
+OPS = OPS + NET_TRAIN_OPS + NET_TRAIN_BACKWARD_OPS
