@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
-"""One training step of ModifiedFPN (--net depth) or SurfaceNormalPrediction (--net normal) under autograd: forward_autograd + the loss operator +
-backward() + torch.optim.Adam.step(), the reference's loop (network_run.py:231-254), at batch 8, 240x320 -- eager, at precision 0 (exact fp32 convs) and 1
-(bf16x3 forward) -- with the matching trainer's captured step (DepthCompletionTrainer / SurfaceNormalTrainer, in the arithmetic VIDC_TRAIN_PRECISION selects)
-timed beside it in the same process on the same inputs.  Timed like tools/dorn_train_step_bench.py: `--warmup` untimed steps, then wall clock over `--steps`
-steps (host enqueue time and time to the last kernel), and by HIP events the three regions of an autograd step: forward + loss, backward, Adam.
+"""One training step of ModifiedFPN (--net depth), SurfaceNormalPrediction (--net normal) or SurfaceNormalDORN (--net dorn) under autograd:
+forward_autograd + the loss operator + backward() + torch.optim.Adam.step(), the reference's loop (network_run.py:231-254), at batch 8, 240x320 -- eager, at
+precision 0 (exact fp32 convs) and 1 (bf16x3 forward) -- with the matching trainer's captured step (DepthCompletionTrainer / SurfaceNormalTrainer, in the
+arithmetic VIDC_TRAIN_PRECISION selects; SurfaceNormalDORN has no trainer) timed beside it in the same process on the same inputs.  Timed like
+tools/train_bench.py: `--warmup` untimed steps, then wall clock over `--steps` steps (host enqueue time and time to the last kernel), and by HIP events the
+three regions of an autograd step: forward + loss, backward, Adam.
 
     python tools/net_train_step_bench.py --net depth --batch 8 --steps 5                          # one JSON line
     python tools/net_train_step_bench.py --net normal --batch 8 --use-mask                        # SurfaceNormalPrediction(use_mask=True): autograd only
+    python tools/net_train_step_bench.py --net dorn --batch 8 --precisions 0                      # SurfaceNormalDORN, dropout_seed 1234: autograd only
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o net -- python tools/net_train_step_bench.py --net depth --precisions 0 --no-trainer
     python tools/net_train_step_bench.py --kernel-stats OUT/.../net_kernel_stats.csv              # the per-kernel share table of that run (no GPU needed)
-"""
+
+The share table groups the kernels of the profiled process (warm-up steps included: they are the same steps) into what the step spends its GPU
+time on -- convs, BatchNorm passes, per-call weight packing, weight-gradient operands, the transposed conv epilogue, torch's own kernels (Adam, cat,
+zero_grad) -- and lists the kernels above 1 %."""
 import argparse
+import csv
 import json
 import os
 import sys
@@ -18,9 +24,40 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 DTYPES = {0: "f32 (fp32 MFMA fwd / dgrad / wgrad)", 1: "f32+bf16x3 forward, fp32 dgrad / wgrad"}
+NETS = {"depth": ("ModifiedFPN", "depth_l1_loss"), "normal": ("SurfaceNormalPrediction", "normal_l1_loss"), "dorn": ("SurfaceNormalDORN", "normal_l1_loss")}
+
+GROUPS = (("BatchNorm passes", ("chan_partial_kernel", "chan_final_kernel", "bn_apply", "bn_bwd_apply")),
+          ("per-call weight packing", ("pack_weight", "pack_batched_kernel")),
+          ("weight-gradient operands / permute", ("im2col_t", "wgrad_permute_kernel", "transpose_bf16_kernel")),
+          ("transposed conv epilogue", ("affine_act_bwd_kernel",)),
+          ("ReLU mask / residual gradient", ("relu_bwd_kernel",)),
+          ("data-gradient zero stuffing", ("zero_stuff_kernel",)),
+          ("dropout, normalize, loss", ("dropout2d_mask_kernel", "scale_image_channels_kernel", "normalize_nchw", "normal_loss")),
+          ("stem, pools, upsample, head", ("stem_", "maxpool", "avgpool", "upsample", "head_")),
+          ("torch (Adam, cat, zero_grad, fills)", ("at::", "elementwise_kernel", "Memset", "Copy", "multi_tensor")),
+          ("convs (forward, data gradient, weight-gradient GEMM)", ("conv", "wgemm", "wgrad", "wino")))
+
+
+def share_table(path):
+    rows = [(r["Name"].replace("(anonymous namespace)::", ""), int(r["Calls"]), float(r["TotalDurationNs"])) for r in csv.DictReader(open(path))]
+    total = sum(t for _, _, t in rows)
+    sums = {g: [0, 0.0] for g, _ in GROUPS}
+    sums["other"] = [0, 0.0]
+    for name, calls, t in rows:
+        g = next((g for g, keys in GROUPS if any(k in name for k in keys)), "other")
+        sums[g][0] += calls
+        sums[g][1] += t
+    print("%-56s %9s %11s %7s" % ("group", "calls", "total ms", "%"))
+    for g, (calls, t) in sorted(sums.items(), key=lambda kv: -kv[1][1]):
+        print("%-56s %9d %11.2f %7.1f" % (g, calls, t / 1e6, 100.0 * t / total))
+    print("\n%-88s %9s %11s %7s %9s" % ("kernel (above 1 %)", "calls", "total ms", "%", "avg us"))
+    for name, calls, t in sorted(rows, key=lambda r: -r[2]):
+        if t < 0.01 * total:
+            break
+        print("%-88s %9d %11.2f %7.1f %9.1f" % (name.split("(")[0][:88], calls, t / 1e6, 100.0 * t / total, t / calls / 1e3))
+    print("total: %.1f ms of kernel time in the profiled process" % (total / 1e6))
 
 
 def timed(step, steps, warmup, events=None):
@@ -40,7 +77,7 @@ def timed(step, steps, warmup, events=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--net", choices=("depth", "normal"), default="depth")
+    ap.add_argument("--net", choices=tuple(NETS), default="depth")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -50,13 +87,13 @@ def main():
     ap.add_argument("--kernel-stats", help="a rocprofv3 --kernel-trace --stats CSV of a run of this script: print its share table and exit")
     args = ap.parse_args()
     if args.kernel_stats:
-        from dorn_train_step_bench import share_table
         return share_table(args.kernel_stats)
     import torch
     from vi_depth_completion_amd import synthetic as S
     from vi_depth_completion_amd import torch_ops  # noqa: F401  (registers torch.ops.vidc)
     from vi_depth_completion_amd.networks.depth_completion import ModifiedFPN
     from vi_depth_completion_amd.networks.surface_normal import SurfaceNormalPrediction
+    from vi_depth_completion_amd.networks.surface_normal_dorn import SurfaceNormalDORN
     from vi_depth_completion_amd.training import DepthCompletionTrainer, SurfaceNormalTrainer
     V = torch.ops.vidc
     dev = torch.device("cuda", 0)
@@ -68,18 +105,22 @@ def main():
         inputs = (image, torch.nn.functional.normalize(image - 0.5, dim=1), b["sparse_depth"].to(dev))
         target = (S.synthetic_ground_truth_depth(b["image"], 1234).to(dev),)
         loss_of = lambda out: V.depth_l1_loss(out, *target)[0]
+        forward_args = {}
     else:
-        make = lambda: SurfaceNormalPrediction(use_mask=args.use_mask)
-        inputs = (image, b["gravity"].to(dev), b["aligned_direction"].to(dev))
-        target = ((S.normal01(1234, "sn.gt", (B, 3, 240, 320)).float() * 1.7).to(dev), (S.uniform01(1234, "sn.mask", (B, 240, 320)) < 0.7).float().to(dev))
-        loss_of = lambda out: V.normal_l1_loss(out, *target, True)[0]
+        dorn = args.net == "dorn"
+        make = (lambda: SurfaceNormalDORN(pretrained=False)) if dorn else (lambda: SurfaceNormalPrediction(use_mask=args.use_mask))
+        inputs = (image,) if dorn else (image, b["gravity"].to(dev), b["aligned_direction"].to(dev))
+        forward_args = {"dropout_seed": 1234} if dorn else {}
+        target = ((S.normal01(1234, "sn.gt", (B, 3, 240, 320)).float() * 1.7).to(dev),
+                  (S.uniform01(1234, "sn.mask", (B, 1, 240, 320) if dorn else (B, 240, 320)) < 0.7).float().to(dev))
+        loss_of = lambda out: V.normal_l1_loss(out, *target, not dorn)[0]          # (SurfaceNormalDORN's output is normalized already)
 
     def network():
         cnn = make().to(dev)
         cnn.load_state_dict(S.seeded_state_dict(cnn.state_dict(), 1234))          # (drawn on the CPU: no generator kernels in a profile of the step)
         return cnn.train()
 
-    result = {"metric": "%s autograd training step" % ("ModifiedFPN" if args.net == "depth" else "SurfaceNormalPrediction"), "unit": "ms/step", "n_gpus": 1,
+    result = {"metric": "%s autograd training step" % NETS[args.net][0], "unit": "ms/step", "n_gpus": 1,
               "batch_per_gpu": B, "use_mask": bool(args.use_mask), "autograd": {}}
     for precision in [int(p) for p in args.precisions.split(",") if p != ""]:
         cnn = network()
@@ -90,7 +131,7 @@ def main():
             mark = (lambda i: marks[i].record()) if marks is not None else (lambda i: None)
             mark(0)
             optimizer.zero_grad()
-            loss = loss_of(cnn.forward_autograd(*inputs, precision=precision))
+            loss = loss_of(cnn.forward_autograd(*inputs, precision=precision, **forward_args))
             mark(1)
             loss.backward()
             mark(2)
@@ -107,7 +148,7 @@ def main():
                                               "losses": losses, "peak_memory_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
         del cnn, optimizer, step
         torch.cuda.empty_cache()
-    if not args.no_trainer and not args.use_mask:
+    if not args.no_trainer and not args.use_mask and args.net != "dorn":
         with torch.no_grad():
             tr = (DepthCompletionTrainer if args.net == "depth" else SurfaceNormalTrainer)(network(), 1e-4)
             ms, enq, losses = timed(lambda _marks: tr.step(*inputs, *target), args.steps, max(args.warmup, 3))      # (the trainer captures its graph in its third step)
@@ -115,7 +156,7 @@ def main():
                              "precision": os.environ.get("VIDC_TRAIN_PRECISION", "fp32"), "losses": losses}
         for p, r in result["autograd"].items():
             r["vs_trainer"] = round(r["ms_per_step"] / result["trainer"]["ms_per_step"], 2)
-    result["config"] = "forward_autograd + %s + backward() + torch.optim.Adam.step(), eager, 320x240, synthetic" % ("depth_l1_loss" if args.net == "depth" else "normal_l1_loss")
+    result["config"] = "forward_autograd + %s + backward() + torch.optim.Adam.step(), eager, 320x240, synthetic" % NETS[args.net][1]
     print(json.dumps(result))
 
 

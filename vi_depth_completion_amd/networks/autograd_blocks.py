@@ -1,9 +1,10 @@
-"""The train() mode forward of the ResNet-101 pyramid and of the four-branch decoder from differentiable `torch.ops.vidc` operators, shared by
-`SurfaceNormalPrediction.forward_autograd` and `ModifiedFPN.forward_autograd` (the reference's networks/surface_normal.py:10-55, 73-145 and
-networks/depth_completion.py:16-65, 75-147 as `cnn.train()` runs them).
+"""The train() mode forward of the ResNet-101 pyramid and of the four-branch decoder from differentiable `torch.ops.vidc` operators, shared by the
+`forward_autograd` of `SurfaceNormalPrediction`, `ModifiedFPN` and `SurfaceNormalDORN` (the reference's networks/surface_normal.py:10-55, 73-145,
+networks/depth_completion.py:16-65, 75-147 and networks/surface_normal_dorn.py:79-89, 130-141 as `cnn.train()` runs them).
 
-Every conv is a conv2d_bn_act with scale 1 and the conv's bias (or 0) as shift; every BatchNorm2d a batch_norm_train on the batch statistics that
-updates the module's running statistics in place; the Bottleneck tail is batch_norm_train(residual=identity, relu=True); z1 + z2 + z3 + z4 is add_rows.
+Every conv is a conv2d_bn_act (dilated: conv2d_dilated_bn_act) with scale 1 and the conv's bias (or 0) as shift; every BatchNorm2d a batch_norm_train on
+the batch statistics that updates the module's running statistics in place; the Bottleneck tail is batch_norm_train(residual=identity, relu=True);
+z1 + z2 + z3 + z4 is add_rows.
 Unlike the inference program (fpn_decoder.emit_branch) nothing is reordered: a train-mode BatchNorm does not commute with the upsample in front of it.
 Activations are NHWC; the module's own parameters and buffers are read, so any torch.optim optimizer steps them.
 """
@@ -30,7 +31,16 @@ class Walk:
     def conv(self, t, m, relu=False):
         co = m.out_channels
         shift = m.bias if m.bias is not None else self.const(co, 0.0)
+        if m.dilation[0] > 1:
+            return self.V.conv2d_dilated_bn_act(t, m.weight, self.const(co, 1.0), shift, m.padding[0], m.dilation[0], relu, self.precision)
         return self.V.conv2d_bn_act(t, m.weight, self.const(co, 1.0), shift, m.stride[0], m.padding[0], relu, self.precision)
+
+    def linear(self, t, m, relu=False):
+        """nn.Linear on t (B, h, w, c) flattened as NCHW, run as a 1x1 conv: the weight's (c, h, w) columns reordered to (h, w, c), as engine.linear."""
+        B, h, w, c = t.shape
+        wt = m.weight.view(-1, c, h, w).permute(0, 2, 3, 1).reshape(-1, h * w * c, 1, 1)
+        shift = m.bias if m.bias is not None else self.const(wt.shape[0], 0.0)
+        return self.V.conv2d_bn_act(t.reshape(B, 1, 1, -1), wt, self.const(wt.shape[0], 1.0), shift, 1, 0, relu, self.precision)
 
     def bn(self, t, m, relu, residual=None):
         if m.momentum is None or not m.track_running_stats:
@@ -87,11 +97,15 @@ class Walk:
         torch._foreach_add_(self._counters, 1)                                            # every num_batches_tracked, one launch
 
 
-def check_train_inputs(module, *tensors):
+def begin(module, tensors, precision):
+    """How every forward_autograd opens, after its own shape checks: refuse CPU tensors, eval() mode and a precision without a backward, and only then
+    mark the module's folded inference weights stale and hand out the pass's Walk."""
     who = type(module).__name__
     for t in tensors:
         if not t.is_cuda:
             raise RuntimeError("%s runs on the GPU only: there is no CPU/eager fallback" % who)
     if not module.training:
         raise RuntimeError("%s.forward_autograd is the train() mode forward; call .train() (eval(): forward)" % who)
-    return who
+    walk = Walk(who, tensors[0].device, precision)
+    module._autograd_dirty = True
+    return walk

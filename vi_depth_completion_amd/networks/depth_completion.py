@@ -84,14 +84,12 @@ class ModifiedFPN(_HipModule):
         input channel), combine_rgbdn as torch.cat per level in NHWC, the 3x-wide decoder branches, add_rows, feature_concat.0 with its ReLU, the
         one-channel head (pad 1, ReLU).  Returns the depth (B, 1, H, W) with a grad_fn; gradients reach normal and incomplete_depth (and image) when they
         require them.  precision: the convs' (0 exact fp32, 1 bf16x3)."""
-        who = autograd_blocks.check_train_inputs(self, image, normal, incomplete_depth)
         B, _c, H, W = image.shape
         if tuple(normal.shape) != (B, 3, H, W) or tuple(incomplete_depth.shape) != (B, 1, H, W) or image.shape[1] != 3:
             raise ValueError("%s: image and normal (B,3,H,W), incomplete_depth (B,1,H,W); got %s, %s, %s"
-                             % (who, tuple(image.shape), tuple(normal.shape), tuple(incomplete_depth.shape)))
-        V = torch.ops.vidc
-        walk = autograd_blocks.Walk(who, image.device, precision)
-        self._autograd_dirty = True
+                             % (type(self).__name__, tuple(image.shape), tuple(normal.shape), tuple(incomplete_depth.shape)))
+        walk = autograd_blocks.begin(self, (image, normal, incomplete_depth), precision)
+        V = walk.V
         pyramids = [walk.pyramid(t, rp) for t, rp in ((image, self.resnet_rgb), (normal, self.resnet_normal), (incomplete_depth, self.resnet_depth))]
         levels = [torch.cat(per_level, dim=3) for per_level in zip(*pyramids)]               # combine_rgbdn, NHWC
         z = walk.decoder(self, levels)

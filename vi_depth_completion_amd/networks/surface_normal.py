@@ -153,13 +153,11 @@ class SurfaceNormalPrediction(_HipModule):
         use_mask feature_mask_scale on the four levels and on their sum (the mask is detached, as there), add_rows, feature_concat.0 with its ReLU, the
         three-channel head, warp2dof_inv_rot_norm(normalize=True).  Returns unit normals (B, 3, H, W) with a grad_fn; the gradient reaches x when it
         requires one.  gravity / aligned get no gradient.  precision: the convs' (0 exact fp32, 1 bf16x3)."""
-        who = autograd_blocks.check_train_inputs(self, x, gravity_tensor, alignment_tensor)
         wp = self.warp_2dof_alignment
         if tuple(x.shape[1:]) != (self.resnet_pyramids.channel, wp.H, wp.W):
-            raise ValueError("%s was built for %s inputs, got %s" % (who, (self.resnet_pyramids.channel, wp.H, wp.W), tuple(x.shape[1:])))
-        V = torch.ops.vidc
-        walk = autograd_blocks.Walk(who, x.device, precision)
-        self._autograd_dirty = True
+            raise ValueError("%s was built for %s inputs, got %s" % (type(self).__name__, (self.resnet_pyramids.channel, wp.H, wp.W), tuple(x.shape[1:])))
+        walk = autograd_blocks.begin(self, (x, gravity_tensor, alignment_tensor), precision)
+        V = walk.V
         geom = (wp.fx, wp.fy, wp.cx, wp.cy, wp.align_corners)
         xw = V.warp2dof_fwd(x, gravity_tensor, alignment_tensor, *geom)[1]
         levels = walk.pyramid(xw, self.resnet_pyramids)

@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import engine
+from . import autograd_blocks
 from .backbone import _conv, _stage, STAGE_BLOCKS, STAGE_PLANES
 from .surface_normal import _HipModule
 
@@ -137,43 +138,21 @@ class SurfaceNormalDORN(_HipModule):
     def forward_autograd(self, x, dropout_seed=None, precision=0, _keeps=None):
         """The reference's forward in train() mode (surface_normal_dorn.py:18-30, 79-89, 130-154) from torch.ops.vidc operators only -- every conv a
         conv2d_bn_act with scale 1 and its bias (or 0) as shift, every BatchNorm a batch_norm_train on the batch statistics (running statistics and
-        num_batches_tracked updated as torch does), the Bottleneck tail batch_norm_train(residual=identity, relu=True) -- on the module's own
-        parameters and buffers; views, permutes and torch.cat are the only torch glue.  Returns unit normals (B, 3, H, W) with a grad_fn.
+        num_batches_tracked updated as torch does), the Bottleneck tail batch_norm_train(residual=identity, relu=True): the backbone is the pyramid walk
+        of networks/autograd_blocks.py, its last level feeds the scene-understanding module below -- on the module's own parameters and buffers; views,
+        permutes and torch.cat are the only torch glue.  Returns unit normals (B, 3, H, W) with a grad_fn.
 
         dropout_seed: the 64-bit Philox key of the three Dropout2d draws (default: drawn from torch's default generator at call time); layer l of
         call n draws at offset 4 * n + l (DROPOUT_OFFSETS, self.dropout_step).  precision: the convs' (0 exact fp32, 1 bf16x3).  _keeps (tests): the
         three (B, C) keep tables to use instead of drawing them."""
-        if not x.is_cuda:
-            raise RuntimeError("SurfaceNormalDORN runs on the GPU only: there is no CPU/eager fallback")
-        if not self.training:
-            raise RuntimeError("SurfaceNormalDORN.forward_autograd is the train() mode forward; call .train() (eval(): forward)")
-        B, _c, H, W = x.shape
+        H, W = x.shape[2:]
         if (H, W) != tuple(self.output_size):
             raise ValueError("SurfaceNormalDORN was built for %s inputs, got %s" % (tuple(self.output_size), (H, W)))
-        V = torch.ops.vidc
+        walk = autograd_blocks.begin(self, (x,), precision)
+        V, conv, bn = walk.V, walk.conv, walk.bn
         if dropout_seed is None:
             dropout_seed = int(torch.empty((), dtype=torch.int64).random_().item())
         step, self.dropout_step = self.dropout_step, self.dropout_step + 1
-        self._autograd_dirty = True
-        consts, counters = {}, []
-
-        def const(n, v):
-            if (n, v) not in consts:
-                consts[(n, v)] = torch.full((n,), v, dtype=torch.float32, device=x.device)
-            return consts[(n, v)]
-
-        def conv(t, m, relu=False):
-            co = m.out_channels
-            shift = m.bias if m.bias is not None else const(co, 0.0)
-            if m.dilation[0] > 1:
-                return V.conv2d_dilated_bn_act(t, m.weight, const(co, 1.0), shift, m.padding[0], m.dilation[0], relu, precision)
-            return V.conv2d_bn_act(t, m.weight, const(co, 1.0), shift, m.stride[0], m.padding[0], relu, precision)
-
-        def bn(t, m, relu, residual=None):
-            if m.momentum is None or not m.track_running_stats:
-                raise RuntimeError("SurfaceNormalDORN.forward_autograd: BatchNorm2d with a momentum and running statistics only (the reference's)")
-            counters.append(m.num_batches_tracked)
-            return V.batch_norm_train(t, m.weight, m.bias, m.running_mean, m.running_var, m.momentum, m.eps, relu, residual)[0]
 
         def dropout(t, name, i):
             if _keeps is not None:
@@ -181,27 +160,14 @@ class SurfaceNormalDORN(_HipModule):
             m = self.aspp_module.get_submodule(name)
             return V.dropout2d(t, m.p, dropout_seed, 4 * step + self.DROPOUT_OFFSETS[name])[0]
 
-        fe, sm = self.feature_extractor, self.aspp_module
-        stem = fe.conv1
-        t = V.stem_conv3x3s2(x, stem.conv1_1.weight, True)
-        t = bn(conv(t, stem.conv1_2), stem.bn_2, True)
-        t = bn(bn(conv(t, stem.conv1_3), stem.bn1_3, True), fe.bn1, True)
-        t = V.maxpool3x3s2(t)
-        for li in range(1, 5):
-            for blk in getattr(fe, "layer%d" % li):
-                u = bn(conv(t, blk.conv1), blk.bn1, True)
-                u = bn(conv(u, blk.conv2), blk.bn2, True)
-                idn = bn(conv(t, blk.downsample[0]), blk.downsample[1], False) if blk.downsample is not None else t
-                t = bn(conv(u, blk.conv3), blk.bn3, True, idn)
-        f = t                                                                                       # (B, H/8, W/8, 2048)
+        sm = self.aspp_module
+        f = walk.pyramid(x, self.feature_extractor)[-1]                                             # (B, H/8, W/8, 2048)
         enc = sm.encoder
         k, s, pd = enc.global_pooling.kernel_size, enc.global_pooling.stride, enc.global_pooling.padding
         pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)
         e = V.avgpool2d(f, *(pair(k) + pair(s) + pair(pd)))
         e = dropout(e, "encoder.dropout", 0)
-        _b, eh, ew, ec = e.shape
-        fc = enc.global_fc.weight.view(-1, ec, eh, ew).permute(0, 2, 3, 1).reshape(-1, eh * ew * ec, 1, 1)      # (c, h, w) columns -> (h, w, c), as engine.linear
-        e = V.conv2d_bn_act(e.reshape(B, 1, 1, -1), fc, const(fc.shape[0], 1.0), enc.global_fc.bias, 1, 0, True, precision)
+        e = walk.linear(e, enc.global_fc, relu=True)
         e = V.upsample_bilinear_ac(conv(e, enc.conv1), f.shape[1], f.shape[2], False)               # from 1x1: a broadcast
         branches = [e]
         for name in ("aspp1", "aspp2", "aspp3", "aspp4"):
@@ -212,5 +178,5 @@ class SurfaceNormalDORN(_HipModule):
         h = dropout(torch.cat(branches, dim=3), "concat_process.0", 1)
         h = dropout(conv(h, cp[1], relu=True), "concat_process.3", 2)
         y = V.head_conv1x1_upsample(h, cp[4].weight, cp[4].bias, 0, H, W, False)
-        torch._foreach_add_(counters, 1)                                                            # every num_batches_tracked, one launch
+        walk.finish()
         return V.normalize_nchw(y)

@@ -5,62 +5,70 @@ Every operator is registered for the GPU dispatch key only (`device_types="cuda"
 CPU tensors raises PyTorch's "no kernel for backend CPU" error -- there is deliberately no CPU implementation.  Shape
 functions (`register_fake`) are provided so the operators can be traced/exported; they allocate nothing on a device.
 
-The networks themselves do not dispatch through these (a network is ONE `vidc_program_run`/hipGraph replay, engine.py);
-the operators are the per-op surface for callers that compose the kernels with other PyTorch code:
+The networks' inference does not dispatch through these (a network is ONE `vidc_program_run`/hipGraph replay, engine.py); the operators are the
+per-op surface for callers that compose the kernels with other PyTorch code, and what the three networks' `forward_autograd` (with
+networks/autograd_blocks.py) are composed of.  OPS lists every name; the tuples at the end of the file group them by the layer that added them.
+
+Inference surface (differentiable where the Autograd section says so):
 
     torch.ops.vidc.warp2dof_fwd(x, g, a, fx, fy, cx, cy, align_corners)      warping_2dof_alignment.py:108-156
     torch.ops.vidc.warp2dof_inv_rot_norm(x, g, a, fx, fy, cx, cy, align_corners, normalize)   :216-255 (+ surface_normal.py:170)
-    torch.ops.vidc.conv2d_bn_act(x_nhwc, w_oihw, scale, shift, stride, pad, relu, precision)  Conv2d+BatchNorm2d(eval)+ReLU
-    torch.ops.vidc.conv3x3_winograd(x_nhwc, w_oihw, scale, shift, m, relu, precision)         the 3x3 / stride-1 layers as Winograd F(m x m, 3x3)
-    torch.ops.vidc.stem_conv3x3s2(x_nchw, w_oihw, relu)                       surface_normal.py:36 (conv1_1, no BN)
-    torch.ops.vidc.maxpool3x3s2(x_nhwc)                                       torchvision ResNet.maxpool
-    torch.ops.vidc.upsample_bilinear_ac(x_nhwc, Ho, Wo, relu)                 nn.UpsamplingBilinear2d (align_corners=True)
-    torch.ops.vidc.head_conv1x1_upsample(x_nhwc, w, bias, pad, Ho, Wo, relu)  depth_completion.py:141-147 / surface_normal.py:140-145
-    torch.ops.vidc.conv2d_dilated_bn_act(x_nhwc, w_oihw, scale, shift, pad, dilation, relu, precision)   surface_normal_dorn.py:45-68 (the ASPP branches)
-    torch.ops.vidc.avgpool2d(x_nhwc, kh, kw, sh, sw, ph, pw)                  surface_normal_dorn.py:10 (nn.AvgPool2d, count_include_pad=True)
     torch.ops.vidc.plane_ransac_normal(normals, ids, slots, hyp_pix)          main.py:38-62 (+ the write-back of :157)
     torch.ops.vidc.plane_offset(homo, depth, slots, inlier_mask, counts, scratch)       main.py:68-101, 162-173
     torch.ops.vidc.plane_project_depth(homo, slots, inlier_mask, scratch, records, plane_depth)   main.py:110-127
     torch.ops.vidc.plane_finalize(depth, plane_depth, records)                main.py:186-187 + the candidate counts of :287-289
     torch.ops.vidc.enrich_scatter(plane_depth, sparse_depth, sub, sub_offsets, chunk_base)        main.py:286, 290-294
-(the host-side draws that feed them -- np.random.permutation / randint in the reference's order -- are plane.draw_normal_hypotheses
+(the host-side draws that feed the plane operators -- np.random.permutation / randint in the reference's order -- are plane.draw_normal_hypotheses
 and plane.draw_enrichment; plane.PlaneBlock is the composition the pipeline uses)
 
-Autograd.  The first ten operators (the warps, the convs and the glue) are differentiable: each has a backward registered with
-`torch.library.register_autograd`, and each backward formula is itself a custom operator (`torch.ops.vidc.*_backward`, listed in
-BACKWARD_OPS and, for the two operators of SurfaceNormalDORN's scene-understanding module, DORN_BACKWARD_OPS) with a shape function, built
-from HIP kernels only -- the warp adjoints of csrc/warp.hip, vidc_affine_act_backward +
-zero-stuffing + the conv kernel on data-gradient weights + vidc_conv_wgrad for the convs (precision 0 and 1; Winograd forwards share the
-direct form's backward; the data gradient runs in exact fp32 except behind a Winograd forward at precision 1, where it runs in bf16x3 like
-the forward), the backward kernels of csrc/train.hip for the glue.  Gradients flow to images / activations, conv weights, the
-folded scale / shift and the head's bias; only those `ctx.needs_input_grad` asks for are computed, and nothing is saved when gradients are
-disabled.  `gravity` / `aligned` get no gradient (the warp record is built with cosf / atan2f / bbox min-max) and precision 3 (MXFP8) has no
-backward: requesting either raises.  The dilated conv's backward is the direct form's with stride 1: the data gradient is the conv kernel on
-the data-gradient weights with the same dilation and pad' = dilation * (k - 1) - pad, the weight gradient vidc_conv_wgrad_dilated; avgpool2d's
-is vidc_avgpool2d_backward.  The head's backward covers up to four output channels with pad 0 or 1 (vidc_head_backward_multi on B * Cout
-one-channel planes: the depth head, surface_normal.py:143 and surface_normal_dorn.py:74-75).  Double backward is not supported.
+Differentiable convs and glue (with the two warps: backward operators in BACKWARD_OPS; DORN_OPS / DORN_BACKWARD_OPS are the two operators of
+SurfaceNormalDORN's scene-understanding module and their backwards):
 
-Training SurfaceNormalDORN (TRAIN_OPS / TRAIN_BACKWARD_OPS; SurfaceNormalDORN.forward_autograd composes them with the operators above):
+    torch.ops.vidc.conv2d_bn_act(x_nhwc, w_oihw, scale, shift, stride, pad, relu, precision)  Conv2d+BatchNorm2d(eval)+ReLU
+    torch.ops.vidc.conv3x3_winograd(x_nhwc, w_oihw, scale, shift, m, relu, precision)         the 3x3 / stride-1 layers as Winograd F(m x m, 3x3)
+    torch.ops.vidc.conv2d_dilated_bn_act(x_nhwc, w_oihw, scale, shift, pad, dilation, relu, precision)   surface_normal_dorn.py:45-68 (the ASPP branches)
+    torch.ops.vidc.stem_conv3x3s2(x_nchw, w_oihw, relu)                       surface_normal.py:36 (conv1_1, no BN)
+    torch.ops.vidc.maxpool3x3s2(x_nhwc)                                       torchvision ResNet.maxpool
+    torch.ops.vidc.avgpool2d(x_nhwc, kh, kw, sh, sw, ph, pw)                  surface_normal_dorn.py:10 (nn.AvgPool2d, count_include_pad=True)
+    torch.ops.vidc.upsample_bilinear_ac(x_nhwc, Ho, Wo, relu)                 nn.UpsamplingBilinear2d (align_corners=True)
+    torch.ops.vidc.head_conv1x1_upsample(x_nhwc, w, bias, pad, Ho, Wo, relu)  depth_completion.py:141-147 / surface_normal.py:140-145
+
+Train-mode operators (TRAIN_OPS / TRAIN_BACKWARD_OPS, added for SurfaceNormalDORN; NET_TRAIN_OPS / NET_TRAIN_BACKWARD_OPS, added for ModifiedFPN and
+SurfaceNormalPrediction):
 
     torch.ops.vidc.batch_norm_train(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual=None) -> (y, save_mean, save_rstd)
     torch.ops.vidc.dropout2d(x_nhwc, p, seed, offset) -> (y, keep)           nn.Dropout2d in train() mode, Philox4x32-10 per (image, channel)
     torch.ops.vidc.scale_image_channels(x_nhwc, keep)                        y = x * keep[b][c]: Dropout2d for a given keep table; its own backward
     torch.ops.vidc.normalize_nchw(x)                                         F.normalize(x, dim=1), surface_normal_dorn.py:154
-    torch.ops.vidc.normal_l1_loss(pred, normal_gt, mask, normalize_prediction) -> (loss, count, angle)     network_run.py:181-189
-
-batch_norm_train is nn.BatchNorm2d in train() mode (+ residual, + ReLU) on the trainers' kernels, updates the running statistics in place, and reads
-x in place when it is a channel slice; its backward, normalize_nchw's and the loss's are the custom operators of TRAIN_BACKWARD_OPS.
-The plane operators (`plane_*`, `enrich_scatter`) stay non-differentiable: they are RANSAC decisions and index scatters.
-
-Training ModifiedFPN and SurfaceNormalPrediction (NET_TRAIN_OPS / NET_TRAIN_BACKWARD_OPS; their forward_autograd and networks/autograd_blocks.py compose them with
-the operators above):
-
-    torch.ops.vidc.depth_l1_loss(pred, depth_gt) -> (loss, count, ratios)    network_run.py:165-179 (+ GetDepthPrintableRatios, :72-82: depth_printable_ratios)
     torch.ops.vidc.feature_mask_scale(x_nhwc, image_nchw)                    surface_normal.py:151-162 (the use_mask multiply; image gets no gradient)
     torch.ops.vidc.add_rows(a, b, relu)                                      z1 + z2 + z3 + z4 of both decoders
 
-depth_l1_loss is one vidc_depth_l1_loss call (csrc/net_train.hip: loss, its gradient, the valid count and the five ratio counts, fp64 sums in a fixed two-level
-order) registered like normal_l1_loss; feature_mask_scale is vidc_mask_scale and its own backward; add_rows is vidc_add_rows, its backward vidc_relu_backward.
+batch_norm_train is nn.BatchNorm2d in train() mode (+ residual, + ReLU) on the trainers' kernels, updates the running statistics in place, and reads
+x in place when it is a channel slice.  feature_mask_scale is vidc_mask_scale and its own backward; add_rows is vidc_add_rows, its backward vidc_relu_backward.
+
+Losses (normal_l1_loss in TRAIN_OPS, depth_l1_loss in NET_TRAIN_OPS; both registered the same way, _register_l1_loss_backward):
+
+    torch.ops.vidc.normal_l1_loss(pred, normal_gt, mask, normalize_prediction) -> (loss, count, angle)     network_run.py:181-189
+    torch.ops.vidc.depth_l1_loss(pred, depth_gt) -> (loss, count, ratios)    network_run.py:165-179 (+ GetDepthPrintableRatios, :72-82: depth_printable_ratios)
+
+Each is one kernel call (vidc_normal_l1_loss of csrc/sn_train.hip; vidc_depth_l1_loss of csrc/net_train.hip: loss, its gradient, the valid count and the
+five ratio counts, fp64 sums in a fixed two-level order) that writes the loss's gradient beside the sums: `*_with_grad` returns it as a fourth output,
+and the loss operator is the first three outputs of that.
+
+Autograd.  The warps, the convs, the glue, the train-mode operators and the losses are differentiable: each has a backward registered with
+`torch.library.register_autograd` (batch_norm_train, which mutates its running statistics, through an autograd.Function), and each backward formula is
+itself a custom operator (`torch.ops.vidc.*_backward`, listed in the *_BACKWARD_OPS tuples) with a shape function, or the forward operator applied to
+the gradient (scale_image_channels, which is also dropout2d's backward, and feature_mask_scale), built from HIP kernels only -- the warp adjoints of
+csrc/warp.hip, vidc_affine_act_backward + zero-stuffing + the conv kernel on data-gradient weights + vidc_conv_wgrad for the convs (precision 0 and 1; Winograd forwards share the
+direct form's backward; the data gradient runs in exact fp32 except behind a Winograd forward at precision 1, where it runs in bf16x3 like
+the forward), the backward kernels of csrc/train.hip for the glue, batch_norm_train and normalize_nchw.  Gradients flow to images / activations, conv weights, the
+folded scale / shift and the head's bias; only those `ctx.needs_input_grad` asks for are computed, and nothing is saved when gradients are
+disabled.  `gravity` / `aligned` get no gradient (the warp record is built with cosf / atan2f / bbox min-max) and precision 3 (MXFP8) has no
+backward: requesting either raises.  The dilated conv's backward is the direct form's with stride 1: the data gradient is the conv kernel on
+the data-gradient weights with the same dilation and pad' = dilation * (k - 1) - pad, the weight gradient vidc_conv_wgrad_dilated; avgpool2d's
+is vidc_avgpool2d_backward.  The head's backward covers up to four output channels with pad 0 or 1 (vidc_head_backward_multi on B * Cout
+one-channel planes: the depth head, surface_normal.py:143 and surface_normal_dorn.py:74-75).  A loss's backward is dpred * grad_loss.  Double backward
+is not supported.  The plane operators (`plane_*`, `enrich_scatter`) stay non-differentiable: they are RANSAC decisions and index scatters.
 """
 from typing import Optional, Tuple
 
@@ -103,14 +111,18 @@ def _(x, gravity, aligned, fx, fy, cx, cy, align_corners, normalize):
     return x.new_empty((x.shape[0], 3, 3)), torch.empty_like(x)
 
 
+def _pack_for(precision):
+    """The weight packing of a conv precision (conv2d_bn_act's docstring); any other value packs exact fp32."""
+    return {1: _ops.pack_conv_weight_bf16x3, 2: _ops.pack_conv_weight_bf16, 3: _ops.pack_conv_weight_mxfp8}.get(precision, _ops.pack_conv_weight)
+
+
 @torch.library.custom_op("vidc::conv2d_bn_act", mutates_args=(), device_types=_DEV)
 def conv2d_bn_act(x_nhwc: torch.Tensor, w_oihw: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, stride: int, pad: int,
                   relu: bool, precision: int) -> torch.Tensor:
     """relu?(conv(x, w) * scale + shift) on NHWC activations; scale/shift = the folded bias + eval-mode BatchNorm
     (engine.fold_bn); precision 0 = exact fp32 MFMA, 1 = bf16x3, 2 = plain bf16 (input and weights rounded to bf16, fp32 accumulation;
     Cin % 64 == 0), 3 = MXFP8: the fp32 input is quantised and the weights packed block-scaled; the output is fp32 (vidc_conv_precision)."""
-    pack = {1: _ops.pack_conv_weight_bf16x3, 2: _ops.pack_conv_weight_bf16, 3: _ops.pack_conv_weight_mxfp8}.get(precision, _ops.pack_conv_weight)
-    return _ops.conv2d_bn_act(x_nhwc, pack(w_oihw), scale, shift, w_oihw.shape[2], w_oihw.shape[3], stride=stride, pad=pad,
+    return _ops.conv2d_bn_act(x_nhwc, _pack_for(precision)(w_oihw), scale, shift, w_oihw.shape[2], w_oihw.shape[3], stride=stride, pad=pad,
                               relu1=relu, precision=precision)
 
 
@@ -126,9 +138,8 @@ def conv2d_dilated_bn_act(x_nhwc: torch.Tensor, w_oihw: torch.Tensor, scale: tor
                           precision: int) -> torch.Tensor:
     """conv2d_bn_act for a dilated conv of stride 1 (the ASPP branches, surface_normal_dorn.py:45-68: Conv2d(2048, 512, 3, padding=d, dilation=d) +
     BatchNorm2d(eval) + ReLU, d = 6 / 12 / 18): tap (kh, kw) reads x[oy - pad + kh * dilation, ox - pad + kw * dilation]; precision as there."""
-    pack = {1: _ops.pack_conv_weight_bf16x3, 2: _ops.pack_conv_weight_bf16, 3: _ops.pack_conv_weight_mxfp8}.get(precision, _ops.pack_conv_weight)
-    return _ops.conv2d_bn_act(x_nhwc, pack(w_oihw), scale, shift, w_oihw.shape[2], w_oihw.shape[3], stride=1, pad=pad, relu1=relu, precision=precision,
-                              dilation=dilation)
+    return _ops.conv2d_bn_act(x_nhwc, _pack_for(precision)(w_oihw), scale, shift, w_oihw.shape[2], w_oihw.shape[3], stride=1, pad=pad, relu1=relu,
+                              precision=precision, dilation=dilation)
 
 
 @conv2d_dilated_bn_act.register_fake
@@ -404,6 +415,13 @@ def _conv_backward_body(what, dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, s
     return dx, dw, (dscale if need_affine else dy.new_empty(0)), (dshift if need_affine else dy.new_empty(0))
 
 
+def _conv_backward_shapes(dy, w_oihw, scale, shift, in_h, in_w, need_x, need_w, need_affine):
+    """The shape function of both conv backward operators: a gradient that is not needed is empty."""
+    empty = lambda: dy.new_empty(0)
+    return (dy.new_empty((dy.shape[0], in_h, in_w, w_oihw.shape[1])) if need_x else empty(), torch.empty_like(w_oihw) if need_w else empty(),
+            torch.empty_like(scale) if need_affine else empty(), torch.empty_like(shift) if need_affine else empty())
+
+
 @torch.library.custom_op("vidc::conv2d_bn_act_backward", mutates_args=(), device_types=_DEV)
 def conv2d_bn_act_backward(dy: torch.Tensor, x_nhwc: Optional[torch.Tensor], w_oihw: torch.Tensor, y: torch.Tensor, scale: torch.Tensor,
                            shift: torch.Tensor, in_h: int, in_w: int, stride: int, pad: int, relu: bool, precision: int, need_x: bool,
@@ -423,52 +441,7 @@ def conv2d_bn_act_backward(dy: torch.Tensor, x_nhwc: Optional[torch.Tensor], w_o
 
 @conv2d_bn_act_backward.register_fake
 def _(dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, stride, pad, relu, precision, need_x, need_w, need_affine, recompute_c):
-    empty = lambda: dy.new_empty(0)
-    return (dy.new_empty((dy.shape[0], in_h, in_w, w_oihw.shape[1])) if need_x else empty(), torch.empty_like(w_oihw) if need_w else empty(),
-            torch.empty_like(scale) if need_affine else empty(), torch.empty_like(shift) if need_affine else empty())
-
-
-def _conv_setup_common(ctx, what, x, w, scale, shift, y, stride, pad, relu, precision, needs, winograd=False):
-    if precision not in (0, 1):
-        raise RuntimeError("torch.ops.vidc.%s: precision %d (plain bf16 is 2, MXFP8 is 3) has no backward; use precision 0 or 1 for inputs that require a gradient"
-                           % (what, precision))
-    need_x, need_w, need_affine = needs[0], needs[1], needs[2] or needs[3]
-    ctx.save_for_backward(x if (need_w or need_affine) else None, w, y, scale, shift)      # (dscale re-runs the conv where a scale is 0)
-    dgrad_precision = precision if winograd else 0      # (see conv2d_bn_act_backward)
-    ctx.args = (x.shape[1], x.shape[2], stride, pad, relu, dgrad_precision, need_x, need_w, need_affine,
-                bool(needs[2] and (precision == 1 or winograd)))
-
-
-def _conv_grads(ctx, grad_y):
-    x, w, y, scale, shift = ctx.saved_tensors
-    dx, dw, dscale, dshift = torch.ops.vidc.conv2d_bn_act_backward(grad_y, x, w, y, scale, shift, *ctx.args)
-    return (_none_if_empty(dx), _none_if_empty(dw), dscale.reshape(scale.shape) if ctx.needs_input_grad[2] else None,
-            dshift.reshape(shift.shape) if ctx.needs_input_grad[3] else None)
-
-
-def _conv_setup(ctx, inputs, output):
-    x, w, scale, shift, stride, pad, relu, precision = inputs
-    _conv_setup_common(ctx, "conv2d_bn_act", x, w, scale, shift, output, stride, pad, relu, precision, ctx.needs_input_grad)
-
-
-def _conv_backward(ctx, grad_y):
-    return _conv_grads(ctx, grad_y) + (None,) * 4
-
-
-torch.library.register_autograd("vidc::conv2d_bn_act", _conv_backward, setup_context=_conv_setup)
-
-
-def _wino_setup(ctx, inputs, output):
-    x, w, scale, shift, m, relu, precision = inputs
-    # the gradient of a 3x3 conv does not care how the forward was evaluated: the direct form's backward with stride 1 / pad 1
-    _conv_setup_common(ctx, "conv3x3_winograd", x, w, scale, shift, output, 1, 1, relu, precision, ctx.needs_input_grad, winograd=True)
-
-
-def _wino_backward(ctx, grad_y):
-    return _conv_grads(ctx, grad_y) + (None,) * 3
-
-
-torch.library.register_autograd("vidc::conv3x3_winograd", _wino_backward, setup_context=_wino_setup)
+    return _conv_backward_shapes(dy, w_oihw, scale, shift, in_h, in_w, need_x, need_w, need_affine)
 
 
 @torch.library.custom_op("vidc::conv2d_dilated_bn_act_backward", mutates_args=(), device_types=_DEV)
@@ -485,9 +458,38 @@ def conv2d_dilated_bn_act_backward(dy: torch.Tensor, x_nhwc: Optional[torch.Tens
 
 @conv2d_dilated_bn_act_backward.register_fake
 def _(dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, pad, dilation, relu, precision, need_x, need_w, need_affine, recompute_c):
-    empty = lambda: dy.new_empty(0)
-    return (dy.new_empty((dy.shape[0], in_h, in_w, w_oihw.shape[1])) if need_x else empty(), torch.empty_like(w_oihw) if need_w else empty(),
-            torch.empty_like(scale) if need_affine else empty(), torch.empty_like(shift) if need_affine else empty())
+    return _conv_backward_shapes(dy, w_oihw, scale, shift, in_h, in_w, need_x, need_w, need_affine)
+
+
+def _conv_setup_common(ctx, what, x, w, scale, shift, y, geometry, relu, precision, needs, winograd=False):
+    """Saves what the backward operator reads and builds ctx.args, its arguments after the six tensors; geometry: its two after in_h, in_w -- (stride, pad), or
+    (pad, dilation) for the dilated operator."""
+    if precision not in (0, 1):
+        raise RuntimeError("torch.ops.vidc.%s: precision %d (plain bf16 is 2, MXFP8 is 3) has no backward; use precision 0 or 1 for inputs that require a gradient"
+                           % (what, precision))
+    need_x, need_w, need_affine = needs[0], needs[1], needs[2] or needs[3]
+    ctx.save_for_backward(x if (need_w or need_affine) else None, w, y, scale, shift)      # (dscale re-runs the conv where a scale is 0)
+    dgrad_precision = precision if winograd else 0      # (see conv2d_bn_act_backward)
+    ctx.args = (x.shape[1], x.shape[2]) + geometry + (relu, dgrad_precision, need_x, need_w, need_affine, bool(needs[2] and (precision == 1 or winograd)))
+
+
+def _conv_grads(ctx, grad_y, backward_op, n_other):
+    """The autograd tuple of a conv forward with n_other arguments behind x, w, scale, shift, from backward_op's four tensors."""
+    x, w, y, scale, shift = ctx.saved_tensors
+    dx, dw, dscale, dshift = backward_op(grad_y, x, w, y, scale, shift, *ctx.args)
+    return (_none_if_empty(dx), _none_if_empty(dw), dscale.reshape(scale.shape) if ctx.needs_input_grad[2] else None,
+            dshift.reshape(shift.shape) if ctx.needs_input_grad[3] else None) + (None,) * n_other
+
+
+def _conv_setup(ctx, inputs, output):
+    x, w, scale, shift, stride, pad, relu, precision = inputs
+    _conv_setup_common(ctx, "conv2d_bn_act", x, w, scale, shift, output, (stride, pad), relu, precision, ctx.needs_input_grad)
+
+
+def _wino_setup(ctx, inputs, output):
+    x, w, scale, shift, m, relu, precision = inputs
+    # the gradient of a 3x3 conv does not care how the forward was evaluated: the direct form's backward with stride 1 / pad 1
+    _conv_setup_common(ctx, "conv3x3_winograd", x, w, scale, shift, output, (1, 1), relu, precision, ctx.needs_input_grad, winograd=True)
 
 
 def _dilated_setup(ctx, inputs, output):
@@ -495,19 +497,13 @@ def _dilated_setup(ctx, inputs, output):
     if w.shape[2] != w.shape[3] or dilation < 1 or dilation * (w.shape[2] - 1) - pad < 0:
         raise RuntimeError("torch.ops.vidc.conv2d_dilated_bn_act: the backward covers square kernels with pad <= dilation * (k - 1) (got %dx%d, pad %d, "
                            "dilation %d)" % (w.shape[2], w.shape[3], pad, dilation))
-    _conv_setup_common(ctx, "conv2d_dilated_bn_act", x, w, scale, shift, output, 1, pad, relu, precision, ctx.needs_input_grad)
-    in_h, in_w, _stride, pad_, *rest = ctx.args
-    ctx.args = (in_h, in_w, pad_, dilation) + tuple(rest)
+    _conv_setup_common(ctx, "conv2d_dilated_bn_act", x, w, scale, shift, output, (pad, dilation), relu, precision, ctx.needs_input_grad)
 
 
-def _dilated_backward(ctx, grad_y):
-    x, w, y, scale, shift = ctx.saved_tensors
-    dx, dw, dscale, dshift = torch.ops.vidc.conv2d_dilated_bn_act_backward(grad_y, x, w, y, scale, shift, *ctx.args)
-    return (_none_if_empty(dx), _none_if_empty(dw), dscale.reshape(scale.shape) if ctx.needs_input_grad[2] else None,
-            dshift.reshape(shift.shape) if ctx.needs_input_grad[3] else None) + (None,) * 4
-
-
-torch.library.register_autograd("vidc::conv2d_dilated_bn_act", _dilated_backward, setup_context=_dilated_setup)
+torch.library.register_autograd("vidc::conv2d_bn_act", lambda ctx, g: _conv_grads(ctx, g, torch.ops.vidc.conv2d_bn_act_backward, 4), setup_context=_conv_setup)
+torch.library.register_autograd("vidc::conv3x3_winograd", lambda ctx, g: _conv_grads(ctx, g, torch.ops.vidc.conv2d_bn_act_backward, 3), setup_context=_wino_setup)
+torch.library.register_autograd("vidc::conv2d_dilated_bn_act", lambda ctx, g: _conv_grads(ctx, g, torch.ops.vidc.conv2d_dilated_bn_act_backward, 4),
+                                setup_context=_dilated_setup)
 
 
 @torch.library.custom_op("vidc::stem_conv3x3s2_backward", mutates_args=(), device_types=_DEV)
@@ -788,6 +784,33 @@ def _normalize_backward(ctx, grad_y):
 torch.library.register_autograd("vidc::normalize_nchw", _normalize_backward, setup_context=_normalize_setup)
 
 
+def _scale_dpred(dpred: torch.Tensor, grad_loss: torch.Tensor) -> torch.Tensor:
+    """dpred * grad_loss (a one-element tensor read on the device: no host read), through vidc_scale_image_channels."""
+    return _ops.scale_by_scalar(dpred, grad_loss)
+
+
+def _loss_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[3])
+    ctx.set_materialize_grads(False)
+    ctx.mark_non_differentiable(output[1], output[2], output[3])
+
+
+def _register_l1_loss_backward(name, n_inputs):
+    """What normal_l1_loss and depth_l1_loss share behind vidc::`name`_with_grad -> (loss, two statistics, dpred): the operator vidc::`name`_backward
+    (_scale_dpred), and the autograd formula that hands it the saved dpred and the loss's gradient; only pred, the first of the n_inputs, gets a gradient."""
+    op = torch.library.custom_op("vidc::%s_backward" % name, _scale_dpred, mutates_args=(), device_types=_DEV)
+    op.register_fake(lambda dpred, grad_loss: dpred.new_empty(dpred.shape))
+    packet = getattr(torch.ops.vidc, "%s_backward" % name)
+
+    def backward(ctx, grad_loss, _g1, _g2, _gd):
+        if grad_loss is None:
+            return (None,) * n_inputs
+        return (packet(ctx.saved_tensors[0], grad_loss),) + (None,) * (n_inputs - 1)
+
+    torch.library.register_autograd("vidc::%s_with_grad" % name, backward, setup_context=_loss_setup)
+    return op
+
+
 @torch.library.custom_op("vidc::normal_l1_loss_with_grad", mutates_args=(), device_types=_DEV)
 def normal_l1_loss_with_grad(pred: torch.Tensor, normal_gt: torch.Tensor, mask: torch.Tensor,
                              normalize_prediction: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -802,30 +825,7 @@ def _(pred, normal_gt, mask, normalize_prediction):
     return pred.new_empty((1,)), pred.new_empty((1,)), pred.new_empty((1,)), pred.new_empty(pred.shape)
 
 
-@torch.library.custom_op("vidc::normal_l1_loss_backward", mutates_args=(), device_types=_DEV)
-def normal_l1_loss_backward(dpred: torch.Tensor, grad_loss: torch.Tensor) -> torch.Tensor:
-    """dpred * grad_loss (a one-element tensor read on the device: no host read), through vidc_scale_image_channels."""
-    return _ops.scale_by_scalar(dpred, grad_loss)
-
-
-@normal_l1_loss_backward.register_fake
-def _(dpred, grad_loss):
-    return dpred.new_empty(dpred.shape)
-
-
-def _normal_loss_setup(ctx, inputs, output):
-    ctx.save_for_backward(output[3])
-    ctx.set_materialize_grads(False)
-    ctx.mark_non_differentiable(output[1], output[2], output[3])
-
-
-def _normal_loss_backward(ctx, grad_loss, _gc, _ga, _gd):
-    if grad_loss is None:
-        return None, None, None, None
-    return torch.ops.vidc.normal_l1_loss_backward(ctx.saved_tensors[0], grad_loss), None, None, None      # (normal_gt and mask get no gradient)
-
-
-torch.library.register_autograd("vidc::normal_l1_loss_with_grad", _normal_loss_backward, setup_context=_normal_loss_setup)
+normal_l1_loss_backward = _register_l1_loss_backward("normal_l1_loss", 4)      # (normal_gt and mask get no gradient)
 
 # normal_l1_loss(pred, normal_gt, mask, normalize_prediction) -> (loss, count, angle): the first three outputs of normal_l1_loss_with_grad.  Registered for
 # every backend as that composition, so its shape function, its GPU-only dispatch and its autograd formula are that operator's.
@@ -840,18 +840,6 @@ def normal_l1_loss(pred, normal_gt, mask, normalize_prediction):
     loss, count, angle, _dpred = torch.ops.vidc.normal_l1_loss_with_grad(pred, normal_gt, mask, normalize_prediction)
     return loss, count, angle
 
-
-BACKWARD_OPS = ("warp2dof_fwd_backward", "warp2dof_inv_rot_norm_backward", "conv2d_bn_act_backward", "stem_conv3x3s2_backward", "maxpool3x3s2_backward",
-                "upsample_bilinear_ac_backward", "head_conv1x1_upsample_backward")
-# the operators the scene-understanding module of SurfaceNormalDORN adds (a tuple of its own: BACKWARD_OPS keeps the seven of the first two networks)
-DORN_OPS = ("conv2d_dilated_bn_act", "avgpool2d")
-DORN_BACKWARD_OPS = ("conv2d_dilated_bn_act_backward", "avgpool2d_backward")
-OPS = ("plane_ransac_normal", "plane_offset", "plane_project_depth", "plane_finalize", "enrich_scatter", "warp2dof_fwd", "warp2dof_inv_rot_norm", "conv2d_bn_act",
-       "conv3x3_winograd", "stem_conv3x3s2", "maxpool3x3s2", "upsample_bilinear_ac", "head_conv1x1_upsample") + BACKWARD_OPS + DORN_OPS + DORN_BACKWARD_OPS
-# what SurfaceNormalDORN.forward_autograd and its loss add (tuples of their own again); scale_image_channels is its own backward and dropout2d's
-TRAIN_OPS = ("batch_norm_train", "dropout2d", "scale_image_channels", "normalize_nchw", "normal_l1_loss", "normal_l1_loss_with_grad")
-TRAIN_BACKWARD_OPS = ("batch_norm_train_backward", "normalize_nchw_backward", "normal_l1_loss_backward")
-OPS = OPS + TRAIN_OPS + TRAIN_BACKWARD_OPS
 
 
 # ---- training ModifiedFPN and SurfaceNormalPrediction under autograd: the depth loss, the use_mask multiply, the decoder's sum -----------------------
@@ -868,30 +856,7 @@ def _(pred, depth_gt):
     return pred.new_empty((1,)), pred.new_empty((1,)), pred.new_empty((5,)), pred.new_empty(pred.shape)
 
 
-@torch.library.custom_op("vidc::depth_l1_loss_backward", mutates_args=(), device_types=_DEV)
-def depth_l1_loss_backward(dpred: torch.Tensor, grad_loss: torch.Tensor) -> torch.Tensor:
-    """dpred * grad_loss (a one-element tensor read on the device: no host read), through vidc_scale_image_channels."""
-    return _ops.scale_by_scalar(dpred, grad_loss)
-
-
-@depth_l1_loss_backward.register_fake
-def _(dpred, grad_loss):
-    return dpred.new_empty(dpred.shape)
-
-
-def _depth_loss_setup(ctx, inputs, output):
-    ctx.save_for_backward(output[3])
-    ctx.set_materialize_grads(False)
-    ctx.mark_non_differentiable(output[1], output[2], output[3])
-
-
-def _depth_loss_backward(ctx, grad_loss, _gc, _gr, _gd):
-    if grad_loss is None:
-        return None, None
-    return torch.ops.vidc.depth_l1_loss_backward(ctx.saved_tensors[0], grad_loss), None      # (depth_gt gets no gradient)
-
-
-torch.library.register_autograd("vidc::depth_l1_loss_with_grad", _depth_loss_backward, setup_context=_depth_loss_setup)
+depth_l1_loss_backward = _register_l1_loss_backward("depth_l1_loss", 2)      # (depth_gt gets no gradient)
 
 # depth_l1_loss(pred, depth_gt) -> (loss, count, ratios): the first three outputs of depth_l1_loss_with_grad, registered as that composition like normal_l1_loss.
 torch.library.define("vidc::depth_l1_loss", "(Tensor pred, Tensor depth_gt) -> (Tensor, Tensor, Tensor)")
@@ -905,9 +870,6 @@ def depth_l1_loss(pred, depth_gt):
     max(pred / gt, gt / pred) below 1.05, 1.10, 1.25, 1.25^2, 1.25^3: not differentiable; depth_printable_ratios turns them into the reference's dictionary."""
     loss, count, ratios, _dpred = torch.ops.vidc.depth_l1_loss_with_grad(pred, depth_gt)
     return loss, count, ratios
-
-
-RATIO_KEYS = ("D_1.05", "D_1.10", "D_1.25", "D_1.56", "D_1.95")
 
 
 def depth_printable_ratios(count, ratios):
@@ -977,7 +939,21 @@ def _add_rows_backward(ctx, grad_y):
 
 torch.library.register_autograd("vidc::add_rows", _add_rows_backward, setup_context=_add_rows_setup)
 
-# what ModifiedFPN.forward_autograd, SurfaceNormalPrediction.forward_autograd and the depth loss add (tuples of their own once more); feature_mask_scale is its own backward
+
+# ---- the operator names, by the layer that added them (tests and INTEGRATION.md pin every tuple) -------------------------------------------------
+# the backward operators of the warps, the convs and the glue
+BACKWARD_OPS = ("warp2dof_fwd_backward", "warp2dof_inv_rot_norm_backward", "conv2d_bn_act_backward", "stem_conv3x3s2_backward", "maxpool3x3s2_backward",
+                "upsample_bilinear_ac_backward", "head_conv1x1_upsample_backward")
+# the scene-understanding module of SurfaceNormalDORN
+DORN_OPS = ("conv2d_dilated_bn_act", "avgpool2d")
+DORN_BACKWARD_OPS = ("conv2d_dilated_bn_act_backward", "avgpool2d_backward")
+# SurfaceNormalDORN.forward_autograd and its loss; scale_image_channels is its own backward and dropout2d's
+TRAIN_OPS = ("batch_norm_train", "dropout2d", "scale_image_channels", "normalize_nchw", "normal_l1_loss", "normal_l1_loss_with_grad")
+TRAIN_BACKWARD_OPS = ("batch_norm_train_backward", "normalize_nchw_backward", "normal_l1_loss_backward")
+# ModifiedFPN.forward_autograd, SurfaceNormalPrediction.forward_autograd and the depth loss; feature_mask_scale is its own backward
 NET_TRAIN_OPS = ("depth_l1_loss", "depth_l1_loss_with_grad", "feature_mask_scale", "add_rows")
 NET_TRAIN_BACKWARD_OPS = ("depth_l1_loss_backward", "add_rows_backward")
-OPS = OPS + NET_TRAIN_OPS + NET_TRAIN_BACKWARD_OPS
+OPS = (("plane_ransac_normal", "plane_offset", "plane_project_depth", "plane_finalize", "enrich_scatter", "warp2dof_fwd", "warp2dof_inv_rot_norm", "conv2d_bn_act",
+        "conv3x3_winograd", "stem_conv3x3s2", "maxpool3x3s2", "upsample_bilinear_ac", "head_conv1x1_upsample")
+       + BACKWARD_OPS + DORN_OPS + DORN_BACKWARD_OPS + TRAIN_OPS + TRAIN_BACKWARD_OPS + NET_TRAIN_OPS + NET_TRAIN_BACKWARD_OPS)
+RATIO_KEYS = ("D_1.05", "D_1.10", "D_1.25", "D_1.56", "D_1.95")      # depth_l1_loss's five ratio counts, as depth_printable_ratios names them
