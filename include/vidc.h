@@ -460,6 +460,35 @@ int vidc_normal_metrics(const float* pred, const float* gt, const float* mask, i
  * hi_filter.  Two passes select any order statistic (the reference's np.median) exactly; the counts sum over batches and ranks. */
 int vidc_hist_u16(const float* vals, long long n, int hi_filter, uint32_t* hist, vidc_stream_t stream);
 
+/* The output images as PNG FILES, encoded on the device (SaveDepthsToImage / SaveNormalsToImage / SaveRgbToImage / SaveMasksToImage,
+ * network_run.py:32-69): what is left to the host is one copy and open().write().  All conversions are fp32 with truncation toward zero
+ * (ndarray.astype), each product and sum rounded on its own like numpy's.  Inputs outside the stated range (and NaN, which gives 0) are
+ * clamped as written; what Pillow would do with them is not part of the contract. */
+enum vidc_png_format {
+    VIDC_PNG_DEPTH16_F32 = 0, /* [B][H][W] fp32 metres (finite, below 2 147 483 m) -> 16-bit gray, big-endian: the millimetres of
+                                 vidc_depth_to_mm_u32 (d * 1000, <= 0 -> 0), then min(mm, 65535) as Pillow saturates mode I to I;16 */
+    VIDC_PNG_NORMAL8_F32 = 1, /* [B][3][H][W] fp32 planar, |n| <= 1 -> 8-bit RGB: t = (1 + n) * 127.5; t <= 0 -> 0, t >= 255 -> 255 */
+    VIDC_PNG_RGB8_F32 = 2,    /* [B][3][H][W] fp32 planar in [0, 1] -> 8-bit RGB: t = x * 255, the same clamp */
+    VIDC_PNG_GRAY8_U8 = 3     /* [B][H][W] uint8 -> 8-bit gray: copied */
+};
+/* The file (its size depends on H, W and the format alone):
+ *   89 50 4E 47 0D 0A 1A 0A
+ *   00 00 00 0D 'IHDR' W(be32) H(be32) bitdepth colourtype 00 00 00 crc(be32)          colour type 0 (gray) or 2 (RGB)
+ *   len(be32) 'IDAT' zlib crc(be32)                                                     ONE IDAT chunk
+ *   00 00 00 00 'IEND' AE 42 60 82
+ *   zlib  = 78 01, stored deflate blocks, adler32(raw)(be32)
+ *   raw   = per row: the filter byte 00, then the row's samples
+ *   block = BFINAL (01 on the last, else 00), LEN(le16), ~LEN(le16), LEN raw bytes; every block but the last has LEN = 65535
+ * i.e. 63 + 5 * ceil(raw / 65535) + raw bytes with raw = H * (1 + W * bytes per pixel); raw byte i sits at 48 + 5 * (i / 65535) + i.
+ * No entropy coder: a 240x320 depth map is 153 918 bytes where Pillow's compressed file has about 76 KB. */
+size_t vidc_png_file_bytes(int H, int W, int format);           /* host only; 0 for H, W <= 0, an unknown format or an IDAT chunk beyond 2^31 - 1 bytes */
+size_t vidc_png_scratch_bytes(int B, int H, int W, int format); /* host only; 0 for bad arguments */
+/* Image i of src -> the file at files + i * file_stride (device memory), in two launches whatever B, with no host synchronisation and
+ * no allocation.  file_stride >= vidc_png_file_bytes() and a multiple of 16, files and scratch 16-byte aligned; the bytes between the
+ * end of a file and file_stride are not written.  An image's bytes do not depend on B or file_stride.  VIDC_ERR_NULL for a null
+ * pointer; VIDC_ERR_SHAPE for B, H, W <= 0, B > 65535, an unknown format, a short or misaligned stride, an image beyond one IDAT chunk. */
+int vidc_png_encode(const void* src, int B, int H, int W, int format, uint8_t* files, size_t file_stride, void* scratch, vidc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * plane-mask head: the two native kernels it reaches   (plane_mask_detection/maskrcnn_benchmark/csrc)
  * ---------------------------------------------------------------------------------------------- */
