@@ -1,6 +1,7 @@
 // Winograd F(4x4, 3x3) in ONE launch for the small maps: input transform, the 36 transform-domain products and the output transform with the conv's
 // epilogue, without the V and M tensors (VERDICT r5 items 2 and 3 iii).  Parity-green; 7 % faster than the three launches alone, +0.7 % on the stream
-// (DESIGN 4.2); the engine records it where the measured table says 5 (or behind VIDC_WINO_FUSED), the committed table does not yet.
+// (DESIGN 4.2); the engine records it where the measured table says 5 (or behind VIDC_WINO_FUSED): in the committed table the two 64-channel stem convs
+// of the four-pyramid launch, which run the Cin = 64 form further down.
 //
 // On a 16x20 map (ResNet-101 layer 3 at the program batch bench.py times: 4 frames x 4 x 5 tiles = 80 tiles per pyramid, Cin = Cout = 256,
 // networks/surface_normal.py:27-50) the three launches of csrc/winograd.hip + conv_mfma.hip take 7 + 28.5 + 9.5 us, of which three launch floors and the
@@ -34,6 +35,7 @@
 // 160 of 256 CUs and the 16x16 MFMA form reads twice the operand bytes per FLOP of the 32x32 form), + U loads 33.5, + transform 41.8 (of which the fold 4);
 // not waiting for the DMA changes nothing.  Earlier forms (git history): 56 -> 53 -> 46 us.
 #include "common.h"
+#include <cstdio>
 #include <cstdlib>
 
 #pragma clang fp contract(off)
@@ -56,7 +58,7 @@ static_assert(LDS_BYTES <= 160 * 1024, "one workgroup per CU");
 
 struct FArgs {
     const float* x; const float* u; float* y; const float* s1; const float* b1; const float* s2; const float* b2;
-    int H, W, Cin, ldx, Cout, ldy, th, tw, T, flags, nbn, gn;      // T = B * th * tw tiles; nbn = Cout / (16 NB) channel blocks of a workgroup; gn = groups * nbn
+    int H, W, Cin, ldx, Cout, ldy, th, tw, T, flags, nbn, gn;      // T = B * th * tw tiles; nbn = Cout / (16 NB) channel blocks of a workgroup (Cin = 64 form: Cout / 64); gn = groups * nbn
     long long x_gs, w_gs, y_gs, p_gs;
     unsigned x_bytes;
 };
@@ -336,6 +338,257 @@ wino4_fused_kernel(const FArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the Cin = 64 form (the stem maps)
+// The 64-channel stem convs have thousands of tile blocks and only four K chunks: run as above, a block's prologue and fold are as long as its
+// products and every 32 output channels repeat the input transform.  Here a workgroup is PERSISTENT: it walks work items I = blockIdx.x, + gridDim.x, ...
+// (item = 16 tiles x 64 output channels of one group; (group, 64-channel block) fastest, as above), and the four chunks of all its items form ONE
+// stream of steps q = 4 i + kc through the same two V buffers and two patch stages:
+//
+//   waves 4..7 (transform), thread = (tile, channel): in step q they issue the LDS-DMA of step q + 2 and compute and write V of step q + 1 -- across
+//       item boundaries, so the patches and the transform of an item's first chunks run under the products of the item before it.  A block of tiles
+//       is transformed once for the 64 output channels of the item.
+//   waves 0..3 (products), one per SIMD: wave w owns output channels 16 w .. 16 w + 15 of the item and ALL 36 positions (36 accumulators of
+//       v_mfma_f32_16x16x4_f32 = 144 registers; two positions are interleaved so that no MFMA waits for the one before it).  U comes from L2 in the
+//       fragment order of vidc_winograd_weight_pack_fused, six positions ahead, across steps and items.  U is the MFMA's A operand and V its B operand
+//       (the fragment order serves both: lane 16 kq + n holds row / column n of k-step kq), so a lane ends up with ONE tile and FOUR consecutive
+//       channels.  After an item's fourth chunk it holds every position of them: it folds A^T (.) A in registers (no LDS, no other wave), applies the
+//       epilogue and stores 16 bytes per output pixel, while the transform waves are already working on the next item.
+//
+// One barrier per step.  K order (chunk, then MFMA k-step), position order and fold are those of the form above and depend on nothing but the output
+// element: bits are independent of the grid (VIDC_WFUSED_STEM_CAP), of the groups and of the frames in the launch -- and equal the form above
+// (tests/test_wfused_stem.py).
+//
+// Measured (tools/wfused_bench.py --only stem, weights HBM-cold, profiles/r7_wfused_stem_bench.txt; 4 frames of 128 x 160, 4 groups): conv1_2 (64 -> 64)
+// 117 us against 153 us for the form above and 213 us for the three launches; conv1_3 (64 -> 128) 205 / 282 / 312.  Attribution (make wfused_attrib,
+// profiles/r7_wfused_stem_attrib.txt, conv1_2): without the MFMAs -32 us, without the fold -28, without patches + transform -16, without the U loads -11:
+// one product wave per SIMD does its MFMAs, its loads and its fold one after the other, and the fold is what is left to hide.
+constexpr int SNK = 4;                               // K chunks of the stem form: Cin = 64
+constexpr int SNPW = 4, SNTW = 4, STHREADS = 64 * (SNPW + SNTW);
+constexpr int SRING = 6;                             // U fragments (positions) a product wave holds ahead (12 spill in the fold: 129 us against 113 in one run)
+constexpr int SDMA = (NDMA + SNTW - 1) / SNTW;       // LDS-DMA instructions per transform wave and chunk
+static_assert(NPOS % SRING == 0 && SRING % 2 == 0, "the ring slot of a position is a compile-time constant");
+
+// DBG: the attribution bits of the form above (1 no MFMAs, 2 no U loads in the loop, 4 no patches / transform, 8 no fold / stores, 16 the fold without its stores)
+template <int DBG>
+__device__ __forceinline__ void stem_product_wave(const FArgs& a, unsigned lds0, int lane, int w, int S) {
+    const int n = lane & 15, kq = lane >> 4;
+    const int n32 = a.Cout / 32;
+    const size_t pos_stride = (size_t)n32 * SNK * 512;
+    // U fragments of step q: item (q >> 2)'s group and channel block, chunk q & 3
+    auto step_ptr = [&](int q) -> const float* {
+        const int I = (int)blockIdx.x + (q >> 2) * (int)gridDim.x;
+        const int r_ = I % a.gn, g = r_ / a.nbn, h = r_ - g * a.nbn;
+        const int nb16 = h * 4 + w;
+        return a.u + (size_t)g * a.w_gs + (size_t)(nb16 >> 1) * (SNK * 512) + (nb16 & 1) * 256 + lane * 4 + (q & 3) * 512;
+    };
+    f32x4 acc[NPOS];
+#pragma unroll
+    for (int p = 0; p < NPOS; ++p) acc[p] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* cur = step_ptr(0);
+    f32x4 bq[SRING];
+#pragma unroll
+    for (int e = 0; e < SRING; ++e) bq[e] = *reinterpret_cast<const f32x4*>(cur + (size_t)e * pos_stride);
+    const unsigned a_off = lds0 + (unsigned)((n * KC + ((kq ^ ((n >> 2) & 3)) * 4)) * 4);
+
+    __builtin_amdgcn_s_barrier();                     // the two barriers of the transform waves' prologue: chunk 0 of V is in buffer 0
+    __builtin_amdgcn_s_barrier();
+    for (int q = 0; q < S; ++q) {
+        const float* nxt = step_ptr(q + 1 < S ? q + 1 : q);          // (the look-ahead loads of the last step re-read it: harmless, no tail case)
+        const unsigned vb = a_off + (unsigned)((q & 1) * VBUF * 4);
+        f32x4 fa[2][2];
+        fa[0][0] = lds_read_b128(vb);
+        fa[0][1] = lds_read_b128(vb + (unsigned)(TB * KC * 4));
+#pragma unroll
+        for (int j = 0; j < NPOS / 2; ++j) {
+            const int c = j & 1, x = c ^ 1, p0 = 2 * j;
+            if (j + 1 < NPOS / 2) {
+                fa[x][0] = lds_read_b128(vb + (unsigned)((p0 + 2) * TB * KC * 4));
+                fa[x][1] = lds_read_b128(vb + (unsigned)((p0 + 3) * TB * KC * 4));
+                wait_lgkmcnt<2>();
+            } else {
+                wait_lgkmcnt<0>();
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                if constexpr (!(DBG & 1)) {
+                    acc[p0] = __builtin_amdgcn_mfma_f32_16x16x4f32(bq[p0 % SRING][ks], fa[c][0][ks], acc[p0], 0, 0, 0);
+                    acc[p0 + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(bq[(p0 + 1) % SRING][ks], fa[c][1][ks], acc[p0 + 1], 0, 0, 0);
+                } else if (ks == 0) {
+                    acc[p0][0] += fa[c][0][0] + fa[c][0][3] + bq[p0 % SRING][0] + bq[p0 % SRING][3];
+                    acc[p0 + 1][0] += fa[c][1][0] + fa[c][1][3] + bq[(p0 + 1) % SRING][0] + bq[(p0 + 1) % SRING][3];
+                }
+            }
+            if constexpr (!(DBG & 2)) {
+                const int pn = p0 + SRING;
+                const float* s = pn < NPOS ? cur + (size_t)pn * pos_stride : nxt + (size_t)(pn - NPOS) * pos_stride;
+                bq[p0 % SRING] = *reinterpret_cast<const f32x4*>(s);
+                bq[(p0 + 1) % SRING] = *reinterpret_cast<const f32x4*>(s + pos_stride);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_s_barrier();                 // every wave has read buffer q & 1; step q + 1 is in the other one
+        cur = nxt;
+        if ((q & 3) != 3) continue;
+        // ---- the item is complete: U was the MFMA's A operand and V its B operand, so the lane holds M[pos][channel 4 kq + i][tile n] -- one tile and
+        // four consecutive channels: fold + epilogue as in the form above per channel, one 16-byte store per output pixel.  The column pass goes column by
+        // column so that the accumulators die as it proceeds.
+        if (!(DBG & 8) || a.H < 0) {                  // (attribution: the fold stays in the code and never runs)
+            const int I = (int)blockIdx.x + (q >> 2) * (int)gridDim.x;
+            const int tb = I / a.gn, r_ = I - tb * a.gn, g = r_ / a.nbn, h = r_ - g * a.nbn;
+            const int ch = h * 64 + w * 16 + 4 * kq;
+            const bool aff2 = a.flags & VIDC_AFFINE2;
+            const size_t pof = (size_t)g * a.p_gs + ch;
+            const float lo1 = (a.flags & VIDC_RELU1) ? 0.f : -INFINITY, lo2 = (a.flags & VIDC_RELU2) ? 0.f : -INFINITY;
+            const int tpf = a.th * a.tw;
+            const int t = tb * TB + n, tcl = t < a.T ? t : 0;
+            const int b = tcl / tpf, rem = tcl - b * tpf, ty = rem / a.tw, tx = rem - ty * a.tw;
+            const bool okt = t < a.T && (!(DBG & 16) || a.H < 0);          // (attribution: the fold without its stores)
+            float* yb = a.y + (size_t)g * a.y_gs + ch + ((size_t)(b * a.H + ty * 4) * a.W + tx * 4) * a.ldy;
+            float tc[4][4][6];                        // [channel][row][column]
+#pragma unroll
+            for (int s = 0; s < 6; ++s) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    float col[6], o4[4];
+#pragma unroll
+                    for (int r = 0; r < 6; ++r) col[r] = acc[r * 6 + s][i];
+                    at6(col, o4);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) tc[i][r][s] = o4[r];
+                }
+                __builtin_amdgcn_sched_barrier(0);    // (column by column, and the constants' registers only after the last: the scheduler would overlap them all)
+            }
+            const f32x4 s1 = *reinterpret_cast<const f32x4*>(a.s1 + pof), b1 = *reinterpret_cast<const f32x4*>(a.b1 + pof);
+            const f32x4 s2 = *reinterpret_cast<const f32x4*>((aff2 ? a.s2 : a.s1) + pof), b2 = *reinterpret_cast<const f32x4*>((aff2 ? a.b2 : a.b1) + pof);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float o[4][4];                        // [channel][column]
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    at6(tc[i][r], o[i]);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        float v = fmaxf(o[i][s] * s1[i] + b1[i], lo1);
+                        if (aff2) v = fmaxf(v * s2[i] + b2[i], lo2);
+                        o[i][s] = v;
+                    }
+                }
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    if (okt && ty * 4 + r < a.H && tx * 4 + s < a.W)
+                        *reinterpret_cast<f32x4*>(yb + ((size_t)r * a.W + s) * a.ldy) = f32x4{o[0][s], o[1][s], o[2][s], o[3][s]};
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < NPOS; ++p) acc[p] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
+template <int DBG>
+__global__ void __launch_bounds__(STHREADS)
+wino4_fused_stem_kernel(const FArgs a, const int nitems) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x;
+    const int S = SNK * ((nitems - 1 - (int)blockIdx.x) / (int)gridDim.x + 1);          // steps of this workgroup (grid <= nitems: at least one item)
+    const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) float*)smem);
+
+    if (tid < 64 * SNPW) {
+        stem_product_wave<DBG>(a, lds0, tid & 63, __builtin_amdgcn_readfirstlane(tid >> 6), S);
+        return;
+    }
+    // ------------------------------------------------------------------ transform waves: thread = (tile m, channel c of the chunk)
+    const int tt = tid - 64 * SNPW, lane = tid & 63;
+    const int w4 = __builtin_amdgcn_readfirstlane(tt >> 6);
+    const int m = tt >> 4, c = tt & 15;
+    const int tpf = a.th * a.tw;
+    // ---- patch stage as in the form above; wave w4 issues instructions w4, w4 + 4, ...; their per-lane offsets are computed once per item
+    constexpr unsigned OOB = 0x80000000u;
+    unsigned voff[SDMA];
+    auto item_offsets = [&](int I) {
+        const int tb = I / a.gn, r_ = I - tb * a.gn, g = r_ / a.nbn;
+#pragma unroll
+        for (int i = 0; i < SDMA; ++i) {
+            const int j = w4 + SNTW * i;
+            const int slot = 16 * j + (lane >> 2), quad = lane & 3;
+            const int ts = slot / XSLOT, px = slot - ts * XSLOT;
+            const int t = tb * TB + ts;
+            bool ok = j < NDMA && px < 36 && t < a.T;
+            const int tc = ok ? t : 0;
+            const int b = tc / tpf, rem = tc - b * tpf, ty = rem / a.tw, tx = rem - ty * a.tw;
+            const int r = px / 6, s = px - r * 6;
+            const int iy = ty * 4 - 1 + r, ix = tx * 4 - 1 + s;
+            ok = ok && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+            voff[i] = ok ? (unsigned)(((size_t)((b * a.H + iy) * a.W + ix) * a.ldx + (size_t)g * a.x_gs + quad * 4) * 4) : OOB;
+        }
+    };
+    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+    auto dma = [&](int q) {                           // step q -> stage buffer q & 1
+        if ((q & 3) == 0) item_offsets((int)blockIdx.x + (q >> 2) * (int)gridDim.x);
+        float* dst = smem + 2 * VBUF + (q & 1) * XBUF;
+        const int soff = (q & 3) * KC * 4;
+#pragma unroll
+        for (int i = 0; i < SDMA; ++i)
+            if (w4 + SNTW * i < NDMA) __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (lds_void_t*)(dst + (w4 + SNTW * i) * 256), 16, (int)voff[i], soff, 0, 0);
+    };
+    const unsigned x_thr = lds0 + (unsigned)((2 * VBUF + (m * XSLOT) * KC + c) * 4);
+    const unsigned v_thr = lds0 + (unsigned)((m * KC + (((c >> 2) ^ ((m >> 2) & 3)) * 4) + (c & 3)) * 4);
+    // the thread's 6 x 6 patch of step q from the stage -> V = B^T d B -> [pos][tile][16 ch] of V buffer q & 1, 16-byte unit (c >> 2) XOR (m >> 2) & 3
+    auto transform = [&](int q) {
+        const unsigned xa = x_thr + (unsigned)((q & 1) * XBUF * 4);
+        float D[36], out[36];
+#define VIDC_RD(i) D[i] = lds_read_b32<(i) * KC * 4>(xa);
+        VIDC_RD(0) VIDC_RD(1) VIDC_RD(2) VIDC_RD(3) VIDC_RD(4) VIDC_RD(5) VIDC_RD(6) VIDC_RD(7) VIDC_RD(8) VIDC_RD(9) VIDC_RD(10) VIDC_RD(11)
+        VIDC_RD(12) VIDC_RD(13) VIDC_RD(14) VIDC_RD(15) VIDC_RD(16) VIDC_RD(17) VIDC_RD(18) VIDC_RD(19) VIDC_RD(20) VIDC_RD(21) VIDC_RD(22) VIDC_RD(23)
+        VIDC_RD(24) VIDC_RD(25) VIDC_RD(26) VIDC_RD(27) VIDC_RD(28) VIDC_RD(29) VIDC_RD(30) VIDC_RD(31) VIDC_RD(32) VIDC_RD(33) VIDC_RD(34) VIDC_RD(35)
+#undef VIDC_RD
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(D[0]), "+v"(D[1]), "+v"(D[2]), "+v"(D[3]), "+v"(D[4]), "+v"(D[5]), "+v"(D[6]), "+v"(D[7]), "+v"(D[8]), "+v"(D[9]), "+v"(D[10]), "+v"(D[11]), "+v"(D[12]), "+v"(D[13]), "+v"(D[14]), "+v"(D[15]), "+v"(D[16]), "+v"(D[17]) :: "memory");
+        asm volatile("" : "+v"(D[18]), "+v"(D[19]), "+v"(D[20]), "+v"(D[21]), "+v"(D[22]), "+v"(D[23]), "+v"(D[24]), "+v"(D[25]), "+v"(D[26]), "+v"(D[27]), "+v"(D[28]), "+v"(D[29]), "+v"(D[30]), "+v"(D[31]), "+v"(D[32]), "+v"(D[33]), "+v"(D[34]), "+v"(D[35]) :: "memory");
+        float tcol[6][6];
+#pragma unroll
+        for (int s = 0; s < 6; ++s) {
+            float col[6], o6[6];
+#pragma unroll
+            for (int r = 0; r < 6; ++r) col[r] = D[r * 6 + s];
+            bt6(col, o6);
+#pragma unroll
+            for (int r = 0; r < 6; ++r) tcol[r][s] = o6[r];
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            float o6[6];
+            bt6(tcol[r], o6);
+#pragma unroll
+            for (int s = 0; s < 6; ++s) out[r * 6 + s] = o6[s];
+        }
+        const unsigned va = v_thr + (unsigned)((q & 1) * VBUF * 4);
+#define VIDC_WR(i) lds_write_b32<(i) * TB * KC * 4>(va, out[i]);
+        VIDC_WR(0) VIDC_WR(1) VIDC_WR(2) VIDC_WR(3) VIDC_WR(4) VIDC_WR(5) VIDC_WR(6) VIDC_WR(7) VIDC_WR(8) VIDC_WR(9) VIDC_WR(10) VIDC_WR(11)
+        VIDC_WR(12) VIDC_WR(13) VIDC_WR(14) VIDC_WR(15) VIDC_WR(16) VIDC_WR(17) VIDC_WR(18) VIDC_WR(19) VIDC_WR(20) VIDC_WR(21) VIDC_WR(22) VIDC_WR(23)
+        VIDC_WR(24) VIDC_WR(25) VIDC_WR(26) VIDC_WR(27) VIDC_WR(28) VIDC_WR(29) VIDC_WR(30) VIDC_WR(31) VIDC_WR(32) VIDC_WR(33) VIDC_WR(34) VIDC_WR(35)
+#undef VIDC_WR
+    };
+    auto fence_barrier = [&]() {                      // own DMA landed, own LDS reads and writes done
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    };
+    // ---- prologue: steps 0 and 1 staged (S >= 4); V of step 0
+    dma(0);
+    dma(1);
+    fence_barrier();
+    transform(0);
+    fence_barrier();
+    // ---- step q (the product waves multiply it): step q + 2 is staged into the buffer transform(q) has left, V of step q + 1 goes into the buffer the
+    // product waves left at the barrier before
+    for (int q = 0; q < S; ++q) {
+        if (!(DBG & 4)) {
+            if (q + 2 < S) dma(q + 2);
+            if (q + 1 < S) transform(q + 1);
+        }
+        fence_barrier();
+    }
+}
+
 // U [36][Cout][Cin] (vidc_winograd_weight_transform, m = 4) -> fragment order [36][Cout / 32][Cin / 16][nblk 2][lane 64][4]: lane = 16 kq + n holds
 // U[pos][32 nb + 16 nblk + n][16 kc + 4 kq + 0..3].  One thread per float4.
 __global__ void __launch_bounds__(256)
@@ -364,6 +617,36 @@ int launch_nb(const FArgs& a, long long wgs, hipStream_t st) {
     }
     hipLaunchKernelGGL((wino4_fused_kernel<NB, DBG>), dim3((unsigned)wgs), dim3(NTHREADS), LDS_BYTES, st, a);
     VIDC_CHECK_LAUNCH("wino4_fused_kernel");
+    return VIDC_OK;
+}
+
+// The Cin = 64 form: one workgroup per CU (146 KB of LDS), each walking its items; VIDC_WFUSED_STEM_CAP sets another grid cap (read at every launch:
+// the tests force several items per workgroup at small shapes with it).
+template <int DBG>
+int launch_stem(FArgs& a, int groups, hipStream_t st) {
+    static bool attr_set[64] = {};
+    static int cus[64] = {};
+    int dev = 0;
+    VIDC_HIP(hipGetDevice(&dev));
+    const bool cached = dev >= 0 && dev < 64;
+    if (!cached || !attr_set[dev]) {
+        VIDC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino4_fused_stem_kernel<DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
+        if (cached) attr_set[dev] = true;
+    }
+    int ncu = cached ? cus[dev] : 0;
+    if (ncu <= 0) {
+        VIDC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+        if (ncu <= 0) ncu = 256;
+        if (cached) cus[dev] = ncu;
+    }
+    a.nbn = a.Cout / 64; a.gn = groups * a.nbn;
+    const long long items = (long long)((a.T + TB - 1) / TB) * a.gn;
+    VIDC_REQUIRE(items * SNK < (1ll << 31), VIDC_ERR_SHAPE, "conv (fused Winograd): grid too large");
+    long long cap = ncu;
+    if (const char* e = getenv("VIDC_WFUSED_STEM_CAP")) { const long long v = atoll(e); if (v > 0) cap = v; }
+    const long long wgs = items < cap ? items : cap;
+    hipLaunchKernelGGL((wino4_fused_stem_kernel<DBG>), dim3((unsigned)wgs), dim3(STHREADS), LDS_BYTES, st, a, (int)items);
+    VIDC_CHECK_LAUNCH("wino4_fused_stem_kernel");
     return VIDC_OK;
 }
 
@@ -396,6 +679,37 @@ int launch_wino4_fused(const vidc_conv_desc& d, hipStream_t st) {
     a.x_gs = d.x_gs; a.w_gs = d.w_gs; a.y_gs = d.y_gs; a.p_gs = d.p_gs;
     VIDC_REQUIRE((long long)d.B * d.H * d.W * d.ldx * 4 < (1ll << 30), VIDC_ERR_SHAPE, "conv (fused Winograd): the input must stay below 1 GiB");
     a.x_bytes = (unsigned)((long long)d.B * d.H * d.W * d.ldx * 4);
+    // Cin = 64 and whole 64-channel blocks of output: the persistent form, once the launch has an item (16 tiles x 64 channels of a group) for every
+    // CU of the chip -- 4096 tiles x groups x 64-channel blocks.  Below that a persistent workgroup has no second item to hide its prologue and fold
+    // under, and the form above spreads 16- / 32-channel workgroups over more CUs.  (VIDC_WFUSED_STEM_MIN_TILES sets another threshold, 0 = never;
+    // VIDC_WFUSED_TRACE=1 prints the form of every launch: tests.)
+    {
+        long long min_tiles = 4096;
+        if (const char* e = getenv("VIDC_WFUSED_STEM_MIN_TILES")) { const long long v = atoll(e); min_tiles = v > 0 ? v : (1ll << 62); }
+        auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };          // (it loads and stores four channels at once)
+        const bool y16 = al16(d.y) && d.ldy % 4 == 0 && d.y_gs % 4 == 0 && d.p_gs % 4 == 0 && al16(d.scale1) && al16(d.shift1) &&
+                         (!(d.flags & VIDC_AFFINE2) || (al16(d.scale2) && al16(d.shift2)));
+        const bool stem = d.Cin == 64 && d.Cout % 64 == 0 && y16 && (long long)a.T * d.groups * (d.Cout / 64) >= min_tiles;
+        if (const char* e = getenv("VIDC_WFUSED_TRACE")) if (atoi(e)) fprintf(stderr, "wino4f: form %s Cin %d Cout %d tiles %d groups %d\n", stem ? "stem" : "4", d.Cin, d.Cout, a.T, d.groups);
+        if (stem) {
+#ifdef VIDC_WFUSED_ATTRIB
+            static const int sdbg = [] { const char* e = getenv("VIDC_WFUSED_DBG"); return e ? atoi(e) : 0; }();
+            switch (sdbg) {
+                case 1: return launch_stem<1>(a, d.groups, st);
+                case 2: return launch_stem<2>(a, d.groups, st);
+                case 4: return launch_stem<4>(a, d.groups, st);
+                case 8: return launch_stem<8>(a, d.groups, st);
+                case 3: return launch_stem<3>(a, d.groups, st);
+                case 7: return launch_stem<7>(a, d.groups, st);
+                case 10: return launch_stem<10>(a, d.groups, st);
+                case 15: return launch_stem<15>(a, d.groups, st);
+                case 16: return launch_stem<16>(a, d.groups, st);
+                default: break;
+            }
+#endif
+            return launch_stem<0>(a, d.groups, st);
+        }
+    }
     const long long wgs = (long long)((a.T + TB - 1) / TB) * a.gn;
     VIDC_REQUIRE(wgs < (1ll << 31), VIDC_ERR_SHAPE, "conv (fused Winograd): grid too large");
 #ifdef VIDC_WFUSED_ATTRIB
