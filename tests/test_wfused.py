@@ -2,6 +2,12 @@
 the small maps (the 22 conv2 of ResNet-101 layer 3, torchvision Bottleneck as used at networks/surface_normal.py:27-35,48-50) without the V / M tensors.
 Against F.conv2d in float64; against the three-launch Winograd path (same arithmetic, another summation order); bits independent of the batch a tile
 is part of and of the groups sharing the launch (what engine.Program.group_variant and the stream mode rely on)."""
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -103,6 +109,74 @@ def test_magnitudes_activations_1e3_weights_1e_3():
     y = ops.conv3x3_winograd_fused(nhwc(x).to(DEV), [t.to(DEV) for t in w], s1.to(DEV), (b1 * 0).to(DEV))
     rel = (nchw(y).cpu().double() - ref).abs().max().item() / ref.abs().max().item()
     assert rel < 2e-5, rel
+
+
+BITS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wfused_bits.json")
+NB2_SHAPE = SHAPES[2]          # nine 32-channel workgroups: NB = 1 unless VIDC_WFUSED_NB=2 forces the other instantiation
+
+
+def _sha(y):
+    torch.cuda.synchronize()
+    return hashlib.sha256(y.contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def _shape_bits(shape):
+    from vi_depth_completion_amd import ops
+    x, w, s1, b1 = _case(41, *shape)
+    return _sha(ops.conv3x3_winograd_fused(nhwc(x).to(DEV), [t.to(DEV) for t in w], s1.to(DEV), b1.to(DEV), relu1=True))
+
+
+def _output_bits():
+    """name -> SHA-256 of the raw output bytes, for the smallest shapes that reach every branch of both forms of the kernel: cases a, b, c of
+    tests/test_wfused_stem.py in the Cin = 64 form and in form 4 (partial block of 16 tiles, blocks across image borders, a tile cut by both borders),
+    case c's second-affine call, SHAPES[2:] (among them a single K chunk; all on the NB = 1 instantiation) and one call on the NB = 2 instantiation.
+    VIDC_WFUSED_STEM_MIN_TILES is read at every launch; VIDC_WFUSED_NB once per process: that call runs in a fresh child."""
+    from vi_depth_completion_amd import ops
+    from test_wfused_stem import CASES, CIN
+    bits, keep = {}, os.environ.get("VIDC_WFUSED_STEM_MIN_TILES")
+    try:
+        for name in sorted(CASES):
+            B, H, W, cout, G = CASES[name]
+            x, w, s1, b1 = _case(60 + ord(name), B, H, W, CIN, cout, G)          # (the inputs of test_wfused_stem._case)
+            xd, wd, s1d, b1d = nhwc(x).to(DEV), [t.to(DEV) for t in w], s1.to(DEV), b1.to(DEV)
+            aff2 = {}
+            if name == "c":
+                aff2 = dict(scale2=(S.uniform01(71, "s2", (G, cout)) + 0.5).to(DEV), shift2=(S.normal01(71, "b2", (G, cout)).float() * 0.1).to(DEV), relu2=True)
+            for form, min_tiles in (("stem", "1"), ("form4", "0")):
+                os.environ["VIDC_WFUSED_STEM_MIN_TILES"] = min_tiles
+                bits["stem_%s/%s" % (name, form)] = _sha(ops.conv3x3_winograd_fused(xd, wd, s1d, b1d, relu1=True))
+                if aff2:
+                    bits["stem_%s_affine2/%s" % (name, form)] = _sha(ops.conv3x3_winograd_fused(xd, wd, s1d, b1d, relu1=True, **aff2))
+    finally:
+        if keep is None:
+            os.environ.pop("VIDC_WFUSED_STEM_MIN_TILES", None)
+        else:
+            os.environ["VIDC_WFUSED_STEM_MIN_TILES"] = keep
+    for shape in SHAPES[2:]:
+        bits["shape_%s" % "_".join(map(str, shape))] = _shape_bits(shape)
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = "import sys; sys.path[:0] = [%r, %r]; import test_wfused as T; print('BITS', T._shape_bits(T.NB2_SHAPE))" % (os.path.dirname(here), here)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, VIDC_WFUSED_NB="2"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "BITS " in r.stdout, (r.stdout + r.stderr)[-4000:]
+    bits["shape_%s/nb2" % "_".join(map(str, NB2_SHAPE))] = r.stdout.split("BITS ")[1].split()[0]
+    return bits
+
+
+def test_output_bits_are_those_recorded_before_the_forms_shared_their_transform_stage(monkeypatch, capfd):
+    """tests/golden/wfused_bits.json was recorded from the library as it was when each form of the kernel had its own copy of the patch stage, the
+    transform, the column formulas and the epilogue: sharing them changed no output bit (and no later change to them may, unless it says so)."""
+    monkeypatch.setenv("VIDC_WFUSED_TRACE", "1")
+    monkeypatch.delenv("VIDC_WFUSED_STEM_CAP", raising=False)
+    monkeypatch.delenv("VIDC_WFUSED_STEM_MIN_TILES", raising=False)
+    capfd.readouterr()
+    got = _output_bits()
+    forms = [line.split()[2] for line in capfd.readouterr().err.splitlines() if line.startswith("wino4f: form")]
+    assert forms == ["stem", "4", "stem", "4", "stem", "stem", "4", "4"] + ["4"] * len(SHAPES[2:]), forms
+    with open(BITS_JSON) as f:
+        want = json.load(f)
+    assert sorted(got) == sorted(want)
+    assert not [k for k in want if got[k] != want[k]], [k for k in want if got[k] != want[k]]
+    assert want["shape_%s/nb2" % "_".join(map(str, NB2_SHAPE))] == want["shape_%s" % "_".join(map(str, NB2_SHAPE))]      # (a tile's bits do not depend on NB)
 
 
 def test_refusals():

@@ -39,6 +39,21 @@ inline hipStream_t as_stream(vidc_stream_t s) { return reinterpret_cast<hipStrea
 
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Lets `Kernel` be launched with `bytes` of dynamic LDS: hipFuncAttributeMaxDynamicSharedMemorySize, set once per device and kernel (the attribute is
+// per device function; benign race: idempotent; devices >= 64 set it at every launch).  *dev_out: the current device, for a launcher that needs it.
+template <auto Kernel>
+int allow_dynamic_lds(size_t bytes, int* dev_out = nullptr) {
+    static bool attr_set[64] = {};
+    int dev = 0;
+    VIDC_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        VIDC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    if (dev_out) *dev_out = dev;
+    return VIDC_OK;
+}
+
 // ---- the training kernels' workgroup (csrc/train.hip, csrc/sn_train.hip) ----------------------------------------------------------
 constexpr int TT = 256;
 inline unsigned blocks(long long n) { return (unsigned)((n + TT - 1) / TT); }

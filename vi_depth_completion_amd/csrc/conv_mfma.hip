@@ -1021,14 +1021,7 @@ template <int BM, int BN, int WMW, int WNW, int WKW, int NS, int PREC, int SPEC>
 int launch_tile_p(const ConvArgs& a, hipStream_t st) {
     constexpr int NT = tile_threads(WMW, WNW, WKW, SPEC);
     constexpr size_t lds = (size_t)NS * ring_slot_floats(BM, BN, WMW * WNW, WKW, PREC == 3) * sizeof(float);
-    static bool attr_set[64] = {};   // per device (the attribute is per device function); benign race: idempotent
-    int dev = 0;
-    VIDC_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        VIDC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_f32<BM, BN, WMW, WNW, WKW, NS, PREC, SPEC>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
+    if (const int rc = vidc::allow_dynamic_lds<&conv_igemm_f32<BM, BN, WMW, WNW, WKW, NS, PREC, SPEC>>(lds)) return rc;
     dim3 grid(a.tiles_m * a.tiles_n * a.splitk * a.groups, 1, 1);
     hipLaunchKernelGGL((conv_igemm_f32<BM, BN, WMW, WNW, WKW, NS, PREC, SPEC>), grid, dim3(NT), lds, st, a);
     VIDC_CHECK_LAUNCH("conv_igemm_f32");

@@ -34,14 +34,21 @@
 // builds (make wfused_attrib, tools/wfused_attrib.sh): empty skeleton 10.7 us (= the launch floor), + MFMAs 29.4 (18.7 us of products: 160 workgroups use
 // 160 of 256 CUs and the 16x16 MFMA form reads twice the operand bytes per FLOP of the 32x32 form), + U loads 33.5, + transform 41.8 (of which the fold 4);
 // not waiting for the DMA changes nothing.  Earlier forms (git history): 56 -> 53 -> 46 us.
+//
+// Both forms share ONE transform stage (patch_offsets .. v_store below: what an LDS-DMA instruction moves where, stage -> registers -> B^T d B -> V
+// buffer), the column formulas and the epilogue value of csrc/wino_math.h (the three-launch path's too), and one launcher.  A form keeps its
+// schedule, its product waves and its fold; that the two compute the same bits (tests/test_wfused_stem.py) follows from the shared code.
 #include "common.h"
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 
 #pragma clang fp contract(off)
+#include "wino_math.h"          // Wino<4>::bt / ::at in the operation order of csrc/winograd.hip, the epilogue value
 
 namespace {
 
+using vidc::Wino;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TB = 16, NBW = 32, KC = 16, NPOS = 36;
@@ -65,34 +72,16 @@ struct FArgs {
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 
-// B^T d for one column / A^T m for one column: Lavin & Gray's F(4x4, 3x3) matrices, the operation order of csrc/winograd.hip Wino<4>
-// (in two halves: rows 0..2 / 3..5 of B^T d share no intermediate)
-template <typename V> __device__ __forceinline__ void bt6_lo(const V (&d)[6], V (&t)[3]) {
-    const V p = d[4] - 4.f * d[2], q = d[3] - 4.f * d[1];
-    t[0] = (4.f * d[0] - 5.f * d[2]) + d[4];
-    t[1] = p + q;
-    t[2] = p - q;
-}
-template <typename V> __device__ __forceinline__ void bt6_hi(const V (&d)[6], V (&t)[3]) {
-    const V r = d[4] - d[2], s = 2.f * (d[3] - d[1]);
-    t[0] = r + s;
-    t[1] = r - s;
-    t[2] = (4.f * d[1] - 5.f * d[3]) + d[5];
-}
-template <typename V> __device__ __forceinline__ void bt6(const V (&d)[6], V (&t)[6]) {
-    V lo[3], hi[3];
-    bt6_lo(d, lo);
-    bt6_hi(d, hi);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { t[i] = lo[i]; t[3 + i] = hi[i]; }
-}
-__device__ __forceinline__ void at6(const float (&m)[6], float (&o)[4]) {
-    const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-    o[0] = (m[0] + s12) + s34;
-    o[1] = d12 + 2.f * d34;
-    o[2] = s12 + 4.f * s34;
-    o[3] = (d12 + 8.f * d34) + m[5];
-}
+// Attribution builds (make wfused_attrib, -DVIDC_WFUSED_ATTRIB; tools/wfused_attrib.sh): VIDC_WFUSED_DBG, read once per process, picks an instantiation
+// of either form without one of its parts.  Bit 16 is the one value that means something else in each form.
+enum : int {
+    DBG_NO_MFMA = 1,                 // no MFMAs
+    DBG_NO_U_LOADS = 2,              // no U loads in the loop
+    DBG_NO_TRANSFORM = 4,            // no patches / transform in the loop (barriers only)
+    DBG_NO_FOLD = 8,                 // no fold / stores (in the Cin = 64 form the fold stays in the code and never runs)
+    DBG_F4_DMA_NOT_AWAITED = 16,     // 16 tiles x 32 channels form: the DMA is not waited for -- wrong results, right schedule
+    DBG_STEM_FOLD_NO_STORES = 16,    // Cin = 64 form: the fold without its stores
+};
 
 template <int N_> __device__ __forceinline__ void wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N_) : "memory"); }
 __device__ __forceinline__ f32x4 lds_read_b128(unsigned addr) {
@@ -108,6 +97,83 @@ template <int OFF> __device__ __forceinline__ float lds_read_b32(unsigned addr) 
     return v;
 }
 template <int OFF> __device__ __forceinline__ void lds_write_b32(unsigned addr, float v) { asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory"); }
+
+// ---------------------------------------------------------------------------------------------------------------- the transform stage of both forms
+struct TileCoords { int b, ty, tx; };
+__device__ __forceinline__ TileCoords tile_coords(const FArgs& a, int t) {
+    const int tpf = a.th * a.tw;
+    const int b = t / tpf, rem = t - b * tpf, ty = rem / a.tw;
+    return {b, ty, rem - ty * a.tw};
+}
+// Patch stage: LDS-DMA instruction j of a chunk moves pixel slots 16 j .. 16 j + 15 (slot = 37 tile + pixel) of tile block tb x 4 channel quads, 1 KiB,
+// into [slot][16 ch]; a pixel outside the map, the 37th slot of a tile and tiles beyond T get an out-of-range offset and arrive as zeros.  A transform
+// wave issues instructions wave, wave + STRIDE, ...: their N per-lane offsets.
+template <int N, int STRIDE>
+__device__ __forceinline__ void patch_offsets(const FArgs& a, int tb, int g, int wave, int lane, unsigned (&voff)[N]) {
+    constexpr unsigned OOB = 0x80000000u;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int j = wave + STRIDE * i;
+        const int slot = 16 * j + (lane >> 2), quad = lane & 3;
+        const int ts = slot / XSLOT, px = slot - ts * XSLOT;
+        const int t = tb * TB + ts;
+        bool ok = j < NDMA && px < 36 && t < a.T;
+        const TileCoords tc = tile_coords(a, ok ? t : 0);
+        const int r = px / 6, s = px - r * 6;
+        const int iy = tc.ty * 4 - 1 + r, ix = tc.tx * 4 - 1 + s;
+        ok = ok && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+        voff[i] = ok ? (unsigned)(((size_t)((tc.b * a.H + iy) * a.W + ix) * a.ldx + (size_t)g * a.x_gs + quad * 4) * 4) : OOB;
+    }
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t patch_rsrc(const FArgs& a) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000); }
+// ... and their issue: the 16 channels at byte offset soff of the pixels -> stage buffer buf
+template <int N, int STRIDE>
+__device__ __forceinline__ void patch_dma(__amdgpu_buffer_rsrc_t x_rsrc, float* smem, int buf, int wave, const unsigned (&voff)[N], int soff) {
+    float* dst = smem + 2 * VBUF + buf * XBUF;
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+        if (wave + STRIDE * i < NDMA) __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (lds_void_t*)(dst + (wave + STRIDE * i) * 256), 16, (int)voff[i], soff, 0, 0);
+}
+// Transform, thread = (tile m, channel c of the chunk): LDS addresses of its patch in stage buffer buf and of its V[0] in V buffer buf
+// ([pos][tile][16 ch], 16-byte unit (c >> 2) XOR (m >> 2) & 3: the product waves' ds_read_b128 are conflict-free without padding)
+__device__ __forceinline__ unsigned patch_addr(unsigned lds0, int m, int c, int buf) { return lds0 + (unsigned)((2 * VBUF + (m * XSLOT) * KC + c) * 4) + (unsigned)(buf * XBUF * 4); }
+__device__ __forceinline__ unsigned v_addr(unsigned lds0, int m, int c, int buf) { return lds0 + (unsigned)((m * KC + (((c >> 2) ^ ((m >> 2) & 3)) * 4) + (c & 3)) * 4) + (unsigned)(buf * VBUF * 4); }
+// the thread's 6 x 6 patch from the stage -> V = B^T d B in registers
+__device__ __forceinline__ void patch_to_v(unsigned xa, float (&out)[36]) {
+    float D[36];
+#define VIDC_RD(i) D[i] = lds_read_b32<(i) * KC * 4>(xa);
+    VIDC_RD(0) VIDC_RD(1) VIDC_RD(2) VIDC_RD(3) VIDC_RD(4) VIDC_RD(5) VIDC_RD(6) VIDC_RD(7) VIDC_RD(8) VIDC_RD(9) VIDC_RD(10) VIDC_RD(11)
+    VIDC_RD(12) VIDC_RD(13) VIDC_RD(14) VIDC_RD(15) VIDC_RD(16) VIDC_RD(17) VIDC_RD(18) VIDC_RD(19) VIDC_RD(20) VIDC_RD(21) VIDC_RD(22) VIDC_RD(23)
+    VIDC_RD(24) VIDC_RD(25) VIDC_RD(26) VIDC_RD(27) VIDC_RD(28) VIDC_RD(29) VIDC_RD(30) VIDC_RD(31) VIDC_RD(32) VIDC_RD(33) VIDC_RD(34) VIDC_RD(35)
+#undef VIDC_RD
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(D[0]), "+v"(D[1]), "+v"(D[2]), "+v"(D[3]), "+v"(D[4]), "+v"(D[5]), "+v"(D[6]), "+v"(D[7]), "+v"(D[8]), "+v"(D[9]), "+v"(D[10]), "+v"(D[11]), "+v"(D[12]), "+v"(D[13]), "+v"(D[14]), "+v"(D[15]), "+v"(D[16]), "+v"(D[17]) :: "memory");
+    asm volatile("" : "+v"(D[18]), "+v"(D[19]), "+v"(D[20]), "+v"(D[21]), "+v"(D[22]), "+v"(D[23]), "+v"(D[24]), "+v"(D[25]), "+v"(D[26]), "+v"(D[27]), "+v"(D[28]), "+v"(D[29]), "+v"(D[30]), "+v"(D[31]), "+v"(D[32]), "+v"(D[33]), "+v"(D[34]), "+v"(D[35]) :: "memory");
+    float tcol[6][6];
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+        float col[6], o6[6];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) col[r] = D[r * 6 + s];
+        Wino<4>::bt(col, o6);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) tcol[r][s] = o6[r];
+    }
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        float o6[6];
+        Wino<4>::bt(tcol[r], o6);
+#pragma unroll
+        for (int s = 0; s < 6; ++s) out[r * 6 + s] = o6[s];
+    }
+}
+// V -> [pos][tile][16 ch] of a V buffer the product waves are not reading
+__device__ __forceinline__ void v_store(unsigned va, const float (&out)[36]) {
+#define VIDC_WR(i) lds_write_b32<(i) * TB * KC * 4>(va, out[i]);
+    VIDC_WR(0) VIDC_WR(1) VIDC_WR(2) VIDC_WR(3) VIDC_WR(4) VIDC_WR(5) VIDC_WR(6) VIDC_WR(7) VIDC_WR(8) VIDC_WR(9) VIDC_WR(10) VIDC_WR(11)
+    VIDC_WR(12) VIDC_WR(13) VIDC_WR(14) VIDC_WR(15) VIDC_WR(16) VIDC_WR(17) VIDC_WR(18) VIDC_WR(19) VIDC_WR(20) VIDC_WR(21) VIDC_WR(22) VIDC_WR(23)
+    VIDC_WR(24) VIDC_WR(25) VIDC_WR(26) VIDC_WR(27) VIDC_WR(28) VIDC_WR(29) VIDC_WR(30) VIDC_WR(31) VIDC_WR(32) VIDC_WR(33) VIDC_WR(34) VIDC_WR(35)
+#undef VIDC_WR
+}
 
 // One product wave: positions pos0 .. pos0 + PW - 1, all of K, 16 tiles x NB blocks of 16 output channels.
 template <int PW, int NB, int DBG>
@@ -157,9 +223,9 @@ __device__ __forceinline__ void product_wave(const FArgs& a, float* smem, unsign
             for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
                 for (int j = 0; j < NB; ++j)
-                    if constexpr (!(DBG & 1)) acc[p][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[cur][ks], bq[p][j][ks], acc[p][j], 0, 0, 0);
+                    if constexpr (!(DBG & DBG_NO_MFMA)) acc[p][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[cur][ks], bq[p][j][ks], acc[p][j], 0, 0, 0);
                     else if (ks == 0) acc[p][j][0] += fa[cur][0] + fa[cur][3] + bq[p][j][0] + bq[p][j][3];
-            if constexpr (!(DBG & 2)) load_b(p, kn, bq[p]);
+            if constexpr (!(DBG & DBG_NO_U_LOADS)) load_b(p, kn, bq[p]);
             __builtin_amdgcn_sched_barrier(0);
         }
         __builtin_amdgcn_s_barrier();                 // every wave has read buffer kc & 1; chunk kc + 1 is in the other one
@@ -175,7 +241,6 @@ __device__ __forceinline__ void product_wave(const FArgs& a, float* smem, unsign
             for (int i = 0; i < 4; ++i) mx[((pos0 + p) * TB + 4 * kq + i) * MLD + j * 16 + n] = acc[p][j][i];
 }
 
-// DBG (attribution builds, -DVIDC_WFUSED_ATTRIB + VIDC_WFUSED_DBG): 1 no MFMAs, 2 no U loads in the loop, 4 no transform (barriers only), 8 no fold / stores
 // NB = 16-channel blocks per workgroup: 2 (32 output channels) when the layer fills the chip that way, 1 for launches of few groups (the head / tail ticks of
 // a stream: twice the workgroups, half the products each).  A tile's result bits do not depend on NB: the same K order and fold per output element.
 template <int NB, int DBG>
@@ -198,77 +263,19 @@ wino4_fused_kernel(const FArgs a) {
         const int tt = tid - 64 * NPW, lane = tid & 63;
         const int w8 = __builtin_amdgcn_readfirstlane(tt >> 6), grp = w8 >> 2;
         const int u_ = tt & 255, m = u_ >> 4, c = u_ & 15;
-        const int tpf = a.th * a.tw;
-        // ---- patch stage: LDS-DMA instruction j of a chunk moves pixel slots 16 j .. 16 j + 15 (slot = 37 tile + pixel) x 4 channel quads, 1 KiB, into
-        // [slot][16 ch]; a pixel outside the map, the 37th slot of a tile and tiles beyond T get an out-of-range offset and arrive as zeros.
-        // Wave w8 issues instructions w8, w8 + 8, ...; their per-lane offsets are computed once.
-        constexpr unsigned OOB = 0x80000000u;
-        unsigned voff[5];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int j = w8 + 8 * i;
-            const int slot = 16 * j + (lane >> 2), quad = lane & 3;
-            const int ts = slot / XSLOT, px = slot - ts * XSLOT;
-            const int t = tb * TB + ts;
-            bool ok = j < NDMA && px < 36 && t < a.T;
-            const int tc = ok ? t : 0;
-            const int b = tc / tpf, rem = tc - b * tpf, ty = rem / a.tw, tx = rem - ty * a.tw;
-            const int r = px / 6, s = px - r * 6;
-            const int iy = ty * 4 - 1 + r, ix = tx * 4 - 1 + s;
-            ok = ok && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-            voff[i] = ok ? (unsigned)(((size_t)((b * a.H + iy) * a.W + ix) * a.ldx + (size_t)g * a.x_gs + quad * 4) * 4) : OOB;
-        }
-        const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-        auto dma = [&](int cc) {                      // chunk cc -> stage buffer cc & 1
-            float* dst = smem + 2 * VBUF + (cc & 1) * XBUF;
-            const int soff = cc * KC * 4;
-#pragma unroll
-            for (int i = 0; i < 5; ++i)
-                if (w8 + 8 * i < NDMA) __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (lds_void_t*)(dst + (w8 + 8 * i) * 256), 16, (int)voff[i], soff, 0, 0);
-        };
-        // ---- phase A: the thread's 6 x 6 patch of chunk cc from the stage -> V = B^T d B in registers (out[36]); phase B (one iteration later, when the
-        // product waves have left that V buffer): out -> [pos][tile][16 ch], 16-byte unit (c >> 2) XOR (m >> 2) & 3
+        // ---- patch stage (patch_offsets): wave w8 issues instructions w8, w8 + 8, ...; their per-lane offsets are computed once
+        constexpr int FDMA = (NDMA + NTW - 1) / NTW;
+        unsigned voff[FDMA];
+        patch_offsets<FDMA, NTW>(a, tb, g, w8, lane, voff);
+        const __amdgpu_buffer_rsrc_t x_rsrc = patch_rsrc(a);
+        auto dma = [&](int cc) { patch_dma<FDMA, NTW>(x_rsrc, smem, cc & 1, w8, voff, cc * KC * 4); };      // chunk cc -> stage buffer cc & 1
+        // ---- phase A: the thread's patch of chunk cc -> V in registers (out[36]); phase B (one iteration later, when the product waves have left that
+        // V buffer): out -> V buffer cc & 1
         float out[36];
-        const unsigned x_thr = lds0 + (unsigned)((2 * VBUF + (m * XSLOT) * KC + c) * 4);
-        const unsigned v_thr = lds0 + (unsigned)((m * KC + (((c >> 2) ^ ((m >> 2) & 3)) * 4) + (c & 3)) * 4);
-        auto phase_a = [&](int cc) {
-            const unsigned xa = x_thr + (unsigned)((cc & 1) * XBUF * 4);
-            float D[36];
-#define VIDC_RD(i) D[i] = lds_read_b32<(i) * KC * 4>(xa);
-            VIDC_RD(0) VIDC_RD(1) VIDC_RD(2) VIDC_RD(3) VIDC_RD(4) VIDC_RD(5) VIDC_RD(6) VIDC_RD(7) VIDC_RD(8) VIDC_RD(9) VIDC_RD(10) VIDC_RD(11)
-            VIDC_RD(12) VIDC_RD(13) VIDC_RD(14) VIDC_RD(15) VIDC_RD(16) VIDC_RD(17) VIDC_RD(18) VIDC_RD(19) VIDC_RD(20) VIDC_RD(21) VIDC_RD(22) VIDC_RD(23)
-            VIDC_RD(24) VIDC_RD(25) VIDC_RD(26) VIDC_RD(27) VIDC_RD(28) VIDC_RD(29) VIDC_RD(30) VIDC_RD(31) VIDC_RD(32) VIDC_RD(33) VIDC_RD(34) VIDC_RD(35)
-#undef VIDC_RD
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(D[0]), "+v"(D[1]), "+v"(D[2]), "+v"(D[3]), "+v"(D[4]), "+v"(D[5]), "+v"(D[6]), "+v"(D[7]), "+v"(D[8]), "+v"(D[9]), "+v"(D[10]), "+v"(D[11]), "+v"(D[12]), "+v"(D[13]), "+v"(D[14]), "+v"(D[15]), "+v"(D[16]), "+v"(D[17]) :: "memory");
-            asm volatile("" : "+v"(D[18]), "+v"(D[19]), "+v"(D[20]), "+v"(D[21]), "+v"(D[22]), "+v"(D[23]), "+v"(D[24]), "+v"(D[25]), "+v"(D[26]), "+v"(D[27]), "+v"(D[28]), "+v"(D[29]), "+v"(D[30]), "+v"(D[31]), "+v"(D[32]), "+v"(D[33]), "+v"(D[34]), "+v"(D[35]) :: "memory");
-            float tcol[6][6];
-#pragma unroll
-            for (int s = 0; s < 6; ++s) {
-                float col[6], o6[6];
-#pragma unroll
-                for (int r = 0; r < 6; ++r) col[r] = D[r * 6 + s];
-                bt6(col, o6);
-#pragma unroll
-                for (int r = 0; r < 6; ++r) tcol[r][s] = o6[r];
-            }
-#pragma unroll
-            for (int r = 0; r < 6; ++r) {
-                float o6[6];
-                bt6(tcol[r], o6);
-#pragma unroll
-                for (int s = 0; s < 6; ++s) out[r * 6 + s] = o6[s];
-            }
-        };
-        auto phase_b = [&](int cc) {
-            const unsigned va = v_thr + (unsigned)((cc & 1) * VBUF * 4);
-#define VIDC_WR(i) lds_write_b32<(i) * TB * KC * 4>(va, out[i]);
-            VIDC_WR(0) VIDC_WR(1) VIDC_WR(2) VIDC_WR(3) VIDC_WR(4) VIDC_WR(5) VIDC_WR(6) VIDC_WR(7) VIDC_WR(8) VIDC_WR(9) VIDC_WR(10) VIDC_WR(11)
-            VIDC_WR(12) VIDC_WR(13) VIDC_WR(14) VIDC_WR(15) VIDC_WR(16) VIDC_WR(17) VIDC_WR(18) VIDC_WR(19) VIDC_WR(20) VIDC_WR(21) VIDC_WR(22) VIDC_WR(23)
-            VIDC_WR(24) VIDC_WR(25) VIDC_WR(26) VIDC_WR(27) VIDC_WR(28) VIDC_WR(29) VIDC_WR(30) VIDC_WR(31) VIDC_WR(32) VIDC_WR(33) VIDC_WR(34) VIDC_WR(35)
-#undef VIDC_WR
-        };
+        auto phase_a = [&](int cc) { patch_to_v(patch_addr(lds0, m, c, cc & 1), out); };
+        auto phase_b = [&](int cc) { v_store(v_addr(lds0, m, c, cc & 1), out); };
         auto fence_barrier = [&]() {                  // own DMA landed, own LDS writes done
-            if constexpr (DBG & 16) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (attribution: the DMA is not waited for -- wrong results, right schedule)
+            if constexpr (DBG & DBG_F4_DMA_NOT_AWAITED) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         };
@@ -284,7 +291,7 @@ wino4_fused_kernel(const FArgs a) {
         fence_barrier();
         // ---- iteration it (the product waves multiply chunk it): group it & 1 does A(it + 2), the other group B(it + 1); chunk it + 3 is staged
         for (int it = 0; it < NK; ++it) {
-            if (!(DBG & 4)) {
+            if (!(DBG & DBG_NO_TRANSFORM)) {
                 if (it + 3 < NK) dma(it + 3);
                 if ((it & 1) == grp) {
                     if (it + 2 < NK) phase_a(it + 2);
@@ -300,9 +307,8 @@ wino4_fused_kernel(const FArgs a) {
     if (tid < TB * 16 * NB) {
         const int m = tid / (16 * NB), c = tid - m * (16 * NB);
         const int t = tb * TB + m;
-        if (t >= a.T || (DBG & 8)) return;
-        const int tpf = a.th * a.tw;
-        const int b = t / tpf, rem = t - b * tpf, ty = rem / a.tw, tx = rem - ty * a.tw;
+        if (t >= a.T || (DBG & DBG_NO_FOLD)) return;
+        const TileCoords tl = tile_coords(a, t);
         const float* mx = smem + m * MLD + c;
         float tc[4][6];
 #pragma unroll
@@ -310,29 +316,26 @@ wino4_fused_kernel(const FArgs a) {
             float col[6], o4[4];
 #pragma unroll
             for (int r = 0; r < 6; ++r) col[r] = mx[(r * 6 + s) * TB * MLD];
-            at6(col, o4);
+            Wino<4>::at(col, o4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) tc[r][s] = o4[r];
         }
         const int ch = nb * 16 * NB + c;
         const float s1 = a.s1[(size_t)g * a.p_gs + ch], b1 = a.b1[(size_t)g * a.p_gs + ch];
-        const bool aff2 = a.flags & VIDC_AFFINE2;
-        const float s2 = aff2 ? a.s2[(size_t)g * a.p_gs + ch] : 0.f, b2 = aff2 ? a.b2[(size_t)g * a.p_gs + ch] : 0.f;
-        const float lo1 = (a.flags & VIDC_RELU1) ? 0.f : -INFINITY, lo2 = (a.flags & VIDC_RELU2) ? 0.f : -INFINITY;
+        const vidc::WinoEpilogue epilogue(a.flags);
+        const float s2 = epilogue.aff2 ? a.s2[(size_t)g * a.p_gs + ch] : 0.f, b2 = epilogue.aff2 ? a.b2[(size_t)g * a.p_gs + ch] : 0.f;
         float* yb = a.y + (size_t)g * a.y_gs + ch;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float o4[4];
-            at6(tc[r], o4);
-            const int oy = ty * 4 + r;
+            Wino<4>::at(tc[r], o4);
+            const int oy = tl.ty * 4 + r;
             if (oy >= a.H) continue;
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                const int ox = tx * 4 + s;
+                const int ox = tl.tx * 4 + s;
                 if (ox >= a.W) continue;
-                float o = fmaxf(o4[s] * s1 + b1, lo1);
-                if (aff2) o = fmaxf(o * s2 + b2, lo2);
-                yb[((size_t)(b * a.H + oy) * a.W + ox) * a.ldy] = o;
+                yb[((size_t)(tl.b * a.H + oy) * a.W + ox) * a.ldy] = epilogue(o4[s], s1, b1, s2, b2);
             }
         }
     }
@@ -344,9 +347,10 @@ wino4_fused_kernel(const FArgs a) {
 // (item = 16 tiles x 64 output channels of one group; (group, 64-channel block) fastest, as above), and the four chunks of all its items form ONE
 // stream of steps q = 4 i + kc through the same two V buffers and two patch stages:
 //
-//   waves 4..7 (transform), thread = (tile, channel): in step q they issue the LDS-DMA of step q + 2 and compute and write V of step q + 1 -- across
-//       item boundaries, so the patches and the transform of an item's first chunks run under the products of the item before it.  A block of tiles
-//       is transformed once for the 64 output channels of the item.
+//   waves 4..7 (transform): the transform stage above on another schedule -- four waves, not two groups of four; in step q they issue the LDS-DMA
+//       of step q + 2 (its offsets recomputed at an item's first step) and compute AND write V of step q + 1 in one go -- across item boundaries, so
+//       the patches and the transform of an item's first chunks run under the products of the item before it.  A block of tiles is transformed once
+//       for the 64 output channels of the item.
 //   waves 0..3 (products), one per SIMD: wave w owns output channels 16 w .. 16 w + 15 of the item and ALL 36 positions (36 accumulators of
 //       v_mfma_f32_16x16x4_f32 = 144 registers; two positions are interleaved so that no MFMA waits for the one before it).  U comes from L2 in the
 //       fragment order of vidc_winograd_weight_pack_fused, six positions ahead, across steps and items.  U is the MFMA's A operand and V its B operand
@@ -368,7 +372,6 @@ constexpr int SRING = 6;                             // U fragments (positions) 
 constexpr int SDMA = (NDMA + SNTW - 1) / SNTW;       // LDS-DMA instructions per transform wave and chunk
 static_assert(NPOS % SRING == 0 && SRING % 2 == 0, "the ring slot of a position is a compile-time constant");
 
-// DBG: the attribution bits of the form above (1 no MFMAs, 2 no U loads in the loop, 4 no patches / transform, 8 no fold / stores, 16 the fold without its stores)
 template <int DBG>
 __device__ __forceinline__ void stem_product_wave(const FArgs& a, unsigned lds0, int lane, int w, int S) {
     const int n = lane & 15, kq = lane >> 4;
@@ -411,7 +414,7 @@ __device__ __forceinline__ void stem_product_wave(const FArgs& a, unsigned lds0,
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                if constexpr (!(DBG & 1)) {
+                if constexpr (!(DBG & DBG_NO_MFMA)) {
                     acc[p0] = __builtin_amdgcn_mfma_f32_16x16x4f32(bq[p0 % SRING][ks], fa[c][0][ks], acc[p0], 0, 0, 0);
                     acc[p0 + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(bq[(p0 + 1) % SRING][ks], fa[c][1][ks], acc[p0 + 1], 0, 0, 0);
                 } else if (ks == 0) {
@@ -419,7 +422,7 @@ __device__ __forceinline__ void stem_product_wave(const FArgs& a, unsigned lds0,
                     acc[p0 + 1][0] += fa[c][1][0] + fa[c][1][3] + bq[(p0 + 1) % SRING][0] + bq[(p0 + 1) % SRING][3];
                 }
             }
-            if constexpr (!(DBG & 2)) {
+            if constexpr (!(DBG & DBG_NO_U_LOADS)) {
                 const int pn = p0 + SRING;
                 const float* s = pn < NPOS ? cur + (size_t)pn * pos_stride : nxt + (size_t)(pn - NPOS) * pos_stride;
                 bq[p0 % SRING] = *reinterpret_cast<const f32x4*>(s);
@@ -433,18 +436,18 @@ __device__ __forceinline__ void stem_product_wave(const FArgs& a, unsigned lds0,
         // ---- the item is complete: U was the MFMA's A operand and V its B operand, so the lane holds M[pos][channel 4 kq + i][tile n] -- one tile and
         // four consecutive channels: fold + epilogue as in the form above per channel, one 16-byte store per output pixel.  The column pass goes column by
         // column so that the accumulators die as it proceeds.
-        if (!(DBG & 8) || a.H < 0) {                  // (attribution: the fold stays in the code and never runs)
+        if (!(DBG & DBG_NO_FOLD) || a.H < 0) {        // (attribution: the fold stays in the code and never runs)
             const int I = (int)blockIdx.x + (q >> 2) * (int)gridDim.x;
             const int tb = I / a.gn, r_ = I - tb * a.gn, g = r_ / a.nbn, h = r_ - g * a.nbn;
             const int ch = h * 64 + w * 16 + 4 * kq;
-            const bool aff2 = a.flags & VIDC_AFFINE2;
+            const vidc::WinoEpilogue epilogue(a.flags);
+            const bool aff2 = epilogue.aff2;
             const size_t pof = (size_t)g * a.p_gs + ch;
-            const float lo1 = (a.flags & VIDC_RELU1) ? 0.f : -INFINITY, lo2 = (a.flags & VIDC_RELU2) ? 0.f : -INFINITY;
-            const int tpf = a.th * a.tw;
-            const int t = tb * TB + n, tcl = t < a.T ? t : 0;
-            const int b = tcl / tpf, rem = tcl - b * tpf, ty = rem / a.tw, tx = rem - ty * a.tw;
-            const bool okt = t < a.T && (!(DBG & 16) || a.H < 0);          // (attribution: the fold without its stores)
-            float* yb = a.y + (size_t)g * a.y_gs + ch + ((size_t)(b * a.H + ty * 4) * a.W + tx * 4) * a.ldy;
+            const int t = tb * TB + n;
+            const TileCoords tl = tile_coords(a, t < a.T ? t : 0);
+            const int ty = tl.ty, tx = tl.tx;
+            const bool okt = t < a.T && (!(DBG & DBG_STEM_FOLD_NO_STORES) || a.H < 0);
+            float* yb = a.y + (size_t)g * a.y_gs + ch + ((size_t)(tl.b * a.H + ty * 4) * a.W + tx * 4) * a.ldy;
             float tc[4][4][6];                        // [channel][row][column]
 #pragma unroll
             for (int s = 0; s < 6; ++s) {
@@ -453,7 +456,7 @@ __device__ __forceinline__ void stem_product_wave(const FArgs& a, unsigned lds0,
                     float col[6], o4[4];
 #pragma unroll
                     for (int r = 0; r < 6; ++r) col[r] = acc[r * 6 + s][i];
-                    at6(col, o4);
+                    Wino<4>::at(col, o4);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) tc[i][r][s] = o4[r];
                 }
@@ -466,13 +469,9 @@ __device__ __forceinline__ void stem_product_wave(const FArgs& a, unsigned lds0,
                 float o[4][4];                        // [channel][column]
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    at6(tc[i][r], o[i]);
+                    Wino<4>::at(tc[i][r], o[i]);
 #pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        float v = fmaxf(o[i][s] * s1[i] + b1[i], lo1);
-                        if (aff2) v = fmaxf(v * s2[i] + b2[i], lo2);
-                        o[i][s] = v;
-                    }
+                    for (int s = 0; s < 4; ++s) o[i][s] = epilogue(o[i][s], s1[i], b1[i], s2[i], b2[i]);
                 }
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
@@ -501,72 +500,20 @@ wino4_fused_stem_kernel(const FArgs a, const int nitems) {
     const int tt = tid - 64 * SNPW, lane = tid & 63;
     const int w4 = __builtin_amdgcn_readfirstlane(tt >> 6);
     const int m = tt >> 4, c = tt & 15;
-    const int tpf = a.th * a.tw;
-    // ---- patch stage as in the form above; wave w4 issues instructions w4, w4 + 4, ...; their per-lane offsets are computed once per item
-    constexpr unsigned OOB = 0x80000000u;
+    // ---- patch stage: wave w4 issues instructions w4, w4 + 4, ...; their per-lane offsets are computed once per item
     unsigned voff[SDMA];
-    auto item_offsets = [&](int I) {
-        const int tb = I / a.gn, r_ = I - tb * a.gn, g = r_ / a.nbn;
-#pragma unroll
-        for (int i = 0; i < SDMA; ++i) {
-            const int j = w4 + SNTW * i;
-            const int slot = 16 * j + (lane >> 2), quad = lane & 3;
-            const int ts = slot / XSLOT, px = slot - ts * XSLOT;
-            const int t = tb * TB + ts;
-            bool ok = j < NDMA && px < 36 && t < a.T;
-            const int tc = ok ? t : 0;
-            const int b = tc / tpf, rem = tc - b * tpf, ty = rem / a.tw, tx = rem - ty * a.tw;
-            const int r = px / 6, s = px - r * 6;
-            const int iy = ty * 4 - 1 + r, ix = tx * 4 - 1 + s;
-            ok = ok && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-            voff[i] = ok ? (unsigned)(((size_t)((b * a.H + iy) * a.W + ix) * a.ldx + (size_t)g * a.x_gs + quad * 4) * 4) : OOB;
-        }
-    };
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t x_rsrc = patch_rsrc(a);
     auto dma = [&](int q) {                           // step q -> stage buffer q & 1
-        if ((q & 3) == 0) item_offsets((int)blockIdx.x + (q >> 2) * (int)gridDim.x);
-        float* dst = smem + 2 * VBUF + (q & 1) * XBUF;
-        const int soff = (q & 3) * KC * 4;
-#pragma unroll
-        for (int i = 0; i < SDMA; ++i)
-            if (w4 + SNTW * i < NDMA) __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (lds_void_t*)(dst + (w4 + SNTW * i) * 256), 16, (int)voff[i], soff, 0, 0);
+        if ((q & 3) == 0) {
+            const int I = (int)blockIdx.x + (q >> 2) * (int)gridDim.x, tb = I / a.gn;
+            patch_offsets<SDMA, SNTW>(a, tb, (I - tb * a.gn) / a.nbn, w4, lane, voff);
+        }
+        patch_dma<SDMA, SNTW>(x_rsrc, smem, q & 1, w4, voff, (q & 3) * KC * 4);
     };
-    const unsigned x_thr = lds0 + (unsigned)((2 * VBUF + (m * XSLOT) * KC + c) * 4);
-    const unsigned v_thr = lds0 + (unsigned)((m * KC + (((c >> 2) ^ ((m >> 2) & 3)) * 4) + (c & 3)) * 4);
-    // the thread's 6 x 6 patch of step q from the stage -> V = B^T d B -> [pos][tile][16 ch] of V buffer q & 1, 16-byte unit (c >> 2) XOR (m >> 2) & 3
-    auto transform = [&](int q) {
-        const unsigned xa = x_thr + (unsigned)((q & 1) * XBUF * 4);
-        float D[36], out[36];
-#define VIDC_RD(i) D[i] = lds_read_b32<(i) * KC * 4>(xa);
-        VIDC_RD(0) VIDC_RD(1) VIDC_RD(2) VIDC_RD(3) VIDC_RD(4) VIDC_RD(5) VIDC_RD(6) VIDC_RD(7) VIDC_RD(8) VIDC_RD(9) VIDC_RD(10) VIDC_RD(11)
-        VIDC_RD(12) VIDC_RD(13) VIDC_RD(14) VIDC_RD(15) VIDC_RD(16) VIDC_RD(17) VIDC_RD(18) VIDC_RD(19) VIDC_RD(20) VIDC_RD(21) VIDC_RD(22) VIDC_RD(23)
-        VIDC_RD(24) VIDC_RD(25) VIDC_RD(26) VIDC_RD(27) VIDC_RD(28) VIDC_RD(29) VIDC_RD(30) VIDC_RD(31) VIDC_RD(32) VIDC_RD(33) VIDC_RD(34) VIDC_RD(35)
-#undef VIDC_RD
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(D[0]), "+v"(D[1]), "+v"(D[2]), "+v"(D[3]), "+v"(D[4]), "+v"(D[5]), "+v"(D[6]), "+v"(D[7]), "+v"(D[8]), "+v"(D[9]), "+v"(D[10]), "+v"(D[11]), "+v"(D[12]), "+v"(D[13]), "+v"(D[14]), "+v"(D[15]), "+v"(D[16]), "+v"(D[17]) :: "memory");
-        asm volatile("" : "+v"(D[18]), "+v"(D[19]), "+v"(D[20]), "+v"(D[21]), "+v"(D[22]), "+v"(D[23]), "+v"(D[24]), "+v"(D[25]), "+v"(D[26]), "+v"(D[27]), "+v"(D[28]), "+v"(D[29]), "+v"(D[30]), "+v"(D[31]), "+v"(D[32]), "+v"(D[33]), "+v"(D[34]), "+v"(D[35]) :: "memory");
-        float tcol[6][6];
-#pragma unroll
-        for (int s = 0; s < 6; ++s) {
-            float col[6], o6[6];
-#pragma unroll
-            for (int r = 0; r < 6; ++r) col[r] = D[r * 6 + s];
-            bt6(col, o6);
-#pragma unroll
-            for (int r = 0; r < 6; ++r) tcol[r][s] = o6[r];
-        }
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            float o6[6];
-            bt6(tcol[r], o6);
-#pragma unroll
-            for (int s = 0; s < 6; ++s) out[r * 6 + s] = o6[s];
-        }
-        const unsigned va = v_thr + (unsigned)((q & 1) * VBUF * 4);
-#define VIDC_WR(i) lds_write_b32<(i) * TB * KC * 4>(va, out[i]);
-        VIDC_WR(0) VIDC_WR(1) VIDC_WR(2) VIDC_WR(3) VIDC_WR(4) VIDC_WR(5) VIDC_WR(6) VIDC_WR(7) VIDC_WR(8) VIDC_WR(9) VIDC_WR(10) VIDC_WR(11)
-        VIDC_WR(12) VIDC_WR(13) VIDC_WR(14) VIDC_WR(15) VIDC_WR(16) VIDC_WR(17) VIDC_WR(18) VIDC_WR(19) VIDC_WR(20) VIDC_WR(21) VIDC_WR(22) VIDC_WR(23)
-        VIDC_WR(24) VIDC_WR(25) VIDC_WR(26) VIDC_WR(27) VIDC_WR(28) VIDC_WR(29) VIDC_WR(30) VIDC_WR(31) VIDC_WR(32) VIDC_WR(33) VIDC_WR(34) VIDC_WR(35)
-#undef VIDC_WR
+    auto transform = [&](int q) {                     // the thread's patch of step q -> V -> V buffer q & 1, in one go
+        float out[36];
+        patch_to_v(patch_addr(lds0, m, c, q & 1), out);
+        v_store(v_addr(lds0, m, c, q & 1), out);
     };
     auto fence_barrier = [&]() {                      // own DMA landed, own LDS reads and writes done
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -581,7 +528,7 @@ wino4_fused_stem_kernel(const FArgs a, const int nitems) {
     // ---- step q (the product waves multiply it): step q + 2 is staged into the buffer transform(q) has left, V of step q + 1 goes into the buffer the
     // product waves left at the barrier before
     for (int q = 0; q < S; ++q) {
-        if (!(DBG & 4)) {
+        if (!(DBG & DBG_NO_TRANSFORM)) {
             if (q + 2 < S) dma(q + 2);
             if (q + 1 < S) transform(q + 1);
         }
@@ -607,14 +554,8 @@ wino4_pack_kernel(const float* __restrict__ u, float* __restrict__ o, int Cout, 
 }
 
 template <int NB, int DBG>
-int launch_nb(const FArgs& a, long long wgs, hipStream_t st) {
-    static bool attr_set[64] = {};
-    int dev = 0;
-    VIDC_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        VIDC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino4_fused_kernel<NB, DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
+int launch_form4(const FArgs& a, long long wgs, hipStream_t st) {
+    if (const int rc = vidc::allow_dynamic_lds<&wino4_fused_kernel<NB, DBG>>(LDS_BYTES)) return rc;
     hipLaunchKernelGGL((wino4_fused_kernel<NB, DBG>), dim3((unsigned)wgs), dim3(NTHREADS), LDS_BYTES, st, a);
     VIDC_CHECK_LAUNCH("wino4_fused_kernel");
     return VIDC_OK;
@@ -624,15 +565,10 @@ int launch_nb(const FArgs& a, long long wgs, hipStream_t st) {
 // the tests force several items per workgroup at small shapes with it).
 template <int DBG>
 int launch_stem(FArgs& a, int groups, hipStream_t st) {
-    static bool attr_set[64] = {};
     static int cus[64] = {};
     int dev = 0;
-    VIDC_HIP(hipGetDevice(&dev));
+    if (const int rc = vidc::allow_dynamic_lds<&wino4_fused_stem_kernel<DBG>>(LDS_BYTES, &dev)) return rc;
     const bool cached = dev >= 0 && dev < 64;
-    if (!cached || !attr_set[dev]) {
-        VIDC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino4_fused_stem_kernel<DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-        if (cached) attr_set[dev] = true;
-    }
     int ncu = cached ? cus[dev] : 0;
     if (ncu <= 0) {
         VIDC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
@@ -650,8 +586,19 @@ int launch_stem(FArgs& a, int groups, hipStream_t st) {
     return VIDC_OK;
 }
 
-template <int DBG>
-int launch_dbg(const FArgs& a, long long wgs, hipStream_t st) { return a.nbn * 32 == a.Cout ? launch_nb<2, DBG>(a, wgs, st) : launch_nb<1, DBG>(a, wgs, st); }
+// launch(std::integral_constant<int, DBG>): in an attribution build with the DBG that VIDC_WFUSED_DBG names, if it is one of Vs -- the values a form
+// has an instantiation for; otherwise, and in every other build, with 0.
+typedef std::integer_sequence<int, 1, 2, 3, 4, 6, 7, 8, 15, 16> Form4Dbg;
+typedef std::integer_sequence<int, 1, 2, 3, 4, 7, 8, 10, 15, 16> StemDbg;
+template <int... Vs, typename F>
+int with_dbg(std::integer_sequence<int, Vs...>, F&& launch) {
+#ifdef VIDC_WFUSED_ATTRIB
+    static const int dbg = [] { const char* e = getenv("VIDC_WFUSED_DBG"); return e ? atoi(e) : 0; }();
+    int rc = VIDC_OK;
+    if (((dbg == Vs && (rc = launch(std::integral_constant<int, Vs>{}), true)) || ...)) return rc;
+#endif
+    return launch(std::integral_constant<int, 0>{});
+}
 
 }  // namespace
 
@@ -691,43 +638,14 @@ int launch_wino4_fused(const vidc_conv_desc& d, hipStream_t st) {
                          (!(d.flags & VIDC_AFFINE2) || (al16(d.scale2) && al16(d.shift2)));
         const bool stem = d.Cin == 64 && d.Cout % 64 == 0 && y16 && (long long)a.T * d.groups * (d.Cout / 64) >= min_tiles;
         if (const char* e = getenv("VIDC_WFUSED_TRACE")) if (atoi(e)) fprintf(stderr, "wino4f: form %s Cin %d Cout %d tiles %d groups %d\n", stem ? "stem" : "4", d.Cin, d.Cout, a.T, d.groups);
-        if (stem) {
-#ifdef VIDC_WFUSED_ATTRIB
-            static const int sdbg = [] { const char* e = getenv("VIDC_WFUSED_DBG"); return e ? atoi(e) : 0; }();
-            switch (sdbg) {
-                case 1: return launch_stem<1>(a, d.groups, st);
-                case 2: return launch_stem<2>(a, d.groups, st);
-                case 4: return launch_stem<4>(a, d.groups, st);
-                case 8: return launch_stem<8>(a, d.groups, st);
-                case 3: return launch_stem<3>(a, d.groups, st);
-                case 7: return launch_stem<7>(a, d.groups, st);
-                case 10: return launch_stem<10>(a, d.groups, st);
-                case 15: return launch_stem<15>(a, d.groups, st);
-                case 16: return launch_stem<16>(a, d.groups, st);
-                default: break;
-            }
-#endif
-            return launch_stem<0>(a, d.groups, st);
-        }
+        if (stem) return with_dbg(StemDbg{}, [&](auto dbg) { return launch_stem<decltype(dbg)::value>(a, d.groups, st); });
     }
     const long long wgs = (long long)((a.T + TB - 1) / TB) * a.gn;
     VIDC_REQUIRE(wgs < (1ll << 31), VIDC_ERR_SHAPE, "conv (fused Winograd): grid too large");
-#ifdef VIDC_WFUSED_ATTRIB
-    static const int dbg = [] { const char* e = getenv("VIDC_WFUSED_DBG"); return e ? atoi(e) : 0; }();
-    switch (dbg) {
-        case 1: return launch_dbg<1>(a, wgs, st);
-        case 2: return launch_dbg<2>(a, wgs, st);
-        case 4: return launch_dbg<4>(a, wgs, st);
-        case 8: return launch_dbg<8>(a, wgs, st);
-        case 3: return launch_dbg<3>(a, wgs, st);
-        case 6: return launch_dbg<6>(a, wgs, st);
-        case 7: return launch_dbg<7>(a, wgs, st);
-        case 15: return launch_dbg<15>(a, wgs, st);
-        case 16: return launch_dbg<16>(a, wgs, st);
-        default: break;
-    }
-#endif
-    return launch_dbg<0>(a, wgs, st);
+    return with_dbg(Form4Dbg{}, [&](auto dbg) {
+        constexpr int DBG = decltype(dbg)::value;
+        return a.nbn * 32 == a.Cout ? launch_form4<2, DBG>(a, wgs, st) : launch_form4<1, DBG>(a, wgs, st);
+    });
 }
 
 }  // namespace vidc

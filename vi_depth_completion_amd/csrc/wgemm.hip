@@ -254,13 +254,7 @@ wgemm_stream_kernel(const WArgs a) {
 template <int NB, int NSR>
 int launch_cfg(const WArgs& a, int padded_chunks, hipStream_t st) {
     typedef Cfg<NB, NSR> C_;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    VIDC_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        VIDC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgemm_stream_kernel<NB, NSR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C_::LDS_BYTES));
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
+    if (const int rc = vidc::allow_dynamic_lds<&wgemm_stream_kernel<NB, NSR>>(C_::LDS_BYTES)) return rc;
     hipLaunchKernelGGL((wgemm_stream_kernel<NB, NSR>), dim3((unsigned)(padded_chunks * a.tiles_n)), dim3(64 * C_::NWV), C_::LDS_BYTES, st, a);
     VIDC_CHECK_LAUNCH("wgemm_stream_kernel");
     return VIDC_OK;

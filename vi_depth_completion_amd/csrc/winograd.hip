@@ -24,6 +24,7 @@
 // same layer, and hipcc contracts `a - 4 * b` into an fma in one instantiation and not in the other -- a frame's bits then depended on
 // which tick of a lane computed it (tests/test_frames_per_launch.py).  Every product and sum below rounds once, like the numpy oracle.
 #pragma clang fp contract(off)
+#include "wino_math.h"          // Wino<m>::bt / ::at and the epilogue value, shared with csrc/wfused.hip
 
 namespace {
 
@@ -83,42 +84,7 @@ template <int N> __device__ __forceinline__ void vstore_split(unsigned short* im
     }
 }
 
-// B^T d for one column (input transform) and A^T m for one column (output transform); the standard matrices of Lavin & Gray
-// ("Fast Algorithms for Convolutional Neural Networks", 2015) with interpolation points 0, +-1 (m = 2) and 0, +-1, +-2 (m = 4).
-template <int M_> struct Wino;
-template <> struct Wino<2> {
-    static constexpr int A = 4;
-    template <typename V> __device__ static __forceinline__ void bt(const V (&d)[4], V (&t)[4]) {
-        t[0] = d[0] - d[2];
-        t[1] = d[1] + d[2];
-        t[2] = d[2] - d[1];
-        t[3] = d[1] - d[3];
-    }
-    template <typename V> __device__ static __forceinline__ void at(const V (&m)[4], V (&o)[2]) {
-        o[0] = (m[0] + m[1]) + m[2];
-        o[1] = (m[1] - m[2]) - m[3];
-    }
-};
-template <> struct Wino<4> {
-    static constexpr int A = 6;
-    template <typename V> __device__ static __forceinline__ void bt(const V (&d)[6], V (&t)[6]) {
-        const V p = d[4] - 4.f * d[2], q = d[3] - 4.f * d[1];
-        const V r = d[4] - d[2], s = 2.f * (d[3] - d[1]);
-        t[0] = (4.f * d[0] - 5.f * d[2]) + d[4];
-        t[1] = p + q;
-        t[2] = p - q;
-        t[3] = r + s;
-        t[4] = r - s;
-        t[5] = (4.f * d[1] - 5.f * d[3]) + d[5];
-    }
-    template <typename V> __device__ static __forceinline__ void at(const V (&m)[6], V (&o)[4]) {
-        const V s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-        o[0] = (m[0] + s12) + s34;
-        o[1] = d12 + 2.f * d34;
-        o[2] = s12 + 4.f * s34;
-        o[3] = (d12 + 8.f * d34) + m[5];
-    }
-};
+using vidc::Wino;
 
 // XCD k takes the k-th contiguous band of the (tile row, column block) space (see pointwise.hip xcd_band_block: neighbouring tile rows
 // share a - m input rows, which then hit the same L2).  gridDim.x is a multiple of 8.
@@ -216,12 +182,10 @@ wino_out_kernel(const float* __restrict__ mm, float* __restrict__ y, unsigned sh
 #pragma unroll
         for (int r = 0; r < M_; ++r) t[r][s] = out[r];
     }
-    // the epilogue of conv_mfma.hip: acc * s1 + b1 -> relu -> [* s2 + b2 -> relu]; ReLU off = max with -inf
     const V s1 = vload<N>(&scale1[c]), b1 = vload<N>(&shift1[c]);
-    const float lo1 = (flags & VIDC_RELU1) ? 0.f : -INFINITY, lo2 = (flags & VIDC_RELU2) ? 0.f : -INFINITY;
-    const bool aff2 = flags & VIDC_AFFINE2;
+    const vidc::WinoEpilogue epilogue(flags);
     V s2 = vzero<N>(), b2 = vzero<N>();
-    if (aff2) { s2 = vload<N>(&scale2[c]); b2 = vload<N>(&shift2[c]); }
+    if (epilogue.aff2) { s2 = vload<N>(&scale2[c]); b2 = vload<N>(&shift2[c]); }
     const bool st_f32 = !(flags & VIDC_NO_F32_OUT);
 #pragma unroll
     for (int r = 0; r < M_; ++r) {
@@ -235,10 +199,10 @@ wino_out_kernel(const float* __restrict__ mm, float* __restrict__ y, unsigned sh
             if (ox >= Wo) continue;
             V o = out[s];
 #pragma unroll
-            for (int k = 0; k < N; ++k) o.v[k] = fmaxf(o.v[k] * s1.v[k] + b1.v[k], lo1);
-            if (aff2) {
+            for (int k = 0; k < N; ++k) o.v[k] = epilogue.stage(o.v[k], s1.v[k], b1.v[k], epilogue.lo1);
+            if (epilogue.aff2) {
 #pragma unroll
-                for (int k = 0; k < N; ++k) o.v[k] = fmaxf(o.v[k] * s2.v[k] + b2.v[k], lo2);
+                for (int k = 0; k < N; ++k) o.v[k] = epilogue.stage(o.v[k], s2.v[k], b2.v[k], epilogue.lo2);
             }
             const size_t row = (size_t)(b * Ho + oy) * Wo + ox;
             if (st_f32) vstore<N>(&y[row * ldy + c], o);
