@@ -27,7 +27,10 @@ added here is the counted one (the two roundings of xh), built like all others f
 the shapes below: largest error / bound 2.14 without the term (shape (257, 132, 160); 1.29 at (63, 68, 72): a row with a closed gate and
 |xh| = 3.0 in a channel with |S g' xh| = 0.004 S |g' xh|), 0.44 with it.  Every other bound held as first derived (largest ratio 0.49).
 """
+import hashlib
+import json
 import math
+import os
 
 import pytest
 import torch
@@ -616,3 +619,182 @@ def test_grad_narrow_widen_exact(n):
         assert (math.isnan(float(back[i])) if math.isnan(v) else float(back[i]) == float(torch.tensor(v).to(torch.bfloat16))), (i, v)
     if n > 6:
         assert float(back[4]) == math.inf and float(back[5]) == -math.inf and math.isnan(float(back[6]))
+
+
+# ---- GPU: the bits of every row kernel, as recorded before the kernels shared their bodies ----------------------------------------------------
+BITS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_rows_bits.json")
+BITS_SHAPE = (70, 68, 72)         # a ragged last channel block (68 = 64 + 4), a ragged last 64-row tile (70 = 64 + 6) and a ragged 16-row lane
+
+
+def _sha(*tensors):
+    """SHA-256 of the raw bytes of the tensors, one after the other (None: skipped)."""
+    h = hashlib.sha256()
+    for t in tensors:
+        if t is not None:
+            h.update(t.detach().contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()
+
+
+def _sha_dict(out):
+    return _sha(*[out[k] for k in sorted(out)])
+
+
+def _chunk_table(x, rows):
+    """The per-channel partial sums of x [M][C] in chan_partial_kernel's layout, [chunk][sum x | sum x^2][C] in float64 for chunks of `rows`
+    rows, each chunk added row by row on the CPU (a fixed order: the same table everywhere)."""
+    M, C = x.shape
+    t = torch.zeros((M + rows - 1) // rows, 2, C, dtype=F64)
+    for r in range(M):
+        v = x[r].to(F64)
+        t[r // rows, 0] += v
+        t[r // rows, 1] += v * v
+    return t
+
+
+def _bits_bn(L, bits):
+    lib = L.lib()
+    M, C, ld = BITS_SHAPE
+    d = _data(M, C)
+    for with_res in (0, 1):
+        for relu in (0, 1):
+            for with_bf16 in (0, 1):
+                a, b = _both_folds(lib, lambda: _run_forward(L, d, ld, relu, bool(with_res), bool(with_bf16)))
+                for fold, out in ((0, a), (1, b)):
+                    bits["bn_forward/res%d_relu%d_bf16%d_fold%d" % (with_res, relu, with_bf16, fold)] = _sha_dict(out)
+    # vidc_bn_train_forward_stats: the chunk sums come from the conv that wrote x, one pair of rows per 32 output rows
+    ldx, ldy, ldr, _ = _strides(C, ld)
+    stats = _chunk_table(d.x, 32).to(DEV)
+    for with_res, relu, with_bf16 in ((0, 0, 0), (1, 1, 1)):
+        x, y = _rows(d.x, ldx), torch.full((M, ldy), SENTINEL, device=DEV)
+        res = _rows(d.res, ldr) if with_res else None
+        gamma, beta, rm, rv = d.gamma.to(DEV), d.beta.to(DEV), d.rm.to(DEV), d.rv.to(DEV)
+        mean, rstd = torch.full((C,), float("nan"), device=DEV), torch.full((C,), float("nan"), device=DEV)
+        yb = torch.full((M, C), -1, dtype=torch.int16, device=DEV) if with_bf16 else None
+        sc = _scratch(lib, M, C)
+        L.check(lib.vidc_bn_train_forward_stats(L.ptr(x), L.ptr(y), M, C, ldx, ldy, L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), EPS, MOMENTUM, relu,
+                                                L.ptr(mean), L.ptr(rstd), L.ptr(yb), L.ptr(res), ldr, L.ptr(stats), L.ptr(sc), L.current_stream()),
+                "bn forward stats")
+        torch.cuda.synchronize()
+        bits["bn_forward_stats/res%d_relu%d_bf16%d" % (with_res, relu, with_bf16)] = _sha(y, yb, mean, rstd, rm, rv)
+    mean, rstd, y_relu = _backward_inputs(d)
+    for y_in in (None, y_relu):
+        for with_dx, with_bf16, with_t in ((1, 0, 0), (1, 1, 0), (1, 1, 1), (0, 1, 1)):
+            a, b = _both_folds(lib, lambda: _run_backward(L, d, ld, mean, rstd, y_in, with_dx, with_bf16, with_t))
+            for fold, out in ((0, a), (1, b)):
+                bits["bn_backward/y%d_dx%d_bf16%d_t%d_fold%d" % (y_in is not None, with_dx, with_bf16, with_t, fold)] = _sha_dict(out)
+
+
+def _bits_rows(L, bits):
+    lib = L.lib()
+    M, C, ld = 5, 12, 16
+    g = torch.Generator().manual_seed(21)
+    a, b, old = torch.randn(M, C, generator=g), torch.randn(M, C, generator=g), torch.randn(M, C, generator=g)
+    b[::2, ::3] = 0.0
+    b[1::2, 1::3] = -0.0
+    ad, bd = _rows(a, ld), _rows(b, ld)
+    out = torch.full((C,), float("nan"), device=DEV)
+    sc = _scratch(lib, M, C)
+    L.check(lib.vidc_colsum(L.ptr(ad), M, C, ld, L.ptr(out), L.ptr(sc), L.current_stream()), "colsum")
+    bits["colsum"] = _sha(out)
+    for relu in (0, 1):
+        for with_bf16 in (0, 1):
+            y = torch.full((M, ld), SENTINEL, device=DEV)
+            yb = torch.full((M, C), -1, dtype=torch.int16, device=DEV) if with_bf16 else None
+            L.check(lib.vidc_add_rows_bf16(L.ptr(ad), L.ptr(bd), L.ptr(y), M, C, ld, ld, ld, relu, L.ptr(yb), L.current_stream()), "add_rows_bf16")
+            bits["add_rows/relu%d_bf16%d" % (relu, with_bf16)] = _sha(y, yb)
+    for y_in in (None, bd):
+        for accumulate in (0, 1):
+            dx = _rows(old, ld, SENTINEL)
+            L.check(lib.vidc_relu_backward(L.ptr(ad), L.ptr(y_in), L.ptr(dx), M, C, ld, ld, ld, accumulate, L.current_stream()), "relu_backward")
+            bits["relu_backward/y%d_acc%d" % (y_in is not None, accumulate)] = _sha(dx)
+    x8 = torch.randn(M, 8, generator=g)
+    x8[0, :len(_TIES)] = torch.tensor(_TIES)
+    xd, y = _rows(x8, ld), torch.full((M, 8), -1, dtype=torch.int16, device=DEV)
+    L.check(lib.vidc_cast_bf16(L.ptr(xd), L.ptr(y), M, 8, ld, L.current_stream()), "cast_bf16")
+    bits["cast_bf16"] = _sha(y)
+
+
+def _bits_pool_upsample(L, bits):
+    """Both launch forms of each: four channels per thread (aligned, strides multiples of 4) and one (forced by lddx = C + 1)."""
+    lib = L.lib()
+    B, C = 2, 8
+    g = torch.Generator().manual_seed(22)
+    for H, W in ((5, 7), (6, 4), (1, 1)):
+        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        x = torch.randint(0, 4, (B, H, W, C), generator=g).float().to(DEV)          # small integers: ties in most windows
+        dy = torch.randn(B, Ho, Wo, C, generator=g).to(DEV)
+        for form, lddx in (("wide", C), ("scalar", C + 1)):
+            dx = torch.full((B, H, W, lddx), SENTINEL, device=DEV)
+            L.check(lib.vidc_maxpool3x3s2_backward(L.ptr(x), L.ptr(dy), L.ptr(dx), B, H, W, C, C, C, lddx, L.current_stream()), "maxpool_bwd")
+            bits["maxpool_backward/%dx%d_%s" % (H, W, form)] = _sha(dx[..., :C])
+            assert bool((dx[..., C:] == SENTINEL).all())
+    for h, w, H, W in ((3, 4, 7, 9), (1, 1, 3, 3), (4, 4, 4, 4)):                    # the second has scale 0, the third is the identity
+        dy = torch.randn(B, H, W, C, generator=g).to(DEV)
+        for form, lddx in (("wide", C), ("scalar", C + 1)):
+            dx = torch.full((B, h, w, lddx), SENTINEL, device=DEV)
+            L.check(lib.vidc_upsample_bilinear_ac_backward(L.ptr(dy), L.ptr(dx), B, h, w, C, C, lddx, H, W, L.current_stream()), "upsample_bwd")
+            bits["upsample_backward/%dx%d_to_%dx%d_%s" % (h, w, H, W, form)] = _sha(dx[..., :C])
+            assert bool((dx[..., C:] == SENTINEL).all())
+
+
+def _bits_im2col(L, bits):
+    """The whole xt buffer over a constant pre-fill: the padding columns m >= M and every byte the kernel leaves alone are pinned too."""
+    lib = L.lib()
+    B, H, W, stride, pad = 2, 5, 6, 2, 1
+    g = torch.Generator().manual_seed(23)
+    for C, ldx in ((8, 12), (6, 8)):                                                 # the 64 x 64 kernel; the 32 x 32 one (C % 4 != 0)
+        x = _rows(torch.randn(B * H * W, C, generator=g), ldx)
+        for k in (3, 1):
+            for dil in (1, 2):
+                Ho, Wo = (H + 2 * pad - dil * (k - 1) - 1) // stride + 1, (W + 2 * pad - dil * (k - 1) - 1) // stride + 1
+                M = B * Ho * Wo
+                for split in (0, 1, 2, 4, 5, 6):
+                    Mp = (M + 63) // 64 * 64 if split & 3 == 2 else (M + 31) // 32 * 32
+                    xt = torch.full((k * k * C, Mp), SENTINEL, device=DEV)
+                    if dil == 1:
+                        L.check(lib.vidc_im2col_transposed(L.ptr(x), L.ptr(xt), B, H, W, C, ldx, Ho, Wo, k, k, stride, pad, Mp, split, L.current_stream()),
+                                "im2col_transposed")
+                    else:
+                        L.check(lib.vidc_im2col_transposed_dilated(L.ptr(x), L.ptr(xt), B, H, W, C, ldx, Ho, Wo, k, k, stride, pad, dil, Mp, split,
+                                                                   L.current_stream()), "im2col_transposed_dilated")
+                    bits["im2col/C%d_k%d_dil%d_split%d" % (C, k, dil, split)] = _sha(xt)
+    for C in (8, 72):
+        xb = _rne(torch.randn(B * H * W, C, generator=g)).to(DEV)
+        for k in (3, 1):
+            Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+            Mp = (B * Ho * Wo + 63) // 64 * 64
+            xt = torch.full((k * k * C, Mp), -1, dtype=torch.int16, device=DEV)
+            L.check(lib.vidc_im2col_transposed_bf16(L.ptr(xb), L.ptr(xt), B, H, W, C, Ho, Wo, k, k, stride, pad, Mp, L.current_stream()), "im2col_transposed_bf16")
+            bits["im2col_bf16/C%d_k%d" % (C, k)] = _sha(xt)
+        xt = torch.full((C, 64), -1, dtype=torch.int16, device=DEV)
+        L.check(lib.vidc_transpose_bf16(L.ptr(xb), L.ptr(xt), B * H * W, C, 64, L.current_stream()), "transpose_bf16")
+        bits["transpose_bf16/C%d" % C] = _sha(xt)
+
+
+def _train_rows_bits():
+    """name -> SHA-256 of the raw output bytes of every kernel of csrc/train.hip that is built from the shared row helpers and bodies, each at the
+    smallest shape that reaches all of its branches.  Inputs are seeded CPU tensors."""
+    from vi_depth_completion_amd import _lib as L
+    bits = {}
+    _bits_bn(L, bits)
+    _bits_rows(L, bits)
+    _bits_pool_upsample(L, bits)
+    _bits_im2col(L, bits)
+    return bits
+
+
+@gpu
+def test_output_bits_are_those_recorded_before_the_kernels_shared_their_bodies():
+    """tests/golden/train_rows_bits.json was recorded on an MI355X from the library as it was when the BatchNorm apply and backward kernels, the
+    max-pool and upsampling backward kernels and the im2col kernels each had two or three copies of their body: sharing one body per map, and the
+    row-quad helpers of csrc/train_rows.h, changed no output bit (and no later change to them may, unless it says so)."""
+    got = _train_rows_bits()
+    with open(BITS_JSON) as f:
+        want = json.load(f)
+    assert sorted(got) == sorted(want)
+    assert not [k for k in want if got[k] != want[k]], [k for k in want if got[k] != want[k]]
+    for k in want:                                                                   # the launch forms of one map wrote the same bytes
+        if k.endswith("_fold1"):
+            assert want[k] == want[k[:-1] + "0"], k
+        if k.endswith("_scalar"):
+            assert want[k] == want[k[:-len("scalar")] + "wide"], k

@@ -9,13 +9,16 @@
 // Layout: activations NHWC fp32, `ld` = channel stride of a row (a tensor may be a channel slice of a concat buffer).  Per-channel
 // reductions accumulate in fp64 with a fixed two-level order (bit-reproducible), like torch's CPU kernels accumulate float in double.
 #include "common.h"
+#include "train_rows.h"
 #include <cstdint>
+#include <type_traits>
 
 namespace {
 
 using vidc::TT;
 using vidc::blocks;
 using vidc::block_tree;
+using vidc::row_quad, vidc::load4, vidc::store4, vidc::store4_bf16, vidc::store8_bf16, vidc::relu_mask4;      // train_rows.h
 
 // What the per-channel sums become, applied by the thread that finishes a channel in chan_final_kernel (no extra launch).
 // batch mean, biased variance and invstd from the two per-channel sums (shared by chan_final_kernel's FinalStats and the kernels that
@@ -93,6 +96,54 @@ __device__ __forceinline__ void column_sums(const double* __restrict__ partial, 
     }
 }
 
+// ---- BatchNorm on one row quad (train_rows.h): the one forward body and the one backward body of every launch form ------------------
+// y = x * alpha + bb with alpha = invstd * gamma, bb = beta - mean * alpha (torch's batch_norm_cpu_transform_input), + res (the Bottleneck
+// tail relu(bn3(.) + identity) in the same pass: the BatchNorm value is rounded to fp32 before the sum, as when a separate add kernel read
+// it back), ReLU optional; y_bf16 != NULL: also the bf16 operand copy the next conv of a VIDC_PREC_BF16 step reads (dense rows of C bf16),
+// saving its cast launch.  Row r, channels c..c+3 of every tensor; res and y_bf16 may be NULL.
+__device__ __forceinline__ void bn_apply_row(long long r, int c, const float* __restrict__ x, int ldx, const float* __restrict__ res, int ldr,
+                                             float* __restrict__ y, int ldy, unsigned short* __restrict__ y_bf16, int C, const float* alpha,
+                                             const float* bb, int relu) {
+    float in[4], out[4], add[4] = {0.f, 0.f, 0.f, 0.f};
+    load4(x + r * ldx + c, in);
+    if (res) load4(res + r * ldr + c, add);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float o = in[k] * alpha[k] + bb[k];
+        if (res) o = __fadd_rn(o, add[k]);
+        out[k] = relu ? fmaxf(o, 0.f) : o;
+    }
+    store4(y + r * ldy + c, out);
+    if (y_bf16) store4_bf16(y_bf16 + r * C + c, out);
+}
+// The operands of the backward: g holds dy on entry and dy' = dy * (y > 0) on return (y != NULL: the output of the ReLU that followed the
+// BatchNorm), xh = (x - mean) * invstd.  Shared by the reduction (chan_partial_kernel<1>) and the apply pass (bn_bwd_row).
+__device__ __forceinline__ void bn_bwd_operands(float* g, float* xh, long long r, int c, const float* __restrict__ x, int ldx,
+                                                const float* __restrict__ y, int ldy, const float* mu, const float* rs) {
+    float xv[4];
+    load4(x + r * ldx + c, xv);
+    if (y) {
+        float yv[4];
+        load4(y + r * ldy + c, yv);
+        relu_mask4(g, yv);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) xh[k] = (xv[k] - mu[k]) * rs[k];
+}
+// dx = gs * (dy' - m1 - xhat * m2) with gs = gamma * invstd, m1 = sum(dy') / M, m2 = sum(dy' * xhat) / M (dgamma = sum(dy' * xhat), dbeta =
+// sum(dy')); o -> dx (NULL: nobody reads the fp32 form) and dx_bf16 (dense rows of C bf16; NULL: not wanted), and back to the caller.
+__device__ __forceinline__ void bn_bwd_row(long long r, int c, const float* __restrict__ dy, int lddy, const float* __restrict__ x, int ldx,
+                                           const float* __restrict__ y, int ldy, float* __restrict__ dx, int lddx, unsigned short* __restrict__ dx_bf16,
+                                           int C, const float* mu, const float* rs, const float* gs, const float* m1, const float* m2, float* o) {
+    float g[4], xh[4];
+    load4(dy + r * lddy + c, g);
+    bn_bwd_operands(g, xh, r, c, x, ldx, y, ldy, mu, rs);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = gs[k] * (g[k] - m1[k] - xh[k] * m2[k]);
+    if (dx) store4(dx + r * lddx + c, o);
+    if (dx_bf16) store4_bf16(dx_bf16 + r * C + c, o);
+}
+
 // ---- per-channel sums over rows: partial[chunk][q][C] (fp64) -------------------------------------------------------------------------
 // block = 256 threads = 64 channels x 4 row-lanes; grid = (C/64 rounded up, n_chunks).  MODE 0: sum x, sum x^2.  MODE 1 (BN backward):
 // sum dy', sum dy' * xhat with dy' = dy * (y > 0) when y != NULL (the ReLU that followed the BatchNorm).
@@ -113,25 +164,16 @@ chan_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, co
             for (int k = 0; k < 4; ++k) { mu[k] = mean[c + k]; rs[k] = rstd[c + k]; }
         }
         for (long long r = r0 + rl; r < r1; r += 16) {
-            const float4 av = *reinterpret_cast<const float4*>(a + r * lda + c);
-            float g[4] = {av.x, av.y, av.z, av.w};
+            float g[4];
+            load4(a + r * lda + c, g);
             if (MODE == 0) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { const double v = (double)g[k]; s0[k] += v; s1[k] += v * v; }
             } else {
-                const float4 bv = *reinterpret_cast<const float4*>(b + r * ldb + c);
-                const float xv[4] = {bv.x, bv.y, bv.z, bv.w};
-                if (y) {
-                    const float4 yv4 = *reinterpret_cast<const float4*>(y + r * ldy + c);
-                    const float yv[4] = {yv4.x, yv4.y, yv4.z, yv4.w};
+                float xh[4];
+                bn_bwd_operands(g, xh, r, c, b, ldb, y, ldy, mu, rs);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) if (!(yv[k] > 0.f)) g[k] = 0.f;
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float xh = (xv[k] - mu[k]) * rs[k];
-                    s0[k] += (double)g[k]; s1[k] += (double)g[k] * (double)xh;
-                }
+                for (int k = 0; k < 4; ++k) { s0[k] += (double)g[k]; s1[k] += (double)g[k] * (double)xh[k]; }
             }
         }
     }
@@ -211,87 +253,46 @@ bn_apply_fold_kernel(const float* __restrict__ x, float* __restrict__ y, int M, 
     for (int rr = 0; rr < 4; ++rr) {
         const int r = m0 + ty + 16 * rr;
         if (r >= M) continue;
-        const float4 v = *reinterpret_cast<const float4*>(x + (size_t)r * ldx + c);
-        float in[4] = {v.x, v.y, v.z, v.w}, out[4], add[4] = {0.f, 0.f, 0.f, 0.f};
-        if (res) {
-            const float4 q = *reinterpret_cast<const float4*>(res + (size_t)r * ldr + c);
-            add[0] = q.x; add[1] = q.y; add[2] = q.z; add[3] = q.w;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float o = in[k] * alpha[k] + bb[k];
-            if (res) o = __fadd_rn(o, add[k]);
-            out[k] = relu ? fmaxf(o, 0.f) : o;
-        }
-        *reinterpret_cast<float4*>(y + (size_t)r * ldy + c) = make_float4(out[0], out[1], out[2], out[3]);
-        if (y_bf16)
-            *reinterpret_cast<uint2*>(y_bf16 + (size_t)r * C + c) = make_uint2(vidc::bf16_rne(out[0]) | ((unsigned)vidc::bf16_rne(out[1]) << 16),
-                                                                               vidc::bf16_rne(out[2]) | ((unsigned)vidc::bf16_rne(out[3]) << 16));
+        bn_apply_row(r, c, x, ldx, res, ldr, y, ldy, y_bf16, C, alpha, bb, relu);
     }
 }
 
-// y = x * alpha + beta' with alpha = invstd * gamma, beta' = beta - mean * alpha (torch's batch_norm_cpu_transform_input), ReLU optional
+// bn_apply_row on a flat launch, one thread per row quad, from the statistics chan_final_kernel<FinalStats> left in mean / rstd
 __global__ void __launch_bounds__(TT)
 bn_apply_kernel(const float* __restrict__ x, float* __restrict__ y, long long M, int C, int ldx, int ldy, const float* __restrict__ mean,
                 const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta, int relu,
                 unsigned short* __restrict__ y_bf16, const float* __restrict__ res, int ldr) {
-    const int c4 = C >> 2;
-    const long long i = (long long)blockIdx.x * TT + threadIdx.x;
-    if (i >= M * c4) return;
-    const long long r = i / c4;
-    const int c = (int)(i - r * c4) * 4;
-    const float4 v = *reinterpret_cast<const float4*>(x + r * ldx + c);
-    float in[4] = {v.x, v.y, v.z, v.w}, out[4], add[4] = {0.f, 0.f, 0.f, 0.f};
-    if (res) {          // Bottleneck tail: relu(bn3(.) + identity) in the same pass (the BatchNorm value is rounded to fp32 before the sum, as when
-        const float4 q = *reinterpret_cast<const float4*>(res + r * ldr + c);      // it was stored and read back by a separate add kernel)
-        add[0] = q.x; add[1] = q.y; add[2] = q.z; add[3] = q.w;
-    }
+    long long r;
+    int c;
+    if (!row_quad(M, C, r, c)) return;
+    float alpha[4], bb[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float alpha = rstd[c + k] * gamma[c + k];
-        const float bb = beta[c + k] - mean[c + k] * alpha;
-        float o = in[k] * alpha + bb;
-        if (res) o = __fadd_rn(o, add[k]);
-        out[k] = relu ? fmaxf(o, 0.f) : o;
+        alpha[k] = rstd[c + k] * gamma[c + k];
+        bb[k] = beta[c + k] - mean[c + k] * alpha[k];
     }
-    *reinterpret_cast<float4*>(y + r * ldy + c) = make_float4(out[0], out[1], out[2], out[3]);
-    if (y_bf16)         // the bf16 operand copy the next conv of a VIDC_PREC_BF16 step reads (dense rows of C bf16), saving its cast launch
-        *reinterpret_cast<uint2*>(y_bf16 + r * C + c) = make_uint2(vidc::bf16_rne(out[0]) | ((unsigned)vidc::bf16_rne(out[1]) << 16),
-                                                                   vidc::bf16_rne(out[2]) | ((unsigned)vidc::bf16_rne(out[3]) << 16));
+    bn_apply_row(r, c, x, ldx, res, ldr, y, ldy, y_bf16, C, alpha, bb, relu);
 }
 
-// dx = gamma * invstd * (dy' - sum(dy')/M - xhat * sum(dy' * xhat)/M); dgamma = sum(dy' * xhat); dbeta = sum(dy')
+// bn_bwd_row on a flat launch, one thread per row quad, from the sums chan_final_kernel<FinalParamGrad> left in sums[2][C]
 __global__ void __launch_bounds__(TT)
 bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ dx, long long M, int C,
                     int lddy, int ldx, int ldy, int lddx, const float* __restrict__ mean, const float* __restrict__ rstd,
                     const float* __restrict__ gamma, const double* __restrict__ sums, unsigned short* __restrict__ dx_bf16) {
-    const int c4 = C >> 2;
-    const long long i = (long long)blockIdx.x * TT + threadIdx.x;
-    if (i >= M * c4) return;
-    const long long r = i / c4;
-    const int c = (int)(i - r * c4) * 4;
-    const float4 g4 = *reinterpret_cast<const float4*>(dy + r * lddy + c), x4 = *reinterpret_cast<const float4*>(x + r * ldx + c);
-    float g[4] = {g4.x, g4.y, g4.z, g4.w}, xv[4] = {x4.x, x4.y, x4.z, x4.w}, o[4];
-    if (y) {
-        const float4 y4 = *reinterpret_cast<const float4*>(y + r * ldy + c);
-        const float yv[4] = {y4.x, y4.y, y4.z, y4.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) if (!(yv[k] > 0.f)) g[k] = 0.f;
-    }
+    long long r;
+    int c;
+    if (!row_quad(M, C, r, c)) return;
     const double invM = 1.0 / (double)M;
+    float mu[4], rs[4], gs[4], m1[4], m2[4], o[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float xh = (xv[k] - mean[c + k]) * rstd[c + k];
-        const float m1 = (float)(sums[c + k] * invM), m2 = (float)(sums[C + c + k] * invM);
-        o[k] = gamma[c + k] * rstd[c + k] * (g[k] - m1 - xh * m2);
+        mu[k] = mean[c + k]; rs[k] = rstd[c + k]; gs[k] = gamma[c + k] * rs[k];
+        m1[k] = (float)(sums[c + k] * invM); m2[k] = (float)(sums[C + c + k] * invM);
     }
-    *reinterpret_cast<float4*>(dx + r * lddx + c) = make_float4(o[0], o[1], o[2], o[3]);
-    if (dx_bf16)
-        *reinterpret_cast<uint2*>(dx_bf16 + r * C + c) = make_uint2(vidc::bf16_rne(o[0]) | ((unsigned)vidc::bf16_rne(o[1]) << 16),
-                                                                    vidc::bf16_rne(o[2]) | ((unsigned)vidc::bf16_rne(o[3]) << 16));
+    bn_bwd_row(r, c, dy, lddy, x, ldx, y, ldy, dx, lddx, dx_bf16, C, mu, rs, gs, m1, m2, o);
 }
 
-// The same map on 64 pixels x 64 channels per workgroup, which ALSO writes the transpose of dx as plain bf16 rows [C][Mp] (zero for
+// bn_bwd_row on 64 pixels x 64 channels per workgroup, which ALSO writes the transpose of dx as plain bf16 rows [C][Mp] (zero for
 // m >= M): dx of the BatchNorm behind a conv is that conv's dY, and its weight-gradient GEMM reads dY^T in exactly this format
 // (vidc_im2col_transposed(..., KH = KW = 1, split = 2) -- one launch and one pass over dY per conv that this kernel makes unnecessary).
 // LDS tile [pixel][channel], pitch 65 floats, both phases as in im2col_t64_kernel; every value is rounded once, from the fp32 result.
@@ -335,26 +336,7 @@ bn_bwd_apply_t64_kernel(const float* __restrict__ dy, const float* __restrict__ 
     for (int r = 0; r < 4; ++r) {
         const int m = m0 + ty + 16 * r;
         float o[4] = {0.f, 0.f, 0.f, 0.f};
-        if (m < M && c < C) {
-            const float4 g4 = *reinterpret_cast<const float4*>(dy + (size_t)m * lddy + c), x4 = *reinterpret_cast<const float4*>(x + (size_t)m * ldx + c);
-            float g[4] = {g4.x, g4.y, g4.z, g4.w};
-            const float xv[4] = {x4.x, x4.y, x4.z, x4.w};
-            if (y) {
-                const float4 y4 = *reinterpret_cast<const float4*>(y + (size_t)m * ldy + c);
-                const float yv[4] = {y4.x, y4.y, y4.z, y4.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) if (!(yv[k] > 0.f)) g[k] = 0.f;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float xh = (xv[k] - mu[k]) * rs[k];
-                o[k] = gs[k] * (g[k] - m1[k] - xh * m2[k]);
-            }
-            if (dx) *reinterpret_cast<float4*>(dx + (size_t)m * lddx + c) = make_float4(o[0], o[1], o[2], o[3]);      // (NULL: nobody reads the fp32 form)
-            if (dx_bf16)
-                *reinterpret_cast<uint2*>(dx_bf16 + (size_t)m * C + c) = make_uint2(vidc::bf16_rne(o[0]) | ((unsigned)vidc::bf16_rne(o[1]) << 16),
-                                                                                    vidc::bf16_rne(o[2]) | ((unsigned)vidc::bf16_rne(o[3]) << 16));
-        }
+        if (m < M && c < C) bn_bwd_row(m, c, dy, lddy, x, ldx, y, ldy, dx, lddx, dx_bf16, C, mu, rs, gs, m1, m2, o);
         float* t = &tile[ty + 16 * r][tx * 4];
         t[0] = o[0]; t[1] = o[1]; t[2] = o[2]; t[3] = o[3];
     }
@@ -365,8 +347,7 @@ bn_bwd_apply_t64_kernel(const float* __restrict__ dy, const float* __restrict__ 
         const int cl = ty + 16 * r, cc = c0 + cl, m = m0 + tx * 4;
         if (cc < C && m < Mp) {
             const float v[4] = {tile[tx * 4][cl], tile[tx * 4 + 1][cl], tile[tx * 4 + 2][cl], tile[tx * 4 + 3][cl]};
-            *reinterpret_cast<uint2*>(dx_bf16_t + (size_t)cc * Mp + m) = make_uint2((unsigned)vidc::bf16_rne(v[0]) | ((unsigned)vidc::bf16_rne(v[1]) << 16),
-                                                                                    (unsigned)vidc::bf16_rne(v[2]) | ((unsigned)vidc::bf16_rne(v[3]) << 16));
+            store4_bf16(dx_bf16_t + (size_t)cc * Mp + m, v);
         }
     }
 }
@@ -376,95 +357,94 @@ bn_bwd_apply_t64_kernel(const float* __restrict__ dy, const float* __restrict__ 
 __global__ void __launch_bounds__(TT)
 add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ y, long long M, int C, int lda, int ldb, int ldy, int relu,
            unsigned short* __restrict__ y_bf16) {
-    const int c4 = C >> 2;
-    const long long i = (long long)blockIdx.x * TT + threadIdx.x;
-    if (i >= M * c4) return;
-    const long long r = i / c4;
-    const int c = (int)(i - r * c4) * 4;
-    const float4 u = *reinterpret_cast<const float4*>(a + r * lda + c), v = *reinterpret_cast<const float4*>(b + r * ldb + c);
-    float4 o = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
-    if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
-    *reinterpret_cast<float4*>(y + r * ldy + c) = o;
-    if (y_bf16)         // the bf16 operand copy (dense rows) the convs of the next block read in a VIDC_PREC_BF16 step: saves their cast launches
-        *reinterpret_cast<uint2*>(y_bf16 + r * C + c) = make_uint2(vidc::bf16_rne(o.x) | ((unsigned)vidc::bf16_rne(o.y) << 16),
-                                                                   vidc::bf16_rne(o.z) | ((unsigned)vidc::bf16_rne(o.w) << 16));
+    long long r;
+    int c;
+    if (!row_quad(M, C, r, c)) return;
+    float u[4], v[4], o[4];
+    load4(a + r * lda + c, u);
+    load4(b + r * ldb + c, v);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = u[k] + v[k];
+    if (relu) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = fmaxf(o[k], 0.f);
+    }
+    store4(y + r * ldy + c, o);
+    if (y_bf16) store4_bf16(y_bf16 + r * C + c, o);      // the bf16 operand copy (dense rows) the convs of the next block read in a VIDC_PREC_BF16 step
 }
 
 // dx (=|+=) dy * (y > 0)   (y NULL: plain copy / accumulate)
 __global__ void __launch_bounds__(TT)
 relu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, float* __restrict__ dx, long long M, int C, int lddy, int ldy, int lddx, int accumulate) {
-    const int c4 = C >> 2;
-    const long long i = (long long)blockIdx.x * TT + threadIdx.x;
-    if (i >= M * c4) return;
-    const long long r = i / c4;
-    const int c = (int)(i - r * c4) * 4;
-    float4 g = *reinterpret_cast<const float4*>(dy + r * lddy + c);
+    long long r;
+    int c;
+    if (!row_quad(M, C, r, c)) return;
+    float g[4];
+    load4(dy + r * lddy + c, g);
     if (y) {
-        const float4 v = *reinterpret_cast<const float4*>(y + r * ldy + c);
-        if (!(v.x > 0.f)) g.x = 0.f;
-        if (!(v.y > 0.f)) g.y = 0.f;
-        if (!(v.z > 0.f)) g.z = 0.f;
-        if (!(v.w > 0.f)) g.w = 0.f;
+        float v[4];
+        load4(y + r * ldy + c, v);
+        relu_mask4(g, v);
     }
-    float4* d = reinterpret_cast<float4*>(dx + r * lddx + c);
-    if (accumulate) { const float4 o = *d; g.x += o.x; g.y += o.y; g.z += o.z; g.w += o.w; }
-    *d = g;
+    float* d = dx + r * lddx + c;
+    if (accumulate) {
+        float o[4];
+        load4(d, o);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[k] += o[k];
+    }
+    store4(d, g);
 }
+
+// ---- gather kernels over the pixels of an NHWC tensor: one thread per V consecutive channels of a pixel ----------------------------
+// V = 4: a row quad through 16-byte accesses and 32-bit offsets (C and the strides multiples of 4, 16-byte aligned tensors below 2^31
+// elements: the pyramids' 64-channel maps; the host entry points check).  V = 1: any C, stride and size, 64-bit offsets.  Per channel both
+// instantiations of a kernel scan and add in the same order: identical bits.
+template <int V>
+struct Lanes {
+    using Index = typename std::conditional<V == 1, long long, unsigned>::type;
+    static __device__ __forceinline__ void load(const float* __restrict__ p, float* v) {
+        if constexpr (V == 4) load4(p, v); else v[0] = *p;
+    }
+    static __device__ __forceinline__ void store(float* __restrict__ p, const float* v) {
+        if constexpr (V == 4) store4(p, v); else *p = v[0];
+    }
+    // thread -> pixel (b, y, x) of a B x H x W x C tensor and first channel c; false for the threads past the end
+    static __device__ __forceinline__ bool pixel(int B, int H, int W, int C, int& b, int& y, int& x, int& c) {
+        const int cv = C / V;
+        const Index i = (Index)blockIdx.x * TT + threadIdx.x;
+        if (i >= (Index)B * H * W * cv) return false;
+        c = (int)(i % cv) * V;
+        Index p = i / cv;
+        x = (int)(p % W); p /= W;
+        y = (int)(p % H);
+        b = (int)(p / H);
+        return true;
+    }
+    // element offset of channel c of pixel (b, y, x), rows of ld channels
+    static __device__ __forceinline__ Index at(int b, int y, int x, int H, int W, int ld, int c) { return (((Index)b * H + y) * W + x) * (Index)ld + c; }
+};
 
 // ---- max-pool 3x3 / stride 2 / pad 1 backward (gather, deterministic) -------------------------------------------------------------
 // An input pixel receives dy of every window whose FIRST maximum (scan order kh, kw like torch's CPU kernel) it is.
+template <int V>
 __global__ void __launch_bounds__(TT)
 maxpool_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx, int B, int H, int W, int C, int ldx, int lddy, int lddx) {
+    using L = Lanes<V>;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const long long i = (long long)blockIdx.x * TT + threadIdx.x;
-    const long long total = (long long)B * H * W * C;
-    if (i >= total) return;
-    const int c = (int)(i % C);
-    long long p = i / C;
-    const int w = (int)(p % W); p /= W;
-    const int h = (int)(p % H);
-    const int b = (int)(p / H);
-    float acc = 0.f;
+    int b, h, w, c;
+    if (!L::pixel(B, H, W, C, b, h, w, c)) return;
+    float acc[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] = 0.f;
     for (int oy = h / 2; oy <= (h + 1) / 2; ++oy) {       // the windows with 2*oy-1 <= h <= 2*oy+1: one for even h, two for odd h
         if (oy >= Ho) continue;
         for (int ox = w / 2; ox <= (w + 1) / 2; ++ox) {
             if (ox >= Wo) continue;
-            float best = -INFINITY;
-            int bh = -1, bw = -1;
-            for (int kh = 0; kh < 3; ++kh) {
-                const int ih = 2 * oy - 1 + kh;
-                if (ih < 0 || ih >= H) continue;
-                for (int kw = 0; kw < 3; ++kw) {
-                    const int iw = 2 * ox - 1 + kw;
-                    if (iw < 0 || iw >= W) continue;
-                    const float v = x[(((long long)b * H + ih) * W + iw) * ldx + c];
-                    if (v > best || bh < 0) { best = v; bh = ih; bw = iw; }
-                }
-            }
-            if (bh == h && bw == w) acc += dy[(((long long)b * Ho + oy) * Wo + ox) * lddy + c];
-        }
-    }
-    dx[(((long long)b * H + h) * W + w) * lddx + c] = acc;
-}
-// The same map, four channels per thread with 16-byte accesses and 32-bit offsets (C, ldx, lddy, lddx multiples of 4, tensors below 2^31
-// elements: the pyramids' 64-channel pool); per channel the scan order and the additions are those of the scalar kernel: identical bits.
-__global__ void __launch_bounds__(TT)
-maxpool_bwd4_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx, int B, int H, int W, int C, int ldx, int lddy, int lddx) {
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, c4 = C >> 2;
-    const unsigned i = blockIdx.x * TT + threadIdx.x;
-    if (i >= (unsigned)B * H * W * c4) return;
-    const int c = (int)(i % c4) * 4;
-    unsigned p = i / c4;
-    const int w = (int)(p % W); p /= W;
-    const int h = (int)(p % H);
-    const int b = (int)(p / H);
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int oy = h / 2; oy <= (h + 1) / 2; ++oy) {
-        if (oy >= Ho) continue;
-        for (int ox = w / 2; ox <= (w + 1) / 2; ++ox) {
-            if (ox >= Wo) continue;
-            float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            int at[4] = {-1, -1, -1, -1};                    // kh * 3 + kw of the first maximum
+            float best[V];
+            int first[V];                                 // kh * 3 + kw of the first maximum
+#pragma unroll
+            for (int k = 0; k < V; ++k) { best[k] = -INFINITY; first[k] = -1; }
 #pragma unroll
             for (int kh = 0; kh < 3; ++kh) {
                 const int ih = 2 * oy - 1 + kh;
@@ -473,21 +453,21 @@ maxpool_bwd4_kernel(const float* __restrict__ x, const float* __restrict__ dy, f
                 for (int kw = 0; kw < 3; ++kw) {
                     const int iw = 2 * ox - 1 + kw;
                     if (iw < 0 || iw >= W) continue;
-                    const float4 v4 = *reinterpret_cast<const float4*>(x + (unsigned)((b * H + ih) * W + iw) * (unsigned)ldx + c);
-                    const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+                    float v[V];
+                    L::load(x + L::at(b, ih, iw, H, W, ldx, c), v);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (v[k] > best[k] || at[k] < 0) { best[k] = v[k]; at[k] = kh * 3 + kw; }
+                    for (int k = 0; k < V; ++k)
+                        if (v[k] > best[k] || first[k] < 0) { best[k] = v[k]; first[k] = kh * 3 + kw; }
                 }
             }
             const int mine = (h - (2 * oy - 1)) * 3 + (w - (2 * ox - 1));
-            const float4 g4 = *reinterpret_cast<const float4*>(dy + (unsigned)((b * Ho + oy) * Wo + ox) * (unsigned)lddy + c);
-            const float g[4] = {g4.x, g4.y, g4.z, g4.w};
+            float g[V];
+            L::load(dy + L::at(b, oy, ox, Ho, Wo, lddy, c), g);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) if (at[k] == mine) acc[k] += g[k];
+            for (int k = 0; k < V; ++k) if (first[k] == mine) acc[k] += g[k];
         }
     }
-    *reinterpret_cast<float4*>(dx + (unsigned)((b * H + h) * W + w) * (unsigned)lddx + c) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    L::store(dx + L::at(b, h, w, H, W, lddx, c), acc);
 }
 
 // ---- bilinear upsampling (align_corners = True) backward, gather form ------------------------------------------------------------
@@ -501,22 +481,21 @@ __device__ inline void up_src(int d, int in, int out, int& i0, int& i1, float& l
     i1 = i0 + (i0 < in - 1 ? 1 : 0);
     lam = s - (float)i0;
 }
+// (the interpolation weights of a pixel are computed once for its V channels)
+template <int V>
 __global__ void __launch_bounds__(TT)
 upsample_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int B, int h, int w, int C, int lddy, int lddx, int H, int W) {
-    const long long i = (long long)blockIdx.x * TT + threadIdx.x;
-    const long long total = (long long)B * h * w * C;
-    if (i >= total) return;
-    const int c = (int)(i % C);
-    long long p = i / C;
-    const int jj = (int)(p % w); p /= w;
-    const int ii = (int)(p % h);
-    const int b = (int)(p / h);
+    using L = Lanes<V>;
+    int b, ii, jj, c;
+    if (!L::pixel(B, h, w, C, b, ii, jj, c)) return;
     // candidate output rows: src in (ii - 1, ii + 1)  ->  dst in ((ii-1)/scale, (ii+1)/scale); scanned with a margin of one
     const float sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f, sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
     int Y0 = 0, Y1 = H - 1, X0 = 0, X1 = W - 1;
     if (sy > 0.f) { Y0 = max(0, (int)floorf((float)(ii - 1) / sy) - 1); Y1 = min(H - 1, (int)ceilf((float)(ii + 1) / sy) + 1); }
     if (sx > 0.f) { X0 = max(0, (int)floorf((float)(jj - 1) / sx) - 1); X1 = min(W - 1, (int)ceilf((float)(jj + 1) / sx) + 1); }
-    float acc = 0.f;
+    float acc[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] = 0.f;
     for (int Y = Y0; Y <= Y1; ++Y) {
         int a0, a1; float ly;
         up_src(Y, h, H, a0, a1, ly);
@@ -527,44 +506,14 @@ upsample_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int B,
             up_src(X, w, W, b0, b1, lx);
             const float wx = (b0 == jj ? 1.f - lx : 0.f) + (b1 == jj ? lx : 0.f);
             if (wx == 0.f) continue;
-            acc += wy * wx * dy[(((long long)b * H + Y) * W + X) * lddy + c];
-        }
-    }
-    dx[(((long long)b * h + ii) * w + jj) * lddx + c] = acc;
-}
-// The same map, four channels per thread (16-byte accesses, 32-bit offsets): the interpolation weights of a pixel are computed once for
-// the four; per channel the (Y, X) scan order and every product are those of the scalar kernel -- identical bits.
-__global__ void __launch_bounds__(TT)
-upsample_bwd4_kernel(const float* __restrict__ dy, float* __restrict__ dx, int B, int h, int w, int C, int lddy, int lddx, int H, int W) {
-    const int c4 = C >> 2;
-    const unsigned i = blockIdx.x * TT + threadIdx.x;
-    if (i >= (unsigned)B * h * w * c4) return;
-    const int c = (int)(i % c4) * 4;
-    unsigned p = i / c4;
-    const int jj = (int)(p % w); p /= w;
-    const int ii = (int)(p % h);
-    const int b = (int)(p / h);
-    const float sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f, sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    int Y0 = 0, Y1 = H - 1, X0 = 0, X1 = W - 1;
-    if (sy > 0.f) { Y0 = max(0, (int)floorf((float)(ii - 1) / sy) - 1); Y1 = min(H - 1, (int)ceilf((float)(ii + 1) / sy) + 1); }
-    if (sx > 0.f) { X0 = max(0, (int)floorf((float)(jj - 1) / sx) - 1); X1 = min(W - 1, (int)ceilf((float)(jj + 1) / sx) + 1); }
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int Y = Y0; Y <= Y1; ++Y) {
-        int a0, a1; float ly;
-        up_src(Y, h, H, a0, a1, ly);
-        const float wy = (a0 == ii ? 1.f - ly : 0.f) + (a1 == ii ? ly : 0.f);
-        if (wy == 0.f) continue;
-        for (int X = X0; X <= X1; ++X) {
-            int b0, b1; float lx;
-            up_src(X, w, W, b0, b1, lx);
-            const float wx = (b0 == jj ? 1.f - lx : 0.f) + (b1 == jj ? lx : 0.f);
-            if (wx == 0.f) continue;
-            const float4 g = *reinterpret_cast<const float4*>(dy + (unsigned)((b * H + Y) * W + X) * (unsigned)lddy + c);
+            float g[V];
+            L::load(dy + L::at(b, Y, X, H, W, lddy, c), g);
             const float ww = wy * wx;
-            acc[0] += ww * g.x; acc[1] += ww * g.y; acc[2] += ww * g.z; acc[3] += ww * g.w;
+#pragma unroll
+            for (int k = 0; k < V; ++k) acc[k] += ww * g[k];
         }
     }
-    *reinterpret_cast<float4*>(dx + (unsigned)((b * h + ii) * w + jj) * (unsigned)lddx + c) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    L::store(dx + L::at(b, ii, jj, h, w, lddx, c), acc);
 }
 
 // ---- nn.AvgPool2d(k, stride, padding), count_include_pad=True, backward (surface_normal_dorn.py:10), gather form -----------------------
@@ -794,15 +743,6 @@ __device__ inline void pack_store(const vidc_pack_item& it, long long off, float
         it.packed[off] = v;
     }
 }
-// Eight consecutive packed elements rounded to bf16 and written by one 16-byte store (dst 16-byte aligned).
-__device__ inline void store8_bf16(unsigned short* __restrict__ dst, const float* v) {
-    uint4 o;
-    o.x = (unsigned)vidc::bf16_rne(v[0]) | ((unsigned)vidc::bf16_rne(v[1]) << 16);
-    o.y = (unsigned)vidc::bf16_rne(v[2]) | ((unsigned)vidc::bf16_rne(v[3]) << 16);
-    o.z = (unsigned)vidc::bf16_rne(v[4]) | ((unsigned)vidc::bf16_rne(v[5]) << 16);
-    o.w = (unsigned)vidc::bf16_rne(v[6]) | ((unsigned)vidc::bf16_rne(v[7]) << 16);
-    *reinterpret_cast<uint4*>(dst) = o;
-}
 // Round 4, plain-bf16 kinds (the training mode configs[4] names; 1.41 ms for the 310 M parameters before): a thread produces eight
 // consecutive bf16 values and stores them at once (2-byte stores before), and a 1x1 forward copy -- the same order as the parameter --
 // skips the LDS round trip: 0.79 ms (4.7 TB/s).  Same values.  (A block -> item index instead of the search over block_begin was
@@ -900,15 +840,13 @@ __global__ void __launch_bounds__(TT) pack_batched_kernel(const vidc_pack_item* 
 
 // fp32 NHWC rows [rows][ldx] (C channels used) -> dense bf16 rows [rows][C] (round to nearest even); one thread per 8 channels
 __global__ void __launch_bounds__(TT) cast_bf16_kernel(const float* __restrict__ x, unsigned short* __restrict__ y, long long rows, int C, int ldx) {
-    const int c8 = C / 8;
-    const long long idx = (long long)blockIdx.x * TT + threadIdx.x;
-    if (idx >= rows * c8) return;
-    const long long r = idx / c8;
-    const int c = (int)(idx - r * c8) * 8;
-    const float4 v0 = *reinterpret_cast<const float4*>(x + r * ldx + c), v1 = *reinterpret_cast<const float4*>(x + r * ldx + c + 4);
-    const unsigned a = vidc::bf16_rne(v0.x) | ((unsigned)vidc::bf16_rne(v0.y) << 16), b = vidc::bf16_rne(v0.z) | ((unsigned)vidc::bf16_rne(v0.w) << 16);
-    const unsigned d = vidc::bf16_rne(v1.x) | ((unsigned)vidc::bf16_rne(v1.y) << 16), e = vidc::bf16_rne(v1.z) | ((unsigned)vidc::bf16_rne(v1.w) << 16);
-    *reinterpret_cast<uint4*>(y + r * C + c) = make_uint4(a, b, d, e);
+    long long r;
+    int c;
+    if (!row_quad<8>(rows, C, r, c)) return;
+    float v[8];
+    load4(x + r * ldx + c, v);
+    load4(x + r * ldx + c + 4, v + 4);
+    store8_bf16(y + r * C + c, v);
 }
 
 // z[b, oy*s, ox*s, :] = dy[b, oy, ox, :], zero elsewhere (z is B x H x W x C, dense)
@@ -1022,11 +960,25 @@ wgrad_final_kernel(const float* __restrict__ partial, int n_chunks, int taps, in
 // ---- wgrad as a GEMM on the conv kernel: transposed operands ---------------------------------------------------------------------------
 // dW[co][tap][ci] = sum_m dY^T[co][m] * Xt[tap*C + ci][m] is a plain "both operands K-contiguous" GEMM with K = the pixels -- exactly
 // the 1x1 case of conv_mfma.hip (activations = rows of dY^T, weights = rows of Xt), which runs at several times the rate of the
-// direct kernel above (LDS-tiled, split-K, fp32 or bf16x3).  This kernel builds the operands: xt[(tap*C + c)][m] = x[b, oy*s - p + kh,
-// ox*s - p + kw, c] (0 outside the image and for m >= M; rows are Mp = M rounded up to 32 long), through a 32x32 LDS transpose so that
-// both the NHWC reads and the row writes are 128-byte coalesced.  With KH = KW = 1, s = 1, p = 0 it is the transpose of dY.  dil: the tap
-// spacing of a dilated conv (x[.., oy*s - p + kh*dil, ox*s - p + kw*dil, ..]; 1 = the plain conv).  split != 0 writes
-// the rows in the split-bf16 operand format of the bf16x3 mode directly (vidc_split_bf16x3's layout; same bytes per row).
+// direct kernel above (LDS-tiled, split-K, fp32 or bf16x3).  The kernels below build the operands: xt[(tap*C + c)][m] = x[b, oy*s - p + kh*dil,
+// ox*s - p + kw*dil, c] (0 outside the image and for m >= M; rows are Mp = M rounded up to 32 long; dil: the tap spacing of a dilated conv,
+// 1 = the plain conv), through an LDS transpose so that both the NHWC reads and the row writes are coalesced.  With KH = KW = 1, s = 1,
+// p = 0 it is the transpose of dY.  split & 3: 0 writes fp32 rows, 1 the split-bf16 operand format of the bf16x3 mode (vidc_split_bf16x3's
+// layout; same bytes per row), 2 plain bf16 rows; split & 4: the rows in chan_major order.
+// The addressing, shared by the kernels.  Source: pixel m = (b, oy, ox) reads, for the tap (kh, kw), the NHWC row `row` of x; false where the
+// tap lies outside the image (row then means nothing).  Destination: the row of xt that holds channel c of a tap, tap-major (tap * C + c) or
+// chan_major (c * taps + tap: the OIHW order of a weight gradient).
+__device__ __forceinline__ bool im2col_src(int m, int kh, int kw, int H, int W, int Ho, int Wo, int stride, int pad, int dil, size_t& row) {
+    const int ox = m % Wo, q = m / Wo, oy = q % Ho, b = q / Ho;
+    const int iy = oy * stride - pad + kh * dil, ix = ox * stride - pad + kw * dil;
+    row = (size_t)(b * H + iy) * W + ix;
+    return (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
+}
+__device__ __forceinline__ size_t im2col_row(bool chan_major, int c, int tap, int taps, int C) {
+    return chan_major ? (size_t)c * taps + tap : (size_t)tap * C + c;
+}
+
+// 32 pixels x 32 channels per workgroup, element by element: any C, ldx and alignment.
 __global__ void __launch_bounds__(256)
 im2col_t_kernel(const float* __restrict__ x, float* __restrict__ xt, int B, int H, int W, int C, int ldx, int Ho, int Wo, int KH, int KW, int stride,
                 int pad, int dil, int M, int Mp, int split) {
@@ -1034,18 +986,14 @@ im2col_t_kernel(const float* __restrict__ x, float* __restrict__ xt, int B, int 
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int m0 = blockIdx.x * 32, c0 = blockIdx.y * 32, tap = blockIdx.z;
     const int kh = tap / KW, kw = tap - kh * KW;
-    const bool chan_major = split & 4;      // rows ordered c * taps + tap (the OIHW order of a weight gradient) instead of tap * C + c
+    const bool chan_major = split & 4;
     split &= 3;
-    const int taps = KH * KW;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int m = m0 + ty + 8 * r, c = c0 + tx;
         float v = 0.f;
-        if (m < M && c < C) {
-            const int ox = m % Wo, q = m / Wo, oy = q % Ho, b = q / Ho;
-            const int iy = oy * stride - pad + kh * dil, ix = ox * stride - pad + kw * dil;
-            if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = x[((size_t)(b * H + iy) * W + ix) * ldx + c];
-        }
+        size_t row;
+        if (m < M && c < C && im2col_src(m, kh, kw, H, W, Ho, Wo, stride, pad, dil, row)) v = x[row * ldx + c];
         tile[ty + 8 * r][tx] = v;
     }
     __syncthreads();
@@ -1054,8 +1002,8 @@ im2col_t_kernel(const float* __restrict__ x, float* __restrict__ xt, int B, int 
         const int c = c0 + ty + 8 * r, m = m0 + tx;
         if (c < C && m < Mp) {
             const float v = tile[tx][ty + 8 * r];
-            const size_t row = chan_major ? (size_t)c * taps + tap : (size_t)tap * C + c;
-            if (split == 2) {    // plain bf16 rows
+            const size_t row = im2col_row(chan_major, c, tap, KH * KW, C);
+            if (split == 2) {
                 reinterpret_cast<unsigned short*>(xt)[row * Mp + m] = vidc::bf16_rne(v);
             } else if (split) {  // the 32 pixels of this tile are one K unit of the GEMM: [32 x hi | 32 x lo] in the same 128 bytes
                 unsigned short h, l;
@@ -1069,91 +1017,62 @@ im2col_t_kernel(const float* __restrict__ x, float* __restrict__ xt, int B, int 
         }
     }
 }
-// The same map on 64 pixels x 64 channels per workgroup with 16-byte accesses on both sides (C % 4 == 0, ldx % 4 == 0, 16-byte aligned
-// pointers; Mp % 32 == 0 makes every 4-pixel group of a row all-inside or all-outside).  LDS tile [pixel][channel], row pitch 65 floats:
-// the 4 x 16 lanes of a wave hit 64 different banks in both phases.
+// The same map on 64 pixels x 64 channels per workgroup, one row quad per thread in and four pixels of a row of xt out (C % 4 == 0, ldx % 4 == 0,
+// aligned pointers; Mp % 32 == 0 makes every 4-pixel group of a row all-inside or all-outside).  LDS tile [pixel][channel] with an odd-word
+// row pitch: the 4 x 16 lanes of a wave hit 64 different banks in both phases.
+// T = float: the fp32 tensor, every output format.  T = unsigned short: the bf16 operand copy of x (dense rows of C bf16, what the forward conv
+// of the plain-bf16 mode read) to plain bf16 rows -- half the bytes in and no rounding step; the copy holds the rounded values, so the bits are
+// those of the fp32 form with split = 2.
+template <typename T>
 __global__ void __launch_bounds__(256)
-im2col_t64_kernel(const float* __restrict__ x, float* __restrict__ xt, int B, int H, int W, int C, int ldx, int Ho, int Wo, int KH, int KW, int stride,
-                  int pad, int dil, int M, int Mp, int split) {
-    __shared__ float tile[64][65];
+im2col_t64_kernel(const T* __restrict__ x, T* __restrict__ xt, int B, int H, int W, int C, int ldx, int Ho, int Wo, int KH, int KW, int stride, int pad,
+                  int dil, int M, int Mp, int split) {
+    constexpr bool kBf16 = sizeof(T) == 2;
+    __shared__ T tile[64][kBf16 ? 66 : 65];
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int m0 = blockIdx.x * 64, c0 = blockIdx.y * 64, tap = blockIdx.z;
     const int kh = tap / KW, kw = tap - kh * KW;
-    const bool chan_major = split & 4;      // rows ordered c * taps + tap instead of tap * C + c (see im2col_t_kernel)
+    const bool chan_major = split & 4;
     split &= 3;
-    const int taps = KH * KW;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int m = m0 + ty + 16 * r, c = c0 + tx * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (m < M && c < C) {
-            const int ox = m % Wo, q = m / Wo, oy = q % Ho, b = q / Ho;
-            const int iy = oy * stride - pad + kh * dil, ix = ox * stride - pad + kw * dil;
-            if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = *reinterpret_cast<const float4*>(x + ((size_t)(b * H + iy) * W + ix) * ldx + c);
-        }
-        float* t = &tile[ty + 16 * r][tx * 4];
-        t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+        T v[4] = {0, 0, 0, 0};
+        size_t row;
+        if (m < M && c < C && im2col_src(m, kh, kw, H, W, Ho, Wo, stride, pad, dil, row)) load4(x + row * ldx + c, v);
+        T* t = &tile[ty + 16 * r][tx * 4];
+        t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
     }
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int cl = ty + 16 * r, c = c0 + cl, m = m0 + tx * 4;
         if (c < C && m < Mp) {
-            const float v[4] = {tile[tx * 4][cl], tile[tx * 4 + 1][cl], tile[tx * 4 + 2][cl], tile[tx * 4 + 3][cl]};
-            const size_t ri = chan_major ? (size_t)c * taps + tap : (size_t)tap * C + c;
-            float* row = xt + ri * Mp;
-            if (split == 2) {    // plain bf16 rows: 4 pixels = 8 bytes
-                unsigned short* u = reinterpret_cast<unsigned short*>(xt) + ri * Mp + m;
-                *reinterpret_cast<uint2*>(u) = make_uint2((unsigned)vidc::bf16_rne(v[0]) | ((unsigned)vidc::bf16_rne(v[1]) << 16),
-                                                          (unsigned)vidc::bf16_rne(v[2]) | ((unsigned)vidc::bf16_rne(v[3]) << 16));
-            } else if (split) {  // 4 pixels of one 32-pixel K unit: their hi halves and their lo halves, 8 bytes each
+            const T v[4] = {tile[tx * 4][cl], tile[tx * 4 + 1][cl], tile[tx * 4 + 2][cl], tile[tx * 4 + 3][cl]};
+            const size_t ri = im2col_row(chan_major, c, tap, KH * KW, C);
+            if constexpr (kBf16) {
+                store4_bf16(xt + ri * Mp + m, v);
+            } else if (split == 2) {    // plain bf16 rows: 4 pixels = 8 bytes
+                store4_bf16(reinterpret_cast<unsigned short*>(xt) + ri * Mp + m, v);
+            } else if (split) {         // 4 pixels of one 32-pixel K unit: their hi halves and their lo halves, 8 bytes each
                 unsigned short h[4], l[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) vidc::split_bf16(v[k], h[k], l[k]);
-                unsigned short* u = reinterpret_cast<unsigned short*>(row + (m & ~31)) + (m & 31);
-                *reinterpret_cast<uint2*>(u) = make_uint2((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16));
-                *reinterpret_cast<uint2*>(u + 32) = make_uint2((unsigned)l[0] | ((unsigned)l[1] << 16), (unsigned)l[2] | ((unsigned)l[3] << 16));
+                unsigned short* u = reinterpret_cast<unsigned short*>(xt + ri * Mp + (m & ~31)) + (m & 31);
+                store4_bf16(u, h);
+                store4_bf16(u + 32, l);
             } else {
-                *reinterpret_cast<float4*>(row + m) = make_float4(v[0], v[1], v[2], v[3]);
+                store4(xt + ri * Mp + m, v);
             }
         }
-    }
-}
-// im2col_t64_kernel for the plain-bf16 mode from the bf16 operand copy of x (dense rows [B*H*W][C] of bf16, what the forward conv read)
-// instead of the fp32 tensor: half the bytes in, no rounding step (same bits: the copy holds the rounded values).  Rows of xt in channel-major
-// order (c * taps + tap), plain bf16, Mp % 64 == 0.
-__global__ void __launch_bounds__(256)
-im2col_t64_bf16_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ xt, int B, int H, int W, int C, int Ho, int Wo, int KH, int KW,
-                       int stride, int pad, int M, int Mp) {
-    __shared__ unsigned short tile[64][66];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int m0 = blockIdx.x * 64, c0 = blockIdx.y * 64, tap = blockIdx.z;
-    const int kh = tap / KW, kw = tap - kh * KW, taps = KH * KW;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int m = m0 + ty + 16 * r, c = c0 + tx * 4;
-        uint2 v = make_uint2(0u, 0u);
-        if (m < M && c < C) {
-            const int ox = m % Wo, q = m / Wo, oy = q % Ho, b = q / Ho;
-            const int iy = oy * stride - pad + kh, ix = ox * stride - pad + kw;
-            if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = *reinterpret_cast<const uint2*>(x + ((size_t)(b * H + iy) * W + ix) * C + c);
-        }
-        unsigned short* t = &tile[ty + 16 * r][tx * 4];
-        t[0] = (unsigned short)v.x; t[1] = (unsigned short)(v.x >> 16); t[2] = (unsigned short)v.y; t[3] = (unsigned short)(v.y >> 16);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int cl = ty + 16 * r, c = c0 + cl, m = m0 + tx * 4;
-        if (c < C && m < Mp)
-            *reinterpret_cast<uint2*>(xt + ((size_t)c * taps + tap) * Mp + m) =
-                make_uint2((unsigned)tile[tx * 4][cl] | ((unsigned)tile[tx * 4 + 1][cl] << 16), (unsigned)tile[tx * 4 + 2][cl] | ((unsigned)tile[tx * 4 + 3][cl] << 16));
     }
 }
 // Dense bf16 rows x[M][C] -> their transpose xt[C][Mp] (zeros for m >= M; Mp % 64 == 0): the right operand of the weight-gradient GEMM of a
 // 1x1 / stride-1 conv in the plain-bf16 mode, from the bf16 operand copy its forward already read (half the bytes of the fp32 source, no
 // rounding step: the bits are those vidc_im2col_transposed(split = 2) produces from the fp32 tensor, which rounds the same values).
-// 64 x 64 tile through LDS, 16-byte reads along C, 32-byte runs along m out.
+// 64 x 64 tile through LDS, 16-byte reads along C, 32-byte runs along m out.  It is the KH = KW = 1 case of im2col_t64_kernel<unsigned short>
+// and stays a kernel of its own for those widths: two loads and two stores of 16 bytes per thread where the im2col form, which must be able
+// to stop at any multiple of four channels, issues four and four of 8 bytes.
 __global__ void __launch_bounds__(256)
 transpose_bf16_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ xt, int M, int C, int Mp) {
     __shared__ unsigned short tile[64][66];
@@ -1425,9 +1344,9 @@ extern "C" int vidc_maxpool3x3s2_backward(const float* x, const float* dy, float
                       (long long)B * Ho * Wo * lddy < (1ll << 31) &&
                       ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0;
     if (wide)
-        hipLaunchKernelGGL(maxpool_bwd4_kernel, dim3(blocks((long long)B * H * W * (C / 4))), dim3(TT), 0, vidc::as_stream(stream), x, dy, dx, B, H, W, C, ldx, lddy, lddx);
+        hipLaunchKernelGGL(maxpool_bwd_kernel<4>, dim3(blocks((long long)B * H * W * (C / 4))), dim3(TT), 0, vidc::as_stream(stream), x, dy, dx, B, H, W, C, ldx, lddy, lddx);
     else
-        hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(blocks((long long)B * H * W * C)), dim3(TT), 0, vidc::as_stream(stream), x, dy, dx, B, H, W, C, ldx, lddy, lddx);
+        hipLaunchKernelGGL(maxpool_bwd_kernel<1>, dim3(blocks((long long)B * H * W * C)), dim3(TT), 0, vidc::as_stream(stream), x, dy, dx, B, H, W, C, ldx, lddy, lddx);
     VIDC_CHECK_LAUNCH("maxpool_bwd_kernel");
     return VIDC_OK;
 }
@@ -1439,9 +1358,9 @@ extern "C" int vidc_upsample_bilinear_ac_backward(const float* dy, float* dx, in
     const bool wide = C % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && (long long)B * H * W * lddy < (1ll << 31) && (long long)B * h * w * lddx < (1ll << 31) &&
                       ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0;
     if (wide)
-        hipLaunchKernelGGL(upsample_bwd4_kernel, dim3(blocks((long long)B * h * w * (C / 4))), dim3(TT), 0, vidc::as_stream(stream), dy, dx, B, h, w, C, lddy, lddx, H, W);
+        hipLaunchKernelGGL(upsample_bwd_kernel<4>, dim3(blocks((long long)B * h * w * (C / 4))), dim3(TT), 0, vidc::as_stream(stream), dy, dx, B, h, w, C, lddy, lddx, H, W);
     else
-        hipLaunchKernelGGL(upsample_bwd_kernel, dim3(blocks((long long)B * h * w * C)), dim3(TT), 0, vidc::as_stream(stream), dy, dx, B, h, w, C, lddy, lddx, H, W);
+        hipLaunchKernelGGL(upsample_bwd_kernel<1>, dim3(blocks((long long)B * h * w * C)), dim3(TT), 0, vidc::as_stream(stream), dy, dx, B, h, w, C, lddy, lddx, H, W);
     VIDC_CHECK_LAUNCH("upsample_bwd_kernel");
     return VIDC_OK;
 }
@@ -1529,9 +1448,10 @@ extern "C" int vidc_adam_step(float* p, const float* g, float* m, float* v, long
 __global__ void __launch_bounds__(TT) grad_narrow_kernel(const float* __restrict__ x, unsigned short* __restrict__ y, long long n) {
     const long long i = ((long long)blockIdx.x * TT + threadIdx.x) * 8;
     if (i + 8 <= n) {
-        const float4 a = *reinterpret_cast<const float4*>(x + i), b = *reinterpret_cast<const float4*>(x + i + 4);
-        *reinterpret_cast<uint4*>(y + i) = make_uint4(vidc::bf16_rne(a.x) | ((unsigned)vidc::bf16_rne(a.y) << 16), vidc::bf16_rne(a.z) | ((unsigned)vidc::bf16_rne(a.w) << 16),
-                                                      vidc::bf16_rne(b.x) | ((unsigned)vidc::bf16_rne(b.y) << 16), vidc::bf16_rne(b.z) | ((unsigned)vidc::bf16_rne(b.w) << 16));
+        float v[8];
+        vidc::load4(x + i, v);
+        vidc::load4(x + i + 4, v + 4);
+        vidc::store8_bf16(y + i, v);
     } else {
         for (long long j = i; j < n; ++j) y[j] = vidc::bf16_rne(x[j]);
     }
@@ -1684,7 +1604,7 @@ int im2col_transposed_launch(const char* what, const float* x, float* xt, int B,
                  VIDC_ERR_SHAPE, "%s: tap coordinates out of range", what);
     const bool wide = C % 4 == 0 && ldx % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(xt)) & 15) == 0;
     if (wide)
-        hipLaunchKernelGGL(im2col_t64_kernel, dim3((Mp + 63) / 64, (C + 63) / 64, KH * KW), dim3(256), 0, vidc::as_stream(stream), x, xt, B, H, W, C, ldx, Ho, Wo,
+        hipLaunchKernelGGL(im2col_t64_kernel<float>, dim3((Mp + 63) / 64, (C + 63) / 64, KH * KW), dim3(256), 0, vidc::as_stream(stream), x, xt, B, H, W, C, ldx, Ho, Wo,
                            KH, KW, stride, pad, dilation, (int)M, Mp, split);
     else
         hipLaunchKernelGGL(im2col_t_kernel, dim3(Mp / 32, (C + 31) / 32, KH * KW), dim3(256), 0, vidc::as_stream(stream), x, xt, B, H, W, C, ldx, Ho, Wo, KH, KW,
@@ -1712,9 +1632,11 @@ extern "C" int vidc_im2col_transposed_bf16(const void* x_bf16, void* xt_bf16, in
                      (long long)B * H * W * C < (1ll << 31) && (long long)KH * KW <= 65535 &&
                      ((reinterpret_cast<uintptr_t>(x_bf16) | reinterpret_cast<uintptr_t>(xt_bf16)) & 7) == 0,
                  VIDC_ERR_SHAPE, "vidc_im2col_transposed_bf16: bad shape (C a multiple of 4, Mp = M rounded up to a multiple of 64, 8-byte aligned tensors)");
-    hipLaunchKernelGGL(im2col_t64_bf16_kernel, dim3(Mp / 64, (C + 63) / 64, KH * KW), dim3(256), 0, vidc::as_stream(stream),
-                       reinterpret_cast<const unsigned short*>(x_bf16), reinterpret_cast<unsigned short*>(xt_bf16), B, H, W, C, Ho, Wo, KH, KW, stride, pad, (int)M, Mp);
-    VIDC_CHECK_LAUNCH("im2col_t64_bf16_kernel");
+    // (dense rows, no dilation; 4 | 2: channel-major rows of plain bf16)
+    hipLaunchKernelGGL(im2col_t64_kernel<unsigned short>, dim3(Mp / 64, (C + 63) / 64, KH * KW), dim3(256), 0, vidc::as_stream(stream),
+                       reinterpret_cast<const unsigned short*>(x_bf16), reinterpret_cast<unsigned short*>(xt_bf16), B, H, W, C, C, Ho, Wo, KH, KW, stride, pad, 1,
+                       (int)M, Mp, 4 | 2);
+    VIDC_CHECK_LAUNCH("im2col_t64_kernel<unsigned short>");
     return VIDC_OK;
 }
 
