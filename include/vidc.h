@@ -480,7 +480,8 @@ enum vidc_png_format {
  *   raw   = per row: the filter byte 00, then the row's samples
  *   block = BFINAL (01 on the last, else 00), LEN(le16), ~LEN(le16), LEN raw bytes; every block but the last has LEN = 65535
  * i.e. 63 + 5 * ceil(raw / 65535) + raw bytes with raw = H * (1 + W * bytes per pixel); raw byte i sits at 48 + 5 * (i / 65535) + i.
- * No entropy coder: a 240x320 depth map is 153 918 bytes where Pillow's compressed file has about 76 KB. */
+ * These files carry no filter and no entropy coder (a 240x320 depth map is 153 918 bytes); vidc_png_encode_deflate below writes the same
+ * images with a PNG filter per row and one Huffman-coded deflate block, 2 to 5 times smaller. */
 size_t vidc_png_file_bytes(int H, int W, int format);           /* host only; 0 for H, W <= 0, an unknown format or an IDAT chunk beyond 2^31 - 1 bytes */
 size_t vidc_png_scratch_bytes(int B, int H, int W, int format); /* host only; 0 for bad arguments */
 /* Image i of src -> the file at files + i * file_stride (device memory), in two launches whatever B, with no host synchronisation and
@@ -488,6 +489,54 @@ size_t vidc_png_scratch_bytes(int B, int H, int W, int format); /* host only; 0 
  * end of a file and file_stride are not written.  An image's bytes do not depend on B or file_stride.  VIDC_ERR_NULL for a null
  * pointer; VIDC_ERR_SHAPE for B, H, W <= 0, B > 65535, an unknown format, a short or misaligned stride, an image beyond one IDAT chunk. */
 int vidc_png_encode(const void* src, int B, int H, int W, int format, uint8_t* files, size_t file_stride, void* scratch, vidc_stream_t stream);
+
+/* The same images as COMPRESSED files: one of the five PNG filters per row, then ONE Huffman-only dynamic deflate block.  There is no LZ77
+ * matcher and there are no run-length symbols (neither in the data nor in the header): every filtered byte is one literal. */
+enum vidc_png_filter {
+    VIDC_PNG_FILTER_NONE = 0, VIDC_PNG_FILTER_SUB = 1, VIDC_PNG_FILTER_UP = 2, VIDC_PNG_FILTER_AVERAGE = 3, VIDC_PNG_FILTER_PAETH = 4, /* every row */
+    VIDC_PNG_FILTER_ADAPTIVE = 5 /* per row the filter with the smallest sum of |byte as int8| over the row's filtered bytes (the filter byte
+                                    not counted); ties go to the lowest id */
+};
+/* The file (its size depends on the image):
+ *   signature, IHDR and IEND as above; ONE IDAT chunk, whose length field is computed on the device
+ *   zlib  = 78 01, ONE deflate block, adler32(filtered)(be32)
+ *   filtered = per row: the filter byte f (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth), then the row filtered as the PNG specification defines
+ *           f: with x the raw byte, a the raw byte bpp to its left, b the raw byte above, c the raw byte above a (0 where the image ends;
+ *           the row above the first row is zeros; bpp = 2 for DEPTH16, 3 for NORMAL8 / RGB8, 1 for GRAY8), all mod 256:
+ *           None x; Sub x - a; Up x - b; Average x - floor((a + b) / 2); Paeth x - (the one of a, b, c nearest to a + b - c, ties in that
+ *           order).  Filters read RAW neighbours, so no output byte depends on another output byte.
+ *   block = bits in deflate's order (the first bit is bit 0 of the first byte; numbers least significant bit first, Huffman codes most
+ *           significant bit first):
+ *             bit 0        BFINAL = 1
+ *             bits 1-2     BTYPE  = 10 (dynamic Huffman; the number 2)
+ *             bits 3-7     HLIT   = 0   (257 literal / length codes)
+ *             bits 8-12    HDIST  = 0   (one distance code)
+ *             bits 13-16   HCLEN  = 15  (19 code-length-code lengths)
+ *             bits 17-73   the 19 lengths of 3 bits in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15: 0 0 0, then 4 sixteen times,
+ *                          so the code of a length L in 0..15 is L itself in 4 bits, and 16 / 17 / 18 never occur
+ *             bits 74-1105 258 lengths of 4 bits: literals 0..255, end-of-block, and the one distance code (length 0)
+ *             bit 1106 on  every filtered byte as its literal's code (canonical codes, RFC 1951 3.2.2), the end-of-block code, then zero
+ *                          bits to the byte boundary
+ *           i.e. the first symbol always starts at bit 1106 = 3 + 14 + 57 + 1032, bit 2 of file byte 181.
+ *   lengths: at most 15 bits, a complete code over the used symbols (the bytes that occur, and end-of-block with count 1).  When the Huffman
+ *           code of these counts (among equal weights the shallower subtree merges first) is at most 15 deep, its lengths: the symbol
+ *           bits are the Huffman optimum.  When it is deeper, the depths are cut to 15 and the counts per length repaired as zlib's
+ *           gen_bitlen does (one leaf a level down, one cut leaf beside it, until the code is complete); should that cost more than a
+ *           flat code of k = ceil(log2(used symbols)) bits, the balanced code instead: the 2^k - used most frequent symbols k - 1 bits,
+ *           the others k.  The longest lengths go to the rarest symbols, ordered by (count, symbol).
+ * i.e. 57 + 2 + ceil((1106 + symbol bits) / 8) + 4 bytes.  A flat 9-bit code bounds every image, so no file is larger than
+ *   vidc_png_deflate_max_file_bytes = 57 + 2 + ceil((1106 + 9 * (raw + 1)) / 8) + 4,   raw = H * (1 + W * bpp):
+ * a noise image grows by up to 12.6 % over the stored file, a 240x320 prediction shrinks to a fifth (normals) or to 40-50 % (depth). */
+size_t vidc_png_deflate_max_file_bytes(int H, int W, int format);          /* host only; 0 as vidc_png_file_bytes */
+size_t vidc_png_deflate_scratch_bytes(int B, int H, int W, int format);    /* host only; 0 for bad arguments */
+/* Image i of src -> the file at files + i * file_stride and its size at file_bytes[i] (both device memory), in four launches whatever B,
+ * with no host synchronisation and no allocation.  file_stride >= vidc_png_deflate_max_file_bytes() and a multiple of 16, files and scratch
+ * 16-byte aligned; nothing at or beyond max_file_bytes rounded up to 16 of a row is written (what lies between the end of a file and
+ * that offset is unspecified).  A file and its size depend on the image and the filter mode alone: not on B, file_stride or what the scratch
+ * held.  VIDC_ERR_NULL for a null pointer; VIDC_ERR_SHAPE for B, H, W <= 0, B > 65535, an unknown format, a filter outside 0..5, a short
+ * or misaligned stride, an image whose largest file is beyond one IDAT chunk -- all refused before any launch. */
+int vidc_png_encode_deflate(const void* src, int B, int H, int W, int format, int filter, uint8_t* files, size_t file_stride,
+                            uint32_t* file_bytes, void* scratch, vidc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * plane-mask head: the two native kernels it reaches   (plane_mask_detection/maskrcnn_benchmark/csrc)

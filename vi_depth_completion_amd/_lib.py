@@ -27,6 +27,7 @@ PREC_FP32, PREC_BF16X3, PREC_BF16, PREC_MXFP8 = 0, 1, 2, 3
 TILE_KIND_AUTO, TILE_KIND_MFMA, TILE_KIND_STREAM, TILE_KIND_WINOGRAD = range(4)      # vidc_conv_tile_kind
 SPLITK_COUNTERS = 16384            # VIDC_SPLITK_COUNTERS: ticket counters at the head of a split-K workspace
 PNG_DEPTH16_F32, PNG_NORMAL8_F32, PNG_RGB8_F32, PNG_GRAY8_U8 = range(4)      # vidc_png_format
+PNG_FILTER_NONE, PNG_FILTER_SUB, PNG_FILTER_UP, PNG_FILTER_AVERAGE, PNG_FILTER_PAETH, PNG_FILTER_ADAPTIVE = range(6)      # vidc_png_filter
 
 _f32p = C.POINTER(C.c_float)
 
@@ -244,6 +245,9 @@ SIGNATURES = {
     "vidc_png_file_bytes": (C.c_size_t, [_i, _i, _i]),
     "vidc_png_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "vidc_png_encode": (C.c_int, [_vp, _i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp]),
+    "vidc_png_deflate_max_file_bytes": (C.c_size_t, [_i, _i, _i]),
+    "vidc_png_deflate_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "vidc_png_encode_deflate": (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp]),
     "vidc_nms_scratch_bytes": (C.c_size_t, [_i]),
     "vidc_nms": (C.c_int, [_vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
     "vidc_nms_segmented_scratch_bytes": (C.c_size_t, [_i, _i]),
