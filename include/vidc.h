@@ -335,19 +335,25 @@ int vidc_head_conv1x1_upsample(const float* x, const float* w, const float* bias
 /* A plane "slot" = one plane id of one image of the batch: int32[4] = {image index b, plane id, offset into hyp_pix,
  * n_hyp}.  Every stage below is ONE launch over all slots (the reference loops in Python, main.py:147-182,279-283).
  * Per-slot result record (VIDC_PLANE_RECORD floats):
- *   [0..2] n_bar  [3] plane offset d  [4] n_inliers (normal RANSAC)  [5] mean |angle| in degrees  [6] accepted (<= 20 deg)
- *   [7] n_pts (sparse depths on the inliers)  [8] mean_depth  [9] n_offset_inliers
- *   [10] 1 = depth written, 0 = plane failed the validity tests, -1 = n_pts > VIDC_MAX_HYP and no host draw was supplied
- *        for this slot (main.py:75-78; see vidc_plane_offset_dense)  [11] n projected pixels  [12] best hypothesis row */
+ *   [0..2] n_bar  [3] plane offset d  [4] n_inliers (normal RANSAC)  [5] mean |angle| in degrees
+ *   [6] 1 = accepted: at least one inlier and mean |angle| <= 20 deg; 0 otherwise, and 0 for a slot flagged in [10]
+ *   [7] n_pts (sparse depths on the inliers; 0 for a slot that is not accepted)  [8] mean_depth  [9] n_offset_inliers
+ *   [10] 1 = the plane passed the validity tests and its depths were written (also when no pixel has |n.homo| > 1e-3: nothing to
+ *        write, [11] = 0), 0 = it failed them -- or never reached them: [6] = 0 or [9] = 0 leave [10] = [11] = 0 --, -1 = n_pts >
+ *        VIDC_MAX_HYP and no host draw was supplied for this slot (main.py:75-78; see vidc_plane_offset_dense; then [6] = [9] = 0,
+ *        [7] = n_pts)
+ *   [11] n projected pixels (mask & |n.homo| > 1e-3; written by vidc_plane_project_depth together with [10])
+ *   [12] best hypothesis row (the first of the rows with the largest count)  [13..15] 0 */
 
 /* Bytes of device scratch the three plane stages below share for one batch (chunk partial sums, validity statistics,
  * the per-image row-major list of sparse-depth pixels). */
 size_t vidc_plane_scratch_bytes(int n_slots, int B, int HW);
 
 /* mean_normal_ranasc (main.py:38-62) + the inlier write-back of main.py:157.
- * normals: NCHW [B][3][HW] unit normals; ids: [B][HW] uint8 plane-id maps; hyp_pix: flat pixel indices of the
- * hypothesis normals of every slot, concatenated (the host draws np.random.permutation exactly like main.py:43);
- * inlier_mask: [n_slots][HW] uint8 out; counts: [n_slots][VIDC_MAX_HYP] int32 out (inliers per hypothesis);
+ * normals: NCHW [B][3][HW] unit normals; ids: [B][HW] uint8 plane-id maps; hyp_pix: flat pixel indices (inside the image) of the
+ * hypothesis normals of every slot, concatenated (the host draws np.random.permutation exactly like main.py:43); 1 <= n_hyp <=
+ * VIDC_MAX_HYP; inlier_mask: [n_slots][HW] uint8 out (0 / 1, every byte written); counts: [n_slots][VIDC_MAX_HYP] int32 out (inliers
+ * per hypothesis, zero behind n_hyp; counts[slot][record[12]] == record[4] == the number of ones in the slot's mask row);
  * the mean normal / mean angle partial sums stay in `scratch` for vidc_plane_offset. */
 int vidc_plane_ransac_normal(const float* normals, const uint8_t* ids, const int32_t* slots, int n_slots,
                              const int32_t* hyp_pix, int HW, uint8_t* inlier_mask, int32_t* counts, void* scratch,

@@ -13,6 +13,8 @@ constexpr int CH = 256;                   // pixels per workgroup chunk
 constexpr float ANGLE_THR = 20.0f;        // MEAN_NORMAL_ANGLE_DIFF_THR / angle_threshold_degrees (main.py:25,38)
 constexpr float RAD2DEG = (float)(180.0 / 3.14159265358979323846);
 constexpr float COS_THR = 0.93969262078590838f;   // cos(20 deg)
+constexpr float COS_SURE = COS_THR + 1e-4f;       // above: closer than 20 deg whatever acosf rounds to
+constexpr float COS_NEVER = COS_THR - 1e-4f;      // below: farther
 constexpr float DIST_THR = 1.0e-1f;       // plane_offset_ransac distance_threshold (main.py:68)
 constexpr float MAX_DEPTH_MULT = 10.f;    // main.py:22
 constexpr float MAX_DEPTH = 10.f;         // main.py:23
@@ -23,8 +25,8 @@ __device__ inline bool close_angle(float dot) {
     // torch: acos(clamp(dot,-1,1)) * (180/pi) < 20.  Far from the threshold the comparison is decided on the cosine;
     // only borderline values pay for the acosf.
     dot = fminf(fmaxf(dot, -1.0f), 1.0f);
-    if (dot > COS_THR + 1e-4f) return true;
-    if (dot < COS_THR - 1e-4f) return false;
+    if (dot > COS_SURE) return true;
+    if (dot < COS_NEVER) return false;
     return acosf(dot) * RAD2DEG < ANGLE_THR;
 }
 
@@ -95,13 +97,16 @@ ransac_count_kernel(const float* __restrict__ normals, const uint8_t* __restrict
 #pragma unroll
         for (int j = 0; j < 4; ++j) {               // same decision as close_angle(): clamp, cosine far from the threshold, acosf near it
             t[j] = fminf(fmaxf(t[j], -1.0f), 1.0f);
-            c += t[j] > COS_THR + 1e-4f ? 1 : 0;
-            edge |= fabsf(t[j] - COS_THR) <= 1e-4f;
+            c += t[j] > COS_SURE ? 1 : 0;
+            edge |= fabsf(t[j] - COS_THR) <= 1.5e-4f;
         }
+        // The slow path's band is wider than [COS_NEVER, COS_SURE] and defers to close_angle() for what the line above has not counted.
+        // (COS_SURE is COS_THR + 1e-4f ROUNDED UP: a band |t - COS_THR| <= 1e-4f, whose subtraction is exact, leaves the dot that equals
+        // COS_SURE to neither path, and the count then disagrees with the mask by that pixel.)
         if (__builtin_expect(edge, 0)) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (fabsf(t[j] - COS_THR) <= 1e-4f) c += acosf(t[j]) * RAD2DEG < ANGLE_THR ? 1 : 0;
+                if (fabsf(t[j] - COS_THR) <= 1.5e-4f && !(t[j] > COS_SURE)) c += close_angle(t[j]) ? 1 : 0;
         }
     }
     if (c) atomicAdd(&counts[blockIdx.y * VIDC_MAX_HYP + threadIdx.x], c);     // integer: order-independent

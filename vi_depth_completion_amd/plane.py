@@ -49,10 +49,13 @@ class _LegacyStream:
 
 def plane_groups(id_map):
     """Pixels of an id map grouped by plane: (classes > 0 ascending, like torch.unique; for each the flat pixel indices ascending, like
-    np.flatnonzero(flat == cls)).  One stable sort instead of one pass over the map per plane."""
+    np.flatnonzero(flat == cls)).  One stable sort instead of one pass over the map per plane.
+    ValueError for an id outside 0..255: the device compares uint8 ids, where a larger one would alias another plane or the background."""
     flat = np.asarray(id_map).reshape(-1)
     if flat.dtype != np.uint8:
         flat = flat.astype(np.int64)
+        if flat.size and (flat.min() < 0 or flat.max() > 255):
+            raise ValueError("plane ids must lie in 0..255 (the device holds them as uint8); got %d..%d" % (flat.min(), flat.max()))
     counts = np.bincount(flat)
     if counts.shape[0] == 1:
         return []                          # only background: the reference returns its inputs unchanged (main.py:135-137)
