@@ -707,6 +707,33 @@ int vidc_masked_l1_loss(const float* pred, const float* gt, long long n, int hw,
 /* torch.optim.Adam.step (defaults: no weight decay, no amsgrad) over a flat buffer; step = 1, 2, ... */
 int vidc_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
                    vidc_stream_t stream);
+/* ---- optimizer options of the trainers (csrc/optim.hip): weight decay, parameter groups, gradient clipping, accumulation ----
+ * Segment table = parameter groups over a flat buffer of n elements: seg_begin[nseg + 1] (int64, strictly increasing, seg_begin[0] = 0,
+ * seg_begin[nseg] = n; boundaries fall anywhere), seg_lr_scale[nseg], seg_weight_decay[nseg] (float), seg_flags[nseg] (int32, bit 0 =
+ * frozen), all in device memory; seg_begin_host is a host copy of seg_begin, on which the calls check that the table covers [0, n) in
+ * increasing order (VIDC_ERR_SHAPE otherwise; nothing is read back from the device).  nseg = 0 or null device pointers: one segment
+ * with scale 1, decay 0, not frozen.
+ *
+ * vidc_grad_sqnorm: the sum of g^2 over the non-frozen segments, every square and sum in fp64 (chunk partials reduced by one workgroup
+ * in a fixed order: no atomics, two runs give the same bits), then record[0] = grad_scale * sqrt(sum) -- the total norm
+ * torch.nn.utils.clip_grad_norm_ reports on the gradient grad_scale * g -- and record[1] = grad_scale * min(1, max_norm / (record[0] +
+ * 1e-6)), the one factor vidc_optimizer_step multiplies gradients by (max_norm <= 0: no clipping, record[1] = grad_scale).  A
+ * non-finite norm propagates as in torch.  g 16-byte aligned; record: 2 doubles; scratch: vidc_grad_sqnorm_scratch_bytes, 8-byte aligned. */
+size_t vidc_grad_sqnorm_scratch_bytes(long long n);
+int vidc_grad_sqnorm(const float* g, long long n, int nseg, const long long* seg_begin, const long long* seg_begin_host, const int* seg_flags,
+                     float grad_scale, float max_norm, double* record, void* scratch, vidc_stream_t stream);
+/* Gradient accumulation over the micro-steps of a window, fp32 adds: mode 0: acc = g (the window's first), 1: acc += g, 2: g += acc (the
+ * window's last: g then holds the sum).  Two distinct 16-byte aligned buffers. */
+int vidc_grad_accumulate(float* acc, float* g, long long n, int mode, vidc_stream_t stream);
+/* vidc_adam_step with options.  Per element: ge = g * s with s = (float)record[1] (a record of vidc_grad_sqnorm in device memory) or,
+ * record == NULL, grad_scale; lr_e = lr * seg_lr_scale, wd = seg_weight_decay; decoupled == 0: ge += wd * p (torch.optim.Adam's
+ * weight_decay); decoupled != 0: p *= 1 - lr_e * wd first (torch.optim.AdamW); then vidc_adam_step's update with lr_e.  Elements of
+ * frozen segments are neither read nor written (p, m, v).  With record == NULL, grad_scale == 1, no table: bit-identical to
+ * vidc_adam_step. */
+int vidc_optimizer_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
+                        int decoupled, const double* record, float grad_scale, int nseg, const long long* seg_begin,
+                        const long long* seg_begin_host, const float* seg_lr_scale, const float* seg_weight_decay, const int* seg_flags,
+                        vidc_stream_t stream);
 /* Process-wide switch of the training BatchNorms (default 0): with 1 the final reduction of the per-chunk channel sums runs inside the
  * prologue of the kernel that consumes it (apply / backward-apply: one launch less per BatchNorm pass on the small maps) instead of in a
  * launch of its own.  Both forms add the same numbers in the same order (bit-identical results); the folded form measured 6 % slower

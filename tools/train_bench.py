@@ -5,6 +5,8 @@ batch=64 on 8xMI355X"): one `_run_training_iteration` per step (network_run.py:2
     python tools/train_bench.py --batch 8 --steps 5                                  # one GPU's share of batch 64
     python tools/train_bench.py --network sn --batch 8                               # the surface-normal network's step (one rank only)
     python tools/train_bench.py --network both --batch 8                             # both in one process, one JSON line each, and their ratio
+    python tools/train_bench.py --weight-decay 0.01 --decoupled --max-grad-norm 1    # AdamW + clipping on the device (csrc/optim.hip)
+    python tools/train_bench.py --accumulate 8                                       # a "step" is a window: 7 backward_only + 1 step (batch 8 x 8)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... tools/train_bench.py --batch 8
 
 Frames shard over ranks (weak scaling), BatchNorm statistics per rank (like the reference's DataParallel replicas), gradients
@@ -28,6 +30,28 @@ PRECISIONS = {"fp32": "f32 (fp32 MFMA fwd / dgrad / wgrad)", "bf16x3": "f32+bf16
               "bf16": "bf16 operands, fp32 accumulate (MFMA fwd / dgrad / wgrad); fp32 master weights, BatchNorm, loss, Adam"}
 
 
+def optimizer_options(args):
+    """The trainers' optimizer keywords from the command line; all defaults: the plain Adam launch."""
+    return dict(weight_decay=args.weight_decay, decoupled_weight_decay=args.decoupled, max_grad_norm=args.max_grad_norm)
+
+
+def window(tr, k, *ins):
+    """One optimizer step over k micro-batches (the same data: a throughput tool): k - 1 `backward_only`, then the `step` that closes the window."""
+    for _ in range(k - 1):
+        tr.backward_only(*ins)
+    return tr.step(*ins)
+
+
+def optimizer_report(args, tr):
+    """What the JSON line says about the options (nothing when they are at their defaults; ms_per_step is then the time of a whole window)."""
+    if not (args.weight_decay or args.max_grad_norm is not None or args.accumulate > 1):
+        return {}
+    out = {"optimizer": dict(optimizer_options(args), accumulate=args.accumulate)}
+    if tr.last_grad_norm is not None:
+        out["last_grad_norm"] = float(tr.last_grad_norm)
+    return out
+
+
 def surface_normal_leg(args, dev):
     """The surface-normal step: seeded weights, synthetic gravity / normals / mask, timed like the depth leg (wall clock over `steps` steps
     after `warmup`); the loss kernel alone by HIP events over 20 calls."""
@@ -35,18 +59,19 @@ def surface_normal_leg(args, dev):
     cnn = SurfaceNormalPrediction().to(dev)
     cnn.load_state_dict(S.seeded_state_dict(cnn.state_dict(), 1234, device=dev))
     cnn.train()
-    tr = SurfaceNormalTrainer(cnn, 1e-4)
+    tr = SurfaceNormalTrainer(cnn, 1e-4, **optimizer_options(args))
+    K = args.accumulate
     B = args.batch
     b = S.synthetic_batch(B, 240, 320, 1234)
     image, gravity, aligned = b["image"].to(dev), b["gravity"].to(dev), b["aligned_direction"].to(dev)
     normal_gt = (S.normal01(1234, "sn.gt", (B, 3, 240, 320)).float() * 1.7).to(dev)
     mask = (S.uniform01(1234, "sn.mask", (B, 240, 320)) < 0.7).float().to(dev)
-    warm = [round(float(tr.step(image, gravity, aligned, normal_gt, mask)), 6) for _ in range(args.warmup)]
+    warm = [round(float(window(tr, K, image, gravity, aligned, normal_gt, mask)), 6) for _ in range(args.warmup)]
     losses = []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        losses.append(tr.step(image, gravity, aligned, normal_gt, mask))
+        losses.append(window(tr, K, image, gravity, aligned, normal_gt, mask))
     t_enq = time.perf_counter() - t0
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -62,10 +87,10 @@ def surface_normal_leg(args, dev):
     ev[1].record()
     torch.cuda.synchronize()
     ms = 1e3 * dt / args.steps
-    print(json.dumps({"metric": "surface-normal training frames/sec", "value": round(B * args.steps / dt, 2), "unit": "frames/s", "n_gpus": 1, "batch_per_gpu": B,
+    print(json.dumps({"metric": "surface-normal training frames/sec", "value": round(K * B * args.steps / dt, 2), "unit": "frames/s", "n_gpus": 1, "batch_per_gpu": B,
                       "ms_per_step": round(ms, 1), "host_enqueue_ms_per_step": round(1e3 * t_enq / args.steps, 1),
                       "loss_kernel_ms": round(ev[0].elapsed_time(ev[1]) / 20, 4), "dtype": PRECISIONS[os.environ.get("VIDC_TRAIN_PRECISION", "fp32")],
-                      "losses": warm + [round(float(x), 6) for x in losses], "angle_sum": round(float(tr.last_angle), 2),
+                      "losses": warm + [round(float(x), 6) for x in losses], "angle_sum": round(float(tr.last_angle), 2), **optimizer_report(args, tr),
                       "config": "SurfaceNormalPrediction training step (train-mode BN, normal L1 / N, Adam), 320x240, synthetic"}))
     return ms
 
@@ -79,6 +104,11 @@ def main():
                                                              "Adam's update does not depend on the gradient's scale, so the losses must follow the single-rank run")
     ap.add_argument("--network", choices=("dc", "sn", "both"), default="dc", help="dc: the depth-completion network (default); sn: the surface-normal\n"
                                                                                  "network; both: one after the other in this process")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="torch.optim.Adam's weight_decay (L2), or with --decoupled torch.optim.AdamW's")
+    ap.add_argument("--decoupled", action="store_true")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the gradient's global norm (torch.nn.utils.clip_grad_norm_); inf: measure only")
+    ap.add_argument("--accumulate", type=int, default=1, metavar="K", help="K micro-batches of --batch frames per optimizer step (K - 1 backward_only + 1 step);\n"
+                                                                          "ms_per_step is then the time of the whole window")
     args = ap.parse_args()
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
@@ -95,7 +125,8 @@ def main():
     cnn = ModifiedFPN().to(dev)
     cnn.load_state_dict(S.seeded_state_dict(cnn.state_dict(), 1234, device=dev))
     cnn.train()
-    tr = DepthCompletionTrainer(cnn, 1e-4)
+    tr = DepthCompletionTrainer(cnn, 1e-4, **optimizer_options(args))
+    K = args.accumulate
     B = args.batch
     b = S.synthetic_batch(B, 240, 320, 1234, frame0=0 if args.same_data else rank * B)
     image = b["image"].to(dev)
@@ -104,7 +135,7 @@ def main():
     gt = S.synthetic_ground_truth_depth(b["image"], 1234).to(dev)
     losses = []
     for _ in range(args.warmup):
-        losses.append(tr.step(image, normal, depth_in, gt))
+        losses.append(window(tr, K, image, normal, depth_in, gt))
     warm = [round(float(x), 6) for x in losses]
     losses = []
     torch.cuda.synchronize()
@@ -112,16 +143,16 @@ def main():
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        losses.append(tr.step(image, normal, depth_in, gt))
+        losses.append(window(tr, K, image, normal, depth_in, gt))
     t_enq = time.perf_counter() - t0          # host time to enqueue the steps (the GPU runs behind it when the step is GPU-bound)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
     if rank == 0:
-        print(json.dumps({"metric": "training frames/sec", "value": round(world * B * args.steps / dt, 2), "unit": "frames/s", "n_gpus": world,
+        print(json.dumps({"metric": "training frames/sec", "value": round(world * K * B * args.steps / dt, 2), "unit": "frames/s", "n_gpus": world,
                           "batch_per_gpu": B, "ms_per_step": round(1e3 * dt / args.steps, 1), "host_enqueue_ms_per_step": round(1e3 * t_enq / args.steps, 1), "dtype": PRECISIONS[os.environ.get("VIDC_TRAIN_PRECISION", "fp32")],
-                          "losses": warm + [round(float(x), 6) for x in losses],
+                          "losses": warm + [round(float(x), 6) for x in losses], **optimizer_report(args, tr),
                           "config": "BASELINE configs[4]: ModifiedFPN training step (train-mode BN, masked L1 / (H*W), Adam), 320x240, synthetic"}))
         if sn_ms is not None:
             print(json.dumps({"metric": "surface-normal step / depth step", "value": round(sn_ms / (1e3 * dt / args.steps), 3), "sn_ms_per_step": round(sn_ms, 1),

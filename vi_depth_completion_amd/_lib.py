@@ -189,6 +189,10 @@ SIGNATURES = {
     "vidc_head_backward_multi": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vidc_clock_stamp": (C.c_int, [_vp, _vp]),
     "vidc_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_longlong, _f, _f, _f, _f, _i, _vp]),
+    "vidc_grad_sqnorm_scratch_bytes": (C.c_size_t, [C.c_longlong]),
+    "vidc_grad_sqnorm": (C.c_int, [_vp, C.c_longlong, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp]),
+    "vidc_grad_accumulate": (C.c_int, [_vp, _vp, C.c_longlong, _i, _vp]),
+    "vidc_optimizer_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_longlong, _f, _f, _f, _f, _i, _i, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vidc_train_bn_fold": (C.c_int, [_i]),
     "vidc_grad_narrow_bf16": (C.c_int, [_vp, _vp, C.c_longlong, _vp]),
     "vidc_grad_widen_bf16": (C.c_int, [_vp, _vp, C.c_longlong, _vp]),

@@ -10,6 +10,7 @@
 // reductions accumulate in fp64 with a fixed two-level order (bit-reproducible), like torch's CPU kernels accumulate float in double.
 #include "common.h"
 #include "train_rows.h"
+#include "optim.h"
 #include <cstdint>
 #include <type_traits>
 
@@ -18,6 +19,7 @@ namespace {
 using vidc::TT;
 using vidc::blocks;
 using vidc::block_tree;
+using vidc::adam_one;
 using vidc::row_quad, vidc::load4, vidc::store4, vidc::store4_bf16, vidc::store8_bf16, vidc::relu_mask4;      // train_rows.h
 
 // What the per-channel sums become, applied by the thread that finishes a channel in chan_final_kernel (no extra launch).
@@ -664,18 +666,7 @@ l1_loss_kernel(const float* __restrict__ pred, const float* __restrict__ gt, lon
 }
 
 // ---- Adam (torch.optim.Adam defaults: no weight decay, no amsgrad) on a flat parameter buffer -------------------------------------
-// One element; every product / sum / quotient rounds once (contraction off: HIP's __fmul_rn / __fadd_rn are plain operators that hipcc
-// may still fuse), so an element's bits do not depend on whether the four-wide body or the scalar tail of the launch handled it (the flat
-// layout -- and with it an element's position -- differs between the grouped and the per-pyramid form of the step, and
-// tests/test_training.py compares their stepped parameters bit for bit).
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float b1, float b2, float c1, float c2, float eps, float step_size,
-                                         float bc2_sqrt) {
-#pragma clang fp contract(off)
-    m = m * b1 + g * c1;
-    v = v * b2 + (g * g) * c2;
-    const float denom = __fsqrt_rn(v) / bc2_sqrt + eps;
-    p = p - step_size * (m / denom);
-}
+// One element: adam_one (optim.h; csrc/optim.hip runs the same update with weight decay, clipping and parameter groups).
 // 28 bytes per parameter (p, g, m, v in; p, m, v out): one thread per four consecutive parameters (16-byte accesses), the n % 4 tail scalar
 __global__ void __launch_bounds__(TT)
 adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n, float lr, float b1, float b2,

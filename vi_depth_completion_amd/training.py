@@ -84,6 +84,37 @@ def _ld(t):
     return t.stride(2)
 
 
+def build_segment_table(named_sizes, param_groups=None, weight_decay=0.0):
+    """The segment table of csrc/optim.hip (include/vidc.h) for a flat buffer: `named_sizes` is [(name, numel)] in the buffer's order (the
+    trainer's `named`, whichever layout it chose -- in "grouped" the three pyramids interleave per name, so a pyramid's group becomes many
+    segments), `param_groups` a sequence of (match, options): match a name prefix or a callable name -> bool, the first match wins; options
+    may hold "lr_scale", "weight_decay", "frozen".  A parameter that matches nothing takes lr_scale 1, `weight_decay`, not frozen.
+    Adjacent tensors with equal settings share a segment.  Returns (begin, lr_scale, weight_decay, flags): begin has one entry more than the
+    others, begin[0] = 0, begin[-1] = the buffer's length; flags bit 0 = frozen.  A pure function (no device, no trainer)."""
+    groups = []
+    for match, options in (param_groups or ()):
+        unknown = set(options) - {"lr_scale", "weight_decay", "frozen"}
+        if unknown:
+            raise ValueError("param_groups: unknown option(s) %s (lr_scale, weight_decay, frozen)" % sorted(unknown))
+        if not (isinstance(match, str) or callable(match)):
+            raise ValueError("param_groups: a match is a name prefix or a callable name -> bool, got %r" % (match,))
+        groups.append((match, options))
+    begin, lr_scale, decay, flags = [0], [], [], []
+    o = 0
+    for name, numel in named_sizes:
+        options = next((opt for match, opt in groups if (name.startswith(match) if isinstance(match, str) else match(name))), {})
+        setting = (float(options.get("lr_scale", 1.0)), float(options.get("weight_decay", weight_decay)), int(bool(options.get("frozen", False))))
+        if numel <= 0:
+            continue
+        if lr_scale and setting == (lr_scale[-1], decay[-1], flags[-1]):
+            begin[-1] = o + numel
+        else:
+            lr_scale.append(setting[0]); decay.append(setting[1]); flags.append(setting[2])
+            begin.append(o + numel)
+        o += numel
+    return begin, lr_scale, decay, flags
+
+
 class GradientBuckets:
     """The flat gradient buffer cut into buckets for the cross-rank SUM (one collective per bucket, ~64 MB each: large enough that a
     ring all-reduce over xGMI runs at link speed, small enough to start before the whole backward has finished if overlapped).
@@ -165,15 +196,41 @@ class _TrainerBase:
     Build the trainer AFTER `torch.distributed.init_process_group` (and after the network is on its GPU): the flat layout of parameters, gradients, Adam
     moments and BatchNorm running statistics is chosen here (`self.layout`: "grouped" = the three pyramids interleaved per parameter name, the multi-rank
     default of the depth trainer; "per_pyramid" otherwise) and every launch of the step addresses tensors as base + offset into those buffers.  A later
-    `cnn.to()` / `.float()` / `.cuda()` that rebinds `p.data` is caught at the next `step()` (`_check_bindings`), not silently read through stale pointers."""
+    `cnn.to()` / `.float()` / `.cuda()` that rebinds `p.data` is caught at the next `step()` (`_check_bindings`), not silently read through stale pointers.
+
+    Optimizer options (csrc/optim.hip; all of it on the device, nothing is read back, the step stays asynchronous).  With every one at its
+    default and no accumulation window open the step issues exactly the launches it issued before these existed (`vidc_adam_step`).
+      weight_decay, decoupled_weight_decay   torch.optim.Adam(weight_decay=...)'s L2 term, or with decoupled_weight_decay torch.optim.AdamW's
+      max_grad_norm       torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) on the (rank-summed, window-summed) gradient of the
+                          non-frozen parameters.  The norm pass runs exactly when max_grad_norm is not None, and `last_grad_norm` (a 0-dim
+                          fp64 device tensor, the norm before clipping; None otherwise) is then refreshed by every optimizer step;
+                          float("inf") measures without clipping.  Across ranks every rank holds the summed gradient: no extra collective.
+      param_groups        a sequence of (match, options): a name prefix or a callable name -> bool, the first match wins; options
+                          "lr_scale", "weight_decay", "frozen" (`build_segment_table`).  A frozen parameter keeps its value and moments bit
+                          for bit and is left out of the norm; its gradient is still computed.
+      accumulate_mean     `backward_only(*ins)` runs a step's forward + backward and adds the gradient to a window (no all-reduce, no update);
+                          the next `step` closes the window: the update sees the SUM of the window's gradients -- what summing over ranks
+                          already means for the depth loss, which divides by the constant H*W: k micro-batches of B frames are one batch of
+                          k B -- or with accumulate_mean their mean.  The normal loss divides by N, the unmasked pixels of ITS batch, so
+                          each micro-batch's gradient is already an average and a window of k usually wants the mean (the sum is a k times
+                          larger step before Adam's normalisation has adapted, and k times the norm that max_grad_norm sees).
+    `lr` stays a plain attribute passed by value: a schedule is an assignment between steps."""
 
     pyramid_names = PYRAMIDS
 
-    def __init__(self, cnn, learning_rate=1e-4, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, cnn, learning_rate=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False, max_grad_norm=None,
+                 param_groups=None, accumulate_mean=False):
         if not torch.cuda.is_available():
             raise RuntimeError("%s needs a GPU: the HIP path has no CPU fallback" % type(self).__name__)
         self.cnn = cnn
         self.lr, self.betas, self.eps = float(learning_rate), betas, float(eps)
+        self.weight_decay, self.decoupled_weight_decay = float(weight_decay), bool(decoupled_weight_decay)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.param_groups = list(param_groups or ())
+        self.accumulate_mean = bool(accumulate_mean)
+        if self.weight_decay < 0 or (self.max_grad_norm is not None and not self.max_grad_norm > 0):
+            raise ValueError("weight_decay must be >= 0 and max_grad_norm > 0 (float('inf'): measure the norm, never clip)")
+        build_segment_table([], self.param_groups)      # (refuses malformed groups before any parameter is rebound)
         self.named = [(k, p) for k, p in cnn.named_parameters()]
         # Grouped pyramids (round 5, VIDC_TRAIN_GROUPED=0 switches back to one launch chain per pyramid): the same layer of the three
         # pyramids runs as ONE launch with three groups -- forward conv, data gradient, weight-gradient GEMM -- and ONE BatchNorm launch over
@@ -248,6 +305,21 @@ class _TrainerBase:
         dec = [offs[k] for k, _ in self.named if k.startswith("feature")]
         self._dec_off = min(dec) if dec and all(k.startswith("feature") for k, _ in self.named if offs[k] >= min(dec)) else n
         self.step_count = 0
+        # the optimizer options as the kernels take them: the segment table (None: one segment at the defaults), the norm record and the window
+        begin, lr_scale, decay, flags = build_segment_table([(k, p.numel()) for k, p in self.named], self.param_groups, self.weight_decay)
+        self._seg = None
+        if (lr_scale, decay, flags) != ([1.0], [0.0], [0]):
+            self._seg = (len(lr_scale), torch.tensor(begin, dtype=torch.int64, device=dev), (C.c_longlong * len(begin))(*begin),
+                         torch.tensor(lr_scale, dtype=torch.float32, device=dev), torch.tensor(decay, dtype=torch.float32, device=dev),
+                         torch.tensor(flags, dtype=torch.int32, device=dev))
+        self._any_frozen = any(flags)
+        self._options_on = self._seg is not None or self.max_grad_norm is not None
+        self._norm_record = self._norm_scratch = self.last_grad_norm = None
+        if self.max_grad_norm is not None:
+            self._norm_record = torch.zeros(2, dtype=torch.float64, device=dev)       # vidc_grad_sqnorm's [total norm, gradient factor]
+            self._norm_scratch = torch.empty(L.lib().vidc_grad_sqnorm_scratch_bytes(n), dtype=torch.uint8, device=dev)
+            self.last_grad_norm = self._norm_record[0]
+        self.flat_acc, self._window = None, 0      # gradient sum of the open accumulation window and its number of micro-steps (0: closed)
         self._ones, self._zeros, self._packed, self._scratch, self._nbt = {}, {}, {}, {}, []
         self._gemm_ws = {}          # split-K workspace per stream lane (lane 0 = the caller's stream)
         self._cur = 0               # stream lane the ops being recorded / replayed run on (0 = main, 1..3 = the three pyramids, 1..4 = the decoder branches)
@@ -454,10 +526,18 @@ class _TrainerBase:
                                    "build a new trainer after moving or casting the network" % (type(self).__name__, self.layout))
 
     def flat_state(self):
-        """Optimizer state for a checkpoint: the flat Adam moments with the layout they belong to and the parameter order that defines the offsets."""
-        return {"layout": self.layout, "order": [k for k, _ in self.named], "m": self.m, "v": self.v, "step_count": self.step_count}
+        """Optimizer state for a checkpoint: the flat Adam moments with the layout they belong to and the parameter order that defines the offsets,
+        and (a record for whoever reads the checkpoint; a trainer's options are its constructor's) the optimizer options they were made under."""
+        if self._window:
+            raise RuntimeError("flat_state(): an accumulation window of %d micro-step(s) is open; close it with step() first (its gradient sum is not "
+                               "part of the state)" % self._window)
+        begin, lr_scale, decay, flags = build_segment_table([(k, p.numel()) for k, p in self.named], self.param_groups, self.weight_decay)
+        options = {"weight_decay": self.weight_decay, "decoupled_weight_decay": self.decoupled_weight_decay, "max_grad_norm": self.max_grad_norm,
+                   "accumulate_mean": self.accumulate_mean, "segments": {"begin": begin, "lr_scale": lr_scale, "weight_decay": decay, "flags": flags}}
+        return {"layout": self.layout, "order": [k for k, _ in self.named], "m": self.m, "v": self.v, "step_count": self.step_count, "options": options}
 
     def load_flat_state(self, st):
+        """(`st["options"]`, absent from states saved before the options existed, is not applied: the options are this trainer's constructor's.)"""
         if st["layout"] != self.layout or list(st["order"]) != [k for k, _ in self.named]:
             raise RuntimeError("optimizer state of layout %r / another parameter order cannot be loaded into a trainer of layout %r (build the trainer under the "
                                "same VIDC_TRAIN_GROUPED setting and process-group state)" % (st["layout"], self.layout))
@@ -958,12 +1038,32 @@ class _TrainerBase:
     @torch.no_grad()
     def optimizer_step(self, reduced=False):
         """torch.optim.Adam.step over the flat buffers; gradients are summed over ranks first (frame-sharded batch) unless `step` has
-        done that already, overlapped with the backward."""
+        done that already, overlapped with the backward.
+
+        With an optimizer option set or an accumulation window open (class docstring) the order is: g += the window's sum, ONE all-reduce of
+        that sum, the norm pass (when max_grad_norm is not None), then `vidc_optimizer_step`; otherwise `vidc_adam_step`, as ever."""
+        lib, n, st = L.lib(), self.flat_p.numel(), L.current_stream()
+        window = self._window
+        if window:
+            if reduced:
+                raise RuntimeError("optimizer_step(reduced=True) with an accumulation window open: the gradient must be all-reduced after the window's sum is added")
+            L.check(lib.vidc_grad_accumulate(L.ptr(self.flat_acc), L.ptr(self.flat_g), n, 2, st), "accumulate")
+            self._window = 0
         if not reduced:
             self.buckets.all_reduce(self.flat_g)
         self.step_count += 1
-        L.check(L.lib().vidc_adam_step(L.ptr(self.flat_p), L.ptr(self.flat_g), L.ptr(self.m), L.ptr(self.v), self.flat_p.numel(), self.lr, self.betas[0],
-                                       self.betas[1], self.eps, self.step_count, L.current_stream()), "adam")
+        if not self._options_on and not window:
+            L.check(lib.vidc_adam_step(L.ptr(self.flat_p), L.ptr(self.flat_g), L.ptr(self.m), L.ptr(self.v), n, self.lr, self.betas[0],
+                                       self.betas[1], self.eps, self.step_count, st), "adam")
+        else:
+            grad_scale = 1.0 / (window + 1) if self.accumulate_mean else 1.0
+            nseg, begin, begin_host, lr_scale, decay, flags = self._seg if self._seg is not None else (0, None, None, None, None, None)
+            if self._norm_record is not None:      # (the norm needs the table only for its frozen flags)
+                L.check(lib.vidc_grad_sqnorm(L.ptr(self.flat_g), n, nseg if self._any_frozen else 0, L.ptr(begin), begin_host, L.ptr(flags), grad_scale, self.max_grad_norm,
+                                             L.ptr(self._norm_record), L.ptr(self._norm_scratch), st), "grad norm")
+            L.check(lib.vidc_optimizer_step(L.ptr(self.flat_p), L.ptr(self.flat_g), L.ptr(self.m), L.ptr(self.v), n, self.lr, self.betas[0], self.betas[1],
+                                            self.eps, self.step_count, int(self.decoupled_weight_decay), L.ptr(self._norm_record), grad_scale, nseg, L.ptr(begin),
+                                            begin_host, L.ptr(lr_scale), L.ptr(decay), L.ptr(flags), st), "optimizer")
         self._packed_fresh = False      # so are the trainer's own packed copies (re-made by the next forward's repack())
         self.cnn._invalidate()          # the inference programs' packed / BN-folded copies are stale now
 
@@ -1039,14 +1139,32 @@ class _TrainerBase:
         hipGraphs (VIDC_TRAIN_GRAPH=0: always eager).  The all-reduce and the Adam launch (its bias correction takes the step number
         by value) stay outside the graphs.  Across ranks the depth trainer's backward is cut where the decoder's part ends
         (`cut_at_decoder`): the all-reduce of the decoder's gradients (59 % of the 1.24 GB) is started there and runs under the pyramids'
-        backward, the rest follows."""
-        multi = self.cut_at_decoder and self._distributed()
+        backward, the rest follows.  A step that closes an accumulation window (`backward_only`) takes the uncut path: the decoder's early
+        all-reduce would run before the window's sum exists, so `optimizer_step` adds the sum and all-reduces it once."""
+        multi = self.cut_at_decoder and self._distributed() and not self._window
         self._check_bindings()
         self._check_inputs(ins)
         loss, waits = self._graphed(ins, multi) if self.use_graph else self._eager_forward_backward(ins, multi)
         for w in waits:
             w()
         self.optimizer_step(reduced=multi)
+        self.last_loss = loss
+        self._after_step()
+        return loss
+
+    def backward_only(self, *ins):
+        """A micro-step of an accumulation window: the forward + backward of `step` on `ins` (captured / replayed like a step's; BatchNorm's
+        running statistics move as in any train-mode forward), then the gradient is added to the window's sum `flat_acc` (allocated on first
+        use; fp32 adds, outside the graphs like the Adam launch).  No all-reduce, no optimizer launch.  Returns the loss.  The next `step`
+        closes the window."""
+        self._check_bindings()
+        self._check_inputs(ins)
+        loss, _ = self._graphed(ins, False) if self.use_graph else self._eager_forward_backward(ins, False)
+        if self.flat_acc is None:
+            self.flat_acc = torch.empty_like(self.flat_g)
+        L.check(L.lib().vidc_grad_accumulate(L.ptr(self.flat_acc), L.ptr(self.flat_g), self.flat_g.numel(), 1 if self._window else 0, L.current_stream()),
+                "accumulate")
+        self._window += 1
         self.last_loss = loss
         self._after_step()
         return loss
@@ -1150,12 +1268,13 @@ class SurfaceNormalTrainer(_TrainerBase):
 
     pyramid_names = ("resnet_pyramids",)
 
-    def __init__(self, cnn, learning_rate=1e-4, betas=(0.9, 0.999), eps=1e-8, normalize_prediction=True):
+    def __init__(self, cnn, learning_rate=1e-4, betas=(0.9, 0.999), eps=1e-8, normalize_prediction=True, **optimizer_options):
+        """optimizer_options: weight_decay, decoupled_weight_decay, max_grad_norm, param_groups, accumulate_mean (`_TrainerBase`)."""
         if getattr(cnn, "use_mask", False):
             raise RuntimeError("SurfaceNormalTrainer: use_mask=True networks are not supported (surface_normal.py:150-162 multiplies the features by the "
                                "warp's validity mask; that multiply has no backward here yet)")
         self._refuse_ranks()
-        super().__init__(cnn, learning_rate, betas, eps)
+        super().__init__(cnn, learning_rate, betas, eps, **optimizer_options)
         self.normalize_prediction = bool(normalize_prediction)
         self._stats = torch.zeros(3, dtype=torch.float64, device=self.device)      # loss, N, angle sum of the step that ran last (written by the loss kernel)
         self.last_angle = self.last_count = None
