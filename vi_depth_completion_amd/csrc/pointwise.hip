@@ -341,6 +341,9 @@ int stem_launch(const float* x, const float* w_oihw, float* y, int B, int Cin, i
     unsigned short* ysp = reinterpret_cast<unsigned short*>(y_split);
     VIDC_REQUIRE((Cin == 1 || Cin == 3) && B > 0 && H > 2 && W > 2 && Cout > 0 && ldy >= Cout, VIDC_ERR_SHAPE,
                  "vidc_stem_conv3x3s2: unsupported shape (Cin=%d must be 1 or 3)", Cin);
+    // y_split is the image of the whole [.., ldy] tensor: the slice split_ch0 .. split_ch0 + Cout must lie inside its row
+    VIDC_REQUIRE(!y_split || (long long)split_ch0 + Cout <= ldy, VIDC_ERR_SHAPE,
+                 "vidc_stem_conv3x3s2: split slice %d + %d channels exceeds ldy = %d", split_ch0, Cout, ldy);
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     dim3 grid(vidc::cdiv(Wo, 64), Ho, B);
     hipStream_t st = vidc::as_stream(stream);
