@@ -442,6 +442,51 @@ int vidc_resize_nearest_u16_depth(const uint16_t* src, float* dst, int B, int H,
                                   const int32_t* ytab, float divisor, vidc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * training-batch pre-processing on the device   (ScanNetSmallFramesDataset dataset.py:95-247, NYUDataset dataset.py:381-438;
+ * SURVEY §8f-2).  Everything below is bit-identical to the host sequence it cites.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Byte image to the loaders' float tensor: src uint8 [B][H][W][C] (C = 1 or 3) -> dst float [B][C][H][W], every operation rounded
+ * once in fp32:
+ *   mode 0   x / 255                    ToTensor of the colour image (dataset.py:123), the orientation mask (dataset.py:129)
+ *   mode 1   -(x / 255) + 0.5           the ground-truth normal Z (dataset.py:130-131)
+ *   mode 2   1 - x / 127.5              predicted_normal of the ScanNet loader (dataset.py:219-221)
+ *   mode 3   -(1 - x / 127.5) + 0.5     predicted_normal of the NYU loader (dataset.py:394-395)
+ * 16-byte loads and stores when H*W is a multiple of 16 and both bases are 16-byte aligned; an element-wise form otherwise. */
+int vidc_u8_decode_chw(const uint8_t* src_hwc, float* dst_chw, int B, int H, int W, int C, int mode, vidc_stream_t stream);
+
+/* The sparse map of tracks given in pixel coordinates (dataset.py:204-212 ScanNet, dataset.py:410-419 NYU): tracks double
+ * [n_tracks][4] = (id, x, y, d), image b owns rows offsets[b] .. offsets[b+1] (int32 [B+1], on the device);
+ * col = (int)(x / divisor), row = (int)(y / divisor) in float64, truncated toward zero; a track whose quotient is not finite or
+ * beyond int32, or whose pixel lies outside the map, is skipped; depth[b][row][col] = (float)d, or gt_depth[b][row][col] with a
+ * non-NULL gt_depth (float [B][H][W]: read_depths_from_pointcloud=False).  A later track overwrites an earlier one: the highest
+ * track index wins a pixel (an atomic max in scratch, then one pass that writes EVERY pixel of depth float [B][H][W], 0 where no
+ * track landed).  scratch: vidc_rasterize_pixel_tracks_scratch_bytes bytes (one int32 per pixel).  tracks may be NULL with n_tracks 0. */
+size_t vidc_rasterize_pixel_tracks_scratch_bytes(int B, int H, int W);
+int vidc_rasterize_pixel_tracks(const double* tracks, const int32_t* offsets, int n_tracks, int B, double divisor, const float* gt_depth,
+                                float* depth, int H, int W, void* scratch, vidc_stream_t stream);
+
+/* torch.nonzero per image (dataset.py:196): v float [B][HW] -> count int32 [B], index int32 [B][HW] = the flat indices of the
+ * elements != 0.0f in ascending order (NaN counts, -0.0 does not); index[b][count[b] ..] is left untouched.  Two launches over
+ * chunks of VIDC_NONZERO_CHUNK elements: the chunk counts, then each chunk sums the counts in front of it and writes its indices
+ * (wave-wide ballots; no workgroup waits for another).  scratch: vidc_nonzero_compact_scratch_bytes bytes (one int32 per chunk). */
+#define VIDC_NONZERO_CHUNK 1024
+size_t vidc_nonzero_compact_scratch_bytes(int B, int HW);
+int vidc_nonzero_compact(const float* v, int B, int HW, int32_t* count, int32_t* index, void* scratch, vidc_stream_t stream);
+
+/* The random sparse sample of the ground truth (dataset.py:197-202).  Image b with nsel[b] < 0: out = depth (the clone of
+ * dataset.py:198).  Otherwise out is zero-filled and out[p] = depth[p] for p = index[b][perm[sel_off[b] + j]], j < nsel[b] (index
+ * from vidc_nonzero_compact; perm: the first nsel[b] entries of the host's permutation, distinct).  max_sel >= every nsel[b].
+ * depth, out float [B][HW]; perm, sel_off [B], nsel [B] int32 on the device; perm may be NULL with max_sel 0. */
+int vidc_sparse_sample_scatter(const float* depth, const int32_t* index, const int32_t* perm, const int32_t* sel_off, const int32_t* nsel,
+                               int max_sel, int B, int HW, float* out, vidc_stream_t stream);
+
+/* Ground-truth depth of the NYU loader (dataset.py:403-408): vidc_resize_nearest_u16_depth with divisor 5000, then
+ * d < min_depth -> 0 and d > max_depth -> 0, compared in fp32 (as torch compares a float tensor with a Python scalar). */
+int vidc_resize_nearest_u16_depth_range(const uint16_t* src, float* dst, int B, int H, int W, int Ho, int Wo, const int32_t* xtab,
+                                        const int32_t* ytab, float divisor, float min_depth, float max_depth, vidc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * evaluation statistics and output conversion on the device   (network_run.py:42-50, 72-82, 198-225, 387-403)
  * ---------------------------------------------------------------------------------------------- */
 

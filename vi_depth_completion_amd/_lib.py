@@ -26,6 +26,8 @@ TILE_AUTO = 0
 PREC_FP32, PREC_BF16X3, PREC_BF16, PREC_MXFP8 = 0, 1, 2, 3
 TILE_KIND_AUTO, TILE_KIND_MFMA, TILE_KIND_STREAM, TILE_KIND_WINOGRAD = range(4)      # vidc_conv_tile_kind
 SPLITK_COUNTERS = 16384            # VIDC_SPLITK_COUNTERS: ticket counters at the head of a split-K workspace
+NONZERO_CHUNK = 1024              # VIDC_NONZERO_CHUNK
+U8_UNIT, U8_NORMAL_GT, U8_NORMAL_PRED, U8_NORMAL_PRED_NYU = range(4)      # modes of vidc_u8_decode_chw
 PNG_DEPTH16_F32, PNG_NORMAL8_F32, PNG_RGB8_F32, PNG_GRAY8_U8 = range(4)      # vidc_png_format
 PNG_FILTER_NONE, PNG_FILTER_SUB, PNG_FILTER_UP, PNG_FILTER_AVERAGE, PNG_FILTER_PAETH, PNG_FILTER_ADAPTIVE = range(6)      # vidc_png_filter
 
@@ -241,6 +243,13 @@ SIGNATURES = {
     "vidc_rasterize_sparse_depth": (C.c_int, [_vp, _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _i, _i, _vp]),
     "vidc_nearest_table": (C.c_int, [_i, _i, _vp]),
     "vidc_resize_nearest_u16_depth": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, C.c_float, _vp]),
+    "vidc_u8_decode_chw": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "vidc_rasterize_pixel_tracks_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
+    "vidc_rasterize_pixel_tracks": (C.c_int, [_vp, _vp, _i, _i, C.c_double, _vp, _vp, _i, _i, _vp, _vp]),
+    "vidc_nonzero_compact_scratch_bytes": (C.c_size_t, [_i, _i]),
+    "vidc_nonzero_compact": (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "vidc_sparse_sample_scatter": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "vidc_resize_nearest_u16_depth_range": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, C.c_float, C.c_float, C.c_float, _vp]),
     "vidc_depth_metrics_scratch_bytes": (C.c_size_t, [C.c_longlong]),
     "vidc_depth_metrics": (C.c_int, [_vp, _vp, C.c_longlong, _vp, _i, _vp, _vp]),
     "vidc_depth_to_mm_u32": (C.c_int, [_vp, _vp, C.c_longlong, _vp]),

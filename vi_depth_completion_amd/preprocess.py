@@ -144,3 +144,209 @@ class FramePreprocessor:
             d16 = depth_u16 if torch.is_tensor(depth_u16) else torch.from_numpy(np.ascontiguousarray(depth_u16))
             out["depth"] = self.gt_depth(d16.to(self.device, non_blocking=True))
         return out
+
+
+# ---- training batches: ScanNetSmallFramesDataset (dataset.py:58-250) and NYUDataset (dataset.py:355-441) ---------------------------
+SCANNET_FC = (577.87061 / 2, 580.25851 / 2)      # dataset.py:91-92
+SCANNET_CC = (319.87654 / 2, 239.87603 / 2)
+TRACK_DIVISOR = 2.0                              # both loaders: "the tracks have been created for 640x480 image" (dataset.py:204, 416-417)
+
+
+def scannet_gravity_and_alignment(gravity):
+    """dataset.py:132 and compute_alignment_tensor (dataset.py:45-55), host, torch CPU fp32 like the reference: no sign flip."""
+    g = torch.tensor(np.asarray(gravity, dtype=np.float64), dtype=torch.float)
+    psi = g[1] * g[1] + g[2] * g[2]
+    if psi < 1e-6:
+        return g, g
+    pitch = torch.atan2(g[2], g[1])
+    if torch.cos(pitch) > 0.3:
+        return g, torch.tensor([0.0, 1.0, 0.0], dtype=torch.float)
+    return g, g
+
+
+def track_rows(klt_tracks):
+    """list of B track tables -> (rows float64 [N,4] of all images, offsets int32 [B+1]).  A table without rows (an empty file, a failed
+    read) contributes none; the three-column table of tracked KLT features (id, x, y: dataset.py:177, 189) gets a zero depth column."""
+    rows = []
+    for t in klt_tracks:
+        a = np.atleast_2d(np.asarray(t, dtype=np.float64))
+        if a.shape[1] == 3:
+            a = np.concatenate([a, np.zeros((a.shape[0], 1))], axis=1)
+        rows.append(a if a.shape[1] == 4 else np.zeros((0, 4)))
+    offs = np.zeros(len(rows) + 1, np.int32)
+    offs[1:] = np.cumsum([r.shape[0] for r in rows])
+    return (np.concatenate(rows) if offs[-1] else np.zeros((0, 4))), offs
+
+
+def draw_sparse_sample(counts, num_points, rng=np.random):
+    """The draws of dataset.py:193-200 for one batch, image by image: `counts[b]` non-zero ground-truth pixels, `num_points[b]` rows in
+    the track table.  num_points >= count: the clone, nothing is drawn (nsel -1).  Otherwise permutation(count)[0:num_points] -- drawn
+    even for num_points == 0 -- natively on the MT19937 state when `rng` is numpy's legacy generator (plane._LegacyStream; committed
+    once), through rng.permutation otherwise.  Returns (perm int32 of all images, sel_off int32 [B], nsel int32 [B])."""
+    from .plane import _LegacyStream
+    stream = _LegacyStream.open(rng)
+    perm, sel_off, nsel, off = [], [], [], 0
+    for count, n in zip(counts, num_points):
+        count, n = int(count), int(n)
+        sel_off.append(off)
+        if n >= count:
+            nsel.append(-1)
+            continue
+        p = stream.permutation_prefix(count, n) if stream is not None else np.asarray(rng.permutation(count)[0:n], dtype=np.int32)
+        perm.append(p)
+        nsel.append(n)
+        off += n
+    if stream is not None:
+        stream.commit()
+    return (np.concatenate(perm).astype(np.int32) if perm else np.zeros(0, np.int32)), np.asarray(sel_off, np.int32), np.asarray(nsel, np.int32)
+
+
+class _TrainingBatches(FramePreprocessor):
+    """What the two training-batch classes share: input checks, the byte-image decode and the pixel-track map (csrc/train_preprocess.hip)."""
+
+    def _input(self, x, name, dtypes, shape):
+        """A raw array of the caller's: numpy -> uploaded through pinned memory; a torch tensor has to be on the GPU already."""
+        if isinstance(x, np.ndarray):
+            if x.dtype == np.uint16:
+                x = x.view(np.int16)
+            x = self._upload(torch.from_numpy(np.ascontiguousarray(x)))
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise RuntimeError("%s: a numpy array or a GPU tensor is needed (there is no CPU path)" % name)
+        if x.dtype not in dtypes:
+            raise RuntimeError("%s: dtype %s, expected %s" % (name, x.dtype, " or ".join(str(d) for d in dtypes)))
+        if tuple(x.shape) != tuple(shape):
+            raise RuntimeError("%s: shape %s, expected %s" % (name, tuple(x.shape), tuple(shape)))
+        return x.contiguous()
+
+    def decode(self, u8, mode):
+        """(B,H,W,C) or (B,H,W) uint8 on the device -> (B,C,H,W) float32 by one of the reference's byte expressions (_lib.U8_*)."""
+        if not torch.is_tensor(u8) or not u8.is_cuda or u8.dtype != torch.uint8 or u8.dim() not in (3, 4):
+            raise RuntimeError("decode() takes a uint8 GPU tensor (B,H,W,C) or (B,H,W)")
+        x = u8.contiguous()
+        B, H, W = x.shape[:3]
+        Cc = x.shape[3] if x.dim() == 4 else 1
+        y = torch.empty((B, Cc, H, W), dtype=torch.float32, device=x.device)
+        L.check(L.lib().vidc_u8_decode_chw(L.ptr(x), L.ptr(y), B, H, W, Cc, mode, L.current_stream()), "u8_decode_chw")
+        return y
+
+    def pixel_tracks(self, klt_tracks, gt_depth=None):
+        """list of B tables (N_i,4) = (id, x, y, d) in 640x480 pixel coordinates -> (B,1,Ho,Wo) float32 sparse depth; with `gt_depth`
+        (B,1,Ho,Wo) the ground truth at the tracks' pixels instead of d."""
+        B = len(klt_tracks)
+        Ho, Wo = self.out_hw
+        allr, offs = track_rows(klt_tracks)
+        n = int(offs[-1])
+        tr = self._upload(torch.from_numpy(np.ascontiguousarray(allr))) if n else None
+        of = self._upload(torch.from_numpy(offs))
+        d = torch.empty((B, 1, Ho, Wo), dtype=torch.float32, device=self.device)
+        lib = L.lib()
+        scratch = torch.empty(lib.vidc_rasterize_pixel_tracks_scratch_bytes(B, Ho, Wo), dtype=torch.uint8, device=self.device)
+        L.check(lib.vidc_rasterize_pixel_tracks(L.ptr(tr), L.ptr(of), n, B, TRACK_DIVISOR, L.ptr(gt_depth), L.ptr(d), Ho, Wo, L.ptr(scratch),
+                                                L.current_stream()), "rasterize_pixel_tracks")
+        self._keep = (tr, of, scratch)
+        return d
+
+
+class ScanNetFramePreprocessor(_TrainingBatches):
+    """The batch dictionary of ScanNetSmallFramesDataset (dataset.py:95-247) on the device, restricted to the keys main.py:262-280 and
+    network_run.py:150-225 read: image, depth, mask, normal, sparse_depth, gravity, aligned_direction, homogeneous_coordinates and
+    predicted_normal.  File reading and the PNG decode stay with the caller, who hands over the raw arrays:
+
+        pre = ScanNetFramePreprocessor(device)
+        batch = pre(color_u8, depth_u16, orient_u8, mask_u8, gravity, klt_tracks)      # (B,240,320,3) / (B,240,320) / (B,3) / list of (N_i,4)
+
+    With generate_random_sparse_pointcloud the sample of dataset.py:193-202 needs the number of non-zero ground-truth pixels of every image
+    on the host before it can draw: ONE device->host read of B counts per batch (the reference's torch.nonzero is the same point of
+    synchronisation), then the draws in batch order from `rng`."""
+
+    def __init__(self, device="cuda", hw=(240, 320), read_depths_from_pointcloud=True, generate_random_sparse_pointcloud=False, rng=np.random):
+        super().__init__(device, in_hw=hw, out_hw=hw, fc=SCANNET_FC, cc=SCANNET_CC)
+        self.read_pointcloud, self.random_sparse, self.rng = bool(read_depths_from_pointcloud), bool(generate_random_sparse_pointcloud), rng
+        self._count_pinned = self._count_event = None
+
+    def random_sparse_sample(self, depth, klt_tracks):
+        """dataset.py:192-202 for a batch: depth (B,1,H,W) float32 on the device -> (B,1,H,W) sparse depth."""
+        lib, st = L.lib(), L.current_stream()
+        B, HW = depth.shape[0], depth.shape[2] * depth.shape[3]
+        count = torch.empty(B, dtype=torch.int32, device=self.device)
+        index = torch.empty((B, HW), dtype=torch.int32, device=self.device)
+        scratch = torch.empty(lib.vidc_nonzero_compact_scratch_bytes(B, HW), dtype=torch.uint8, device=self.device)
+        L.check(lib.vidc_nonzero_compact(L.ptr(depth), B, HW, L.ptr(count), L.ptr(index), L.ptr(scratch), st), "nonzero_compact")
+        if self._count_pinned is None or self._count_pinned.numel() != B:
+            self._count_pinned = torch.empty(B, dtype=torch.int32, pin_memory=True)
+            self._count_event = torch.cuda.Event()
+        self._count_pinned.copy_(count, non_blocking=True)
+        self._count_event.record()
+        num_points = [np.atleast_2d(np.asarray(t)).shape[0] for t in klt_tracks]      # dataset.py:183, 193: an empty file counts 1, a failed read 0
+        self._count_event.synchronize()
+        perm, sel_off, nsel = draw_sparse_sample(self._count_pinned.numpy(), num_points, self.rng)
+        table = self._upload(torch.from_numpy(np.concatenate([sel_off, nsel, perm])))
+        out = torch.empty_like(depth)
+        max_sel = max(0, int(nsel.max()))
+        L.check(lib.vidc_sparse_sample_scatter(L.ptr(depth), L.ptr(index), table.data_ptr() + 8 * B if perm.size else None, table.data_ptr(),
+                                               table.data_ptr() + 4 * B, max_sel, B, HW, L.ptr(out), st), "sparse_sample_scatter")
+        self._keep = (count, index, scratch, table)
+        return out
+
+    def __call__(self, color_u8, depth_u16, orient_u8, mask_u8, gravity, klt_tracks, predicted_normal_u8=None):
+        H, W = self.out_hw
+        B = len(klt_tracks)
+        u8, u16 = (torch.uint8,), (torch.uint16, torch.int16)
+        color = self._input(color_u8, "color_u8", u8, (B, H, W, 3))
+        depth16 = self._input(depth_u16, "depth_u16", u16, (B, H, W))
+        orient = self._input(orient_u8, "orient_u8", u8, (B, H, W, 3))
+        mask = self._input(mask_u8, "mask_u8", u8, (B, H, W))
+        gv = np.asarray(gravity, dtype=np.float64)
+        if gv.shape != (B, 3):
+            raise RuntimeError("gravity: shape %s, expected %s" % (gv.shape, (B, 3)))
+        ga = [scannet_gravity_and_alignment(g) for g in gv]
+        depth = self.gt_depth(depth16)                      # dataset.py:124-126: / 1000.0, identity tables
+        if self.random_sparse:
+            sparse = self.random_sparse_sample(depth, klt_tracks)
+        else:
+            sparse = self.pixel_tracks(klt_tracks, None if self.read_pointcloud else depth)
+        out = {"image": self.decode(color, L.U8_UNIT), "mask": self.decode(mask, L.U8_UNIT).view(B, H, W), "depth": depth,
+               "normal": self.decode(orient, L.U8_NORMAL_GT), "sparse_depth": sparse,
+               "gravity": self._upload(torch.stack([g for g, _ in ga])), "aligned_direction": self._upload(torch.stack([a for _, a in ga])),
+               "homogeneous_coordinates": self.homogeneous.unsqueeze(0).expand(B, -1, -1, -1)}
+        if predicted_normal_u8 is not None:
+            out["predicted_normal"] = self.decode(self._input(predicted_normal_u8, "predicted_normal_u8", u8, (B, H, W, 3)), L.U8_NORMAL_PRED)
+        return out
+
+
+class NYUFramePreprocessor(_TrainingBatches):
+    """The batch dictionary of NYUDataset (dataset.py:381-438) on the device: image (bilinear resize + ToTensor), depth (nearest resize,
+    / 5000, the [min_depth, max_depth] rule), sparse_depth and predicted_normal.
+
+        pre = NYUFramePreprocessor(device)
+        batch = pre(color_u8, depth_u16, klt_tracks, predicted_normal_u8)      # (B,480,640,3) / (B,480,640) / list of (N_i,4) / (B,240,320,3)"""
+
+    DEPTH_UNITS_PER_METRE = 5000.0      # dataset.py:405
+
+    def __init__(self, device="cuda", in_hw=(480, 640), out_hw=(240, 320), max_depth=7.0, min_depth=0.1):
+        super().__init__(device, in_hw=in_hw, out_hw=out_hw)
+        self.max_depth, self.min_depth = float(max_depth), float(min_depth)
+
+    def gt_depth_range(self, depth_u16):
+        """(B,H,W) uint16 on the device -> (B,1,Ho,Wo) float32 metres, 0 outside [min_depth, max_depth] (dataset.py:403-408)."""
+        if not depth_u16.is_cuda or depth_u16.dtype not in (torch.uint16, torch.int16):
+            raise RuntimeError("gt_depth_range() takes a uint16 GPU tensor (B,H,W)")
+        x = depth_u16.contiguous()
+        B = x.shape[0]
+        H, W = self.in_hw
+        Ho, Wo = self.out_hw
+        y = torch.empty((B, 1, Ho, Wo), dtype=torch.float32, device=x.device)
+        L.check(L.lib().vidc_resize_nearest_u16_depth_range(L.ptr(x), L.ptr(y), B, H, W, Ho, Wo, L.ptr(self.nx), L.ptr(self.ny), self.DEPTH_UNITS_PER_METRE,
+                                                            self.min_depth, self.max_depth, L.current_stream()), "gt_depth_range")
+        return y
+
+    def __call__(self, color_u8, depth_u16, klt_tracks, predicted_normal_u8=None):
+        (H, W), (Ho, Wo) = self.in_hw, self.out_hw
+        B = len(klt_tracks)
+        color = self._input(color_u8, "color_u8", (torch.uint8,), (B, H, W, 3))
+        depth16 = self._input(depth_u16, "depth_u16", (torch.uint16, torch.int16), (B, H, W))
+        out = {"image": self.resize(color), "depth": self.gt_depth_range(depth16), "sparse_depth": self.pixel_tracks(klt_tracks)}
+        if predicted_normal_u8 is not None:
+            out["predicted_normal"] = self.decode(self._input(predicted_normal_u8, "predicted_normal_u8", (torch.uint8,), (B, Ho, Wo, 3)),
+                                                  L.U8_NORMAL_PRED_NYU)
+        return out
