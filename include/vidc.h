@@ -931,13 +931,14 @@ int vidc_depth_l1_loss(const float* pred, const float* depth_gt, int B, int H, i
 enum vidc_op_kind { VIDC_OP_CONV = 1, VIDC_OP_STEM = 2, VIDC_OP_MAXPOOL = 3, VIDC_OP_UPSAMPLE = 4, VIDC_OP_HEAD = 5,
                     VIDC_OP_WARP_PARAMS = 6, VIDC_OP_WARP_FWD = 7, VIDC_OP_WARP_INV = 8, VIDC_OP_COPY = 9, VIDC_OP_SPLIT = 10,
                     VIDC_OP_AVGPOOL = 11, VIDC_OP_NORMALIZE = 12, VIDC_OP_DET_IM2COL = 13, VIDC_OP_NEAREST2X = 14,
-                    /* 15: retired (persistent conv chain, removed in round 5) */ VIDC_OP_MASK = 16 /* vidc_mask_scale: p = x, image, y; i = B,h,w,C,ldx,ldy,H,W */,
-                    VIDC_OP_WINO_IN = 17  /* vidc_winograd_input_transform: p = x, v; i = B,H,W,C,ldx,Cin,m,split,ldv */,
-                    VIDC_OP_WINO_OUT = 18 /* vidc_winograd_output_transform: p = mm, y, y_split, scale1, shift1, scale2, shift2; i = B,Ho,Wo,C,Cout,ldy,m,flags,ldm */,
-                    VIDC_OP_QUANT = 19    /* vidc_quant_mxfp8: p = x, y; i = rows (lo, hi), C, ldx, groups */,
-                    VIDC_OP_CAST = 20     /* vidc_cast_bf16: p = x, y; i = rows (lo, hi), C, ldx */ };
+                    /* 15: retired (persistent conv chain, removed in round 5) */ VIDC_OP_MASK = 16, VIDC_OP_WINO_IN = 17,
+                    VIDC_OP_WINO_OUT = 18, VIDC_OP_QUANT = 19, VIDC_OP_CAST = 20, VIDC_OP_STEM_WARPED = 21 };
 
-typedef struct vidc_generic_args {   /* arguments of the non-conv launchers, in declaration order */
+/* The arguments of every op but VIDC_OP_CONV (which carries its vidc_conv_desc).  Each kind runs one entry point (vidc_op_info names it;
+ * VIDC_OP_COPY: a device-to-device copy (const void* src, void* dst, long long bytes)), and the slots are a function of that entry's
+ * declaration: walk its parameters in order; a pointer takes the next p slot, an int the next i slot, a float the next f slot, a long long
+ * the next two i slots (low word, then high word); the stream is not stored.  Unused slots are zero. */
+typedef struct vidc_generic_args {
     const void* p[8];
     int32_t i[16];
     float f[8];
@@ -953,6 +954,15 @@ typedef struct vidc_op {
         vidc_generic_args g;
     } u;
 } vidc_op;
+
+/* What the library runs for one op kind (its row of csrc/program.hip's table): the binding packs and tests check slots by asking. */
+typedef struct vidc_op_entry {
+    const char* name;      /* the entry point, in static storage, e.g. "vidc_maxpool3x3s2" */
+    const char* classes;   /* one char per parameter of its declaration without the stream: p pointer, i int, f float, l long long */
+} vidc_op_entry;
+/* Fills *out for a vidc_op_kind (VIDC_OP_CONV: vidc_conv2d_bn_act, "p" -- the descriptor it points to is op.u.conv itself, not a slot);
+ * VIDC_ERR_SHAPE for any other number. */
+int vidc_op_info(int kind, vidc_op_entry* out);
 
 #define VIDC_MAX_STREAMS 4
 #define VIDC_MAX_SEGMENTS 4

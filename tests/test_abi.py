@@ -212,9 +212,70 @@ def test_opt_in_warp_fusion_rewrites_the_program(lib, monkeypatch):
     stems = [kw for k, _, _, kw in fp.ops if k == "stem"]
     assert [kw.get("warp") is not None for kw in stems] == [True, False, False, False] and stems[0]["key"].startswith("sn/")
     i = kinds.index("stem")
-    g, wf = fp.c_ops[i].u.g, stems[0]["warp"]      # engine.finalize -> program.hip launch_op: the record pointer, the principal point, the convention
-    assert g.p[4] == fp.storage[wf["p"].buf].data_ptr() + 4 * wf["p"].ch_off and g.p[0] == fp.storage[wf["x"].buf].data_ptr() + 4 * wf["x"].ch_off
-    assert (g.f[0], g.f[1], g.i[8]) == (np.float32(wf["intr"].cx), np.float32(wf["intr"].cy), int(wf["ac"]))
+    wf = stems[0]["warp"]      # engine.finalize -> program.hip launch_op: the record pointer, the principal point, the convention
+    assert fp.c_ops[i].kind == L.OP_STEM_WARPED == 21 and [op.kind for op, k in zip(fp.c_ops, kinds) if k == "stem"][1:] == [L.OP_STEM] * 3
+    x, records, _w, _y, _B, _H, _W, _Cout, _ldy, _relu, _y_split, _split_ch0, cx, cy, align_corners = L.op_args(fp.c_ops[i])
+    assert records == fp.storage[wf["p"].buf].data_ptr() + 4 * wf["p"].ch_off and x == fp.storage[wf["x"].buf].data_ptr() + 4 * wf["x"].ch_off
+    assert (cx, cy, align_corners) == (np.float32(wf["intr"].cx), np.float32(wf["intr"].cy), int(wf["ac"]))
+
+
+GENERIC_KINDS = [k for k in range(2, 22) if k != 15]
+
+
+def _classes_of(argtypes):
+    """The class string of an entry's ctypes argument list without the stream."""
+    table = {C.c_void_p: "p", C.c_int: "i", C.c_float: "f", C.c_longlong: "l"}
+    return "".join("p" if issubclass(t, C._Pointer) else table[t] for t in argtypes[:-1])
+
+
+@pytest.mark.parametrize("kind", [1] + GENERIC_KINDS)
+def test_op_info_agrees_with_the_binding(lib, kind):
+    """vidc_op_info for every op kind: where the entry it names is exported, the argument classes the library derived from the C declaration
+    are the ones of the ctypes table (written by hand from the same header)."""
+    e = L.OpEntry()
+    assert lib.vidc_op_info(kind, C.byref(e)) == 0 and e.classes == L.op_classes(kind)
+    exported = e.name in L.SIGNATURES
+    assert exported == (kind != L.OP_COPY) and set(e.classes) <= set("pifl")
+    if exported:
+        assert e.classes == _classes_of(L.SIGNATURES[e.name][1]) and L.SIGNATURES[e.name][1][-1] is C.c_void_p
+    else:
+        assert e.classes == "ppl"      # the copy: (src, dst, long long bytes)
+    if kind == L.OP_CONV:              # its descriptor is op.u.conv, not slots
+        assert (e.name, e.classes) == ("vidc_conv2d_bn_act", "p")
+        with pytest.raises(ValueError):
+            L.pack_op(L.Op(), kind, (8,))
+
+
+@pytest.mark.parametrize("kind", GENERIC_KINDS)
+def test_pack_op_round_trips(lib, kind):
+    """pack_op then op_args gives back a tuple of pairwise distinct values, a long long above 2^32 among them; the slots used are the
+    leading ones of each class and the rest stay zero; a short and a long tuple are refused."""
+    classes = L.op_classes(kind)
+    args = tuple({"p": 0x7F0000001000 + 256 * j, "i": 1000 + j, "f": 0.5 + j, "l": (5 << 32) + 0x80000007 + j}[c] for j, c in enumerate(classes))
+    op = L.pack_op(L.Op(), kind, args)
+    assert op.kind == kind and L.op_args(op) == args
+    g = op.u.g
+    used = {"p": classes.count("p"), "i": classes.count("i") + 2 * classes.count("l"), "f": classes.count("f")}
+    for c, n in used.items():
+        arr = list(getattr(g, c))
+        assert all(arr[:n]) and not any(arr[n:]), (c, arr)
+    for bad in (args[:-1], args + (1,)):
+        with pytest.raises(ValueError):
+            L.pack_op(L.Op(), kind, bad)
+    for j in (classes.find("i"), classes.find("l")):
+        for wrong in (1.5, 1 << 31):         # a non-integer where an int or a long long is due, an int that does not fit an int
+            if j >= 0 and (classes[j] == "i" or wrong == 1.5):
+                with pytest.raises((TypeError, ValueError)):
+                    L.pack_op(L.Op(), kind, args[:j] + (wrong,) + args[j + 1:])
+    assert L.op_args(L.pack_op(L.Op(), kind, tuple(None if c == "p" else a for c, a in zip(classes, args))))[classes.index("p")] == 0
+
+
+def test_unknown_op_kinds_are_refused(lib):
+    for kind in (0, 15, 22, -1):
+        assert lib.vidc_op_info(kind, C.byref(L.OpEntry())) == -2
+        with pytest.raises(RuntimeError):
+            L.pack_op(L.Op(), kind, ())
+    assert lib.vidc_op_info(L.OP_STEM, None) == -1
 
 
 def test_frame_program_structure(recorded_frame_program, recorded_programs):

@@ -189,9 +189,9 @@ def test_bf16_descriptors(programs):
             if d.flags & L.BF16_OUT:
                 assert d.y_split == prog.storage[kw["bf16_out"].buf].data_ptr() and d.ldy == len(kw["keys"]) * co
         elif kind == "cast":
-            g = op.u.g
-            assert op.kind == L.OP_CAST == 20 and (g.i[0], g.i[2], g.i[3]) == (kw["x"].B * kw["x"].H * kw["x"].W, kw["x"].C * kw["x"].G, kw["x"].ld)
-            assert prog.buf_elems[kw["y"].buf] * 2 == g.i[0] * g.i[2]
+            _x, _y, rows, c, ldx = L.op_args(op)
+            assert op.kind == L.OP_CAST == 20 and (rows, c, ldx) == (kw["x"].B * kw["x"].H * kw["x"].W, kw["x"].C * kw["x"].G, kw["x"].ld)
+            assert prog.buf_elems[kw["y"].buf] * 2 == rows * c
 
 
 def test_other_modes_are_untouched(programs):

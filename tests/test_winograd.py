@@ -116,7 +116,8 @@ def test_recorded_program_has_winograd_triples(monkeypatch):
             a2 = (kwargs["m"] + 2) ** 2
             desc = w.c_ops[i + 1].u.conv
             assert desc.groups == a2 * len(w.ops[i + 1][3]["keys"]) and desc.KH == 1 and desc.flags == 0 and desc.p_gs == 0
-            assert desc.ldx == a2 * kwargs["x"].C * kwargs["x"].G and w.c_ops[i].u.g.i[8] == desc.ldx and w.c_ops[i + 2].u.g.i[8] == desc.ldy
+            ldv, ldm = L.op_args(w.c_ops[i])[-1], L.op_args(w.c_ops[i + 2])[-1]      # the last argument of either transform
+            assert desc.ldx == a2 * kwargs["x"].C * kwargs["x"].G and ldv == desc.ldx and ldm == desc.ldy
 
 
 def test_recorded_program_with_one_launch_layers(monkeypatch):

@@ -83,9 +83,7 @@ def time_split(lib, x_ptr, y_ptr, rows, Cc, ldx, st, copies=20):
     """GPU-bound time of the split kernel that a bf16x3 conv needs in front of it."""
     ops = (L.Op * copies)()
     for o in ops:
-        o.kind = L.OP_SPLIT
-        o.u.g.p[0], o.u.g.p[1] = x_ptr, y_ptr
-        o.u.g.i[0], o.u.g.i[1], o.u.g.i[2], o.u.g.i[3] = rows & 0xFFFFFFFF, rows >> 32, Cc, ldx
+        L.pack_op(o, L.OP_SPLIT, (x_ptr, y_ptr, rows, Cc, ldx))      # vidc_split_bf16x3's arguments
     h = C.c_void_p()
     if lib.vidc_program_create(ops, copies, C.byref(h)) != 0:
         return 0.0

@@ -3,9 +3,10 @@
     python tools/program_digest.py DIR            # the full dumps, DIR/<name>.json, for diffing two commits
     python tools/program_digest.py DIR --golden   # ... and tests/golden/program_recordings.json: {name: [ops, sha256 of the dump, counters, op hashes]}
 
-16 dry-run recordings on CPU (batch 1, 240x320; tests/test_bf16_cpu.py::_record): the frame program, the two stand-alone networks and
--- under mixed and bf16 -- the DORN network in each of the four precision modes, and the mixed frame program with VIDC_FUSE_SPLIT=0 and
-with VIDC_FUSE_WARP=1.  A dump holds every op (name, kind, stream, wait mask, buffers read and written, the whole descriptor) and the
+18 dry-run recordings on CPU (batch 1, 240x320; tests/test_bf16_cpu.py::_record): the frame program, the two stand-alone networks and
+-- under mixed and bf16 -- the DORN network in each of the four precision modes, the mixed frame program with VIDC_FUSE_SPLIT=0 and
+with VIDC_FUSE_WARP=1, and the two group variants of the mixed frame program's segment 0 that pipeline.build_frame_program makes (the
+first and the drain tick).  A dump holds every op (name, kind, stream, wait mask, buffers read and written, the whole descriptor) and the
 program's buffer sizes, cuts, allocation and fold counters.  Device addresses are replaced by names that do not depend on the process:
 ["S", storage block, byte offset], ["K", kept weight / affine tensor, byte offset], ["WS", stream id]; an address that is none of these
 is an error.  tests/test_program_recording.py compares the digests with the committed golden.
@@ -23,12 +24,13 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 GOLDEN = os.path.join(ROOT, "tests", "golden", "program_recordings.json")
 MODES = ("fp32", "mixed", "mxfp8", "bf16")
 EXTRA = {"mixed+nofuse/frame": ("VIDC_FUSE_SPLIT", "0"), "mixed+fusewarp/frame": ("VIDC_FUSE_WARP", "1")}      # frame program, mixed mode
+VARIANTS = {"mixed/frame/variant(0,1,4,keep)": (0, 0, 1, 4, True), "mixed/frame/variant(1,4,4,drop)": (0, 1, 4, 4, False)}      # Program.variant_ops arguments
 COUNTERS = ("n_fused_splits", "n_fused_quants", "n_fused_casts", "n_fused_warps")
 CONV_POINTERS = ("x", "w", "y", "scale1", "shift1", "scale2", "shift2", "residual", "workspace", "y_split")
 
 
 def record_all(programs=None):
-    """{"<mode>/<name>": Program} of the 16 recordings.  programs: {mode: _record(mode)} the caller made already."""
+    """{"<mode>/<name>": Program} of the 16 whole-program recordings.  programs: {mode: _record(mode)} the caller made already."""
     from test_bf16_cpu import _record
     out = {}
     for mode in MODES:
@@ -70,12 +72,25 @@ def _namer(prog):
     return name
 
 
-def dump(prog):
-    """The canonical form of a finalized (dry-run) program: a JSON-able dict."""
+def dump_all():
+    """{name: dump} of the 18 recordings."""
+    progs = record_all()
+    dumps = {name: dump(prog) for name, prog in progs.items()}
+    for name, args in VARIANTS.items():
+        dumps[name] = dump(progs["mixed/frame"], *progs["mixed/frame"].variant_ops(*args))
+    return dumps
+
+
+def dump(prog, c_ops=None, indices=None):
+    """The canonical form of a finalized (dry-run) program: a JSON-able dict.  c_ops, indices: the op array of a group variant and the
+    program's ops it was made from (Program.variant_ops), in place of the program's own."""
     from vi_depth_completion_amd import _lib as L
     name = _namer(prog)
     ops = []
-    for i, (cop, (_kind, reads, writes, _kw)) in enumerate(zip(prog.c_ops, prog.ops)):
+    c_ops = prog.c_ops if c_ops is None else c_ops
+    indices = range(len(prog.ops)) if indices is None else indices
+    for cop, i in zip(c_ops, indices):
+        _kind, reads, writes, _kw = prog.ops[i]
         o = {"name": prog.op_names[i], "kind": cop.kind, "stream_id": cop.stream_id, "wait_mask": cop.wait_mask,
              "reads": sorted(reads), "writes": sorted(writes)}
         if cop.kind == L.OP_CONV:
@@ -83,7 +98,7 @@ def dump(prog):
         else:
             o["p"], o["i"], o["f"] = [name(a) for a in cop.u.g.p], list(cop.u.g.i), [repr(v) for v in cop.u.g.f]
         ops.append(o)
-    assert len(ops) == len(prog.c_ops) == len(prog.ops) == len(prog.op_names)
+    assert len(ops) == len(c_ops) == len(indices) and len(prog.c_ops) == len(prog.ops) == len(prog.op_names)
     return {"ops": ops, "buf_elems": list(prog.buf_elems), "cuts": list(prog.cuts), "bytes_allocated": prog.bytes_allocated,
             "counters": {c: getattr(prog, c, 0) for c in COUNTERS}}
 
@@ -104,8 +119,7 @@ def main(argv):
         sys.exit(__doc__)
     os.makedirs(argv[0], exist_ok=True)
     golden = {}
-    for name, prog in record_all().items():
-        d = dump(prog)
+    for name, d in dump_all().items():
         golden[name] = digest(d)
         with open(os.path.join(argv[0], name.replace("/", "_") + ".json"), "w") as f:
             f.write(text(d) + "\n")

@@ -4,6 +4,7 @@ There is no fallback: if the library is missing or a call fails, a RuntimeError 
 `build()` compiles it in-tree with hipcc for gfx950 (also used by __graft_entry__.build()).
 """
 import ctypes as C
+import operator
 import os
 import subprocess
 
@@ -21,7 +22,7 @@ CLOCK_STAMP_WGS = 8      # VIDC_CLOCK_STAMP_WGS
 # vidc_conv_flags / vidc_up_flags / vidc_op_kind / vidc_conv_tile
 RELU1, AFFINE2, RELU2, RESIDUAL, RELU3, ACCUM, SPLIT_OUT, NO_F32_OUT, STATS_OUT, X_PLANAR_GROUPS, MXFP8_OUT, BF16_OUT = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048
 UP_RELU, UP_ACCUM, UP_NO_F32_OUT = 1, 2, 4
-OP_CONV, OP_STEM, OP_MAXPOOL, OP_UPSAMPLE, OP_HEAD, OP_WARP_PARAMS, OP_WARP_FWD, OP_WARP_INV, OP_COPY, OP_SPLIT, OP_AVGPOOL, OP_NORMALIZE, OP_DET_IM2COL, OP_NEAREST2X, _OP_RETIRED_15, OP_MASK, OP_WINO_IN, OP_WINO_OUT, OP_QUANT, OP_CAST = range(1, 21)
+OP_CONV, OP_STEM, OP_MAXPOOL, OP_UPSAMPLE, OP_HEAD, OP_WARP_PARAMS, OP_WARP_FWD, OP_WARP_INV, OP_COPY, OP_SPLIT, OP_AVGPOOL, OP_NORMALIZE, OP_DET_IM2COL, OP_NEAREST2X, _OP_RETIRED_15, OP_MASK, OP_WINO_IN, OP_WINO_OUT, OP_QUANT, OP_CAST, OP_STEM_WARPED = range(1, 22)
 TILE_AUTO = 0
 PREC_FP32, PREC_BF16X3, PREC_BF16, PREC_MXFP8 = 0, 1, 2, 3
 TILE_KIND_AUTO, TILE_KIND_MFMA, TILE_KIND_STREAM, TILE_KIND_WINOGRAD = range(4)      # vidc_conv_tile_kind
@@ -140,6 +141,13 @@ class _OpUnion(C.Union):
 class Op(C.Structure):
     _fields_ = [("kind", C.c_int32), ("stream_id", C.c_int32), ("wait_mask", C.c_int32), ("reserved", C.c_int32),
                 ("u", _OpUnion)]
+
+
+class OpEntry(C.Structure):
+    """vidc_op_entry (include/vidc.h): the entry point an op kind runs and the classes of its arguments."""
+    _fields_ = [("_name", C.c_char_p), ("_classes", C.c_char_p)]
+    name = property(lambda self: self._name.decode())
+    classes = property(lambda self: self._classes.decode())
 
 
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
@@ -278,6 +286,7 @@ SIGNATURES = {
     "vidc_mask_paste": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "vidc_instance_map_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "vidc_instance_map": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
+    "vidc_op_info": (C.c_int, [_i, C.POINTER(OpEntry)]),
     "vidc_program_create": (C.c_int, [C.POINTER(Op), _i, C.POINTER(_vp)]),
     "vidc_program_run": (C.c_int, [_vp, _vp]),
     "vidc_program_capture": (C.c_int, [_vp, _vp]),
@@ -340,6 +349,67 @@ def __getattr__(name):
                      BF16_TILES=tuple(t for t, ti in info.items() if ti.precisions >> PREC_BF16 & 1),
                      TILE_WINO4_FUSED=next(t for t, ti in info.items() if ti.kind == TILE_KIND_WINOGRAD))
     return globals()[name]
+
+
+# ---- the slot rule of vidc_generic_args (include/vidc.h) is written in pack_op / op_args and nowhere else in Python -------------------
+_op_classes = {}
+
+
+def op_classes(kind):
+    """The argument classes of an op kind's entry point, one char per parameter without the stream (vidc_op_info)."""
+    if kind not in _op_classes:
+        e = OpEntry()
+        check(lib().vidc_op_info(kind, C.byref(e)), "op_info")
+        _op_classes[kind] = e.classes
+    return _op_classes[kind]
+
+
+def pack_op(op, kind, args):
+    """op.kind = kind and op.u.g = `args`, the arguments of the kind's entry point in the header's declaration order without the stream:
+    a pointer (an int, or None) takes the next p slot, an int the next i slot, a float the next f slot, a long long the next two i slots
+    (low word, then high word); the other slots are zero.  Raises on a wrong argument count, a non-integer where a pointer or an int is
+    due, an int outside int32 and an entry that needs more slots than there are."""
+    if kind == OP_CONV:
+        raise ValueError("a conv op carries its descriptor (op.u.conv), not argument slots")
+    classes = op_classes(kind)
+    if len(args) != len(classes):
+        raise ValueError("op kind %d takes %d arguments (%s), got %d" % (kind, len(classes), classes, len(args)))
+    slots = {"p": [], "i": [], "f": []}
+    for c, v in zip(classes, args):
+        if c == "f":
+            slots["f"].append(float(v))
+            continue
+        v = 0 if v is None and c == "p" else operator.index(v)      # (TypeError for a float or a tensor)
+        if c == "p":
+            slots["p"].append(v)
+        elif c == "l":
+            slots["i"] += [v & 0xFFFFFFFF, v >> 32 & 0xFFFFFFFF]
+        elif -1 << 31 <= v < 1 << 31:
+            slots["i"].append(v)
+        else:
+            raise ValueError("op kind %d: %d does not fit an int" % (kind, v))
+    g = GenericArgs()
+    for c, vals in slots.items():
+        arr = getattr(g, c)
+        if len(vals) > len(arr):
+            raise ValueError("op kind %d needs %d %s slots of %d" % (kind, len(vals), c, len(arr)))
+        for j, v in enumerate(vals):
+            arr[j] = v
+    op.kind, op.u.g = kind, g
+    return op
+
+
+def op_args(op):
+    """The inverse of pack_op: the arguments of a packed op in declaration order (a null pointer as 0)."""
+    g, n, out = op.u.g, {"p": 0, "i": 0, "f": 0}, []
+    for c in op_classes(op.kind):
+        k = "i" if c == "l" else c
+        v = getattr(g, k)[n[k]] or 0
+        n[k] += 1
+        if c == "l":
+            v, n["i"] = (v & 0xFFFFFFFF) | g.i[n["i"]] << 32, n["i"] + 1
+        out.append(v)
+    return tuple(out)
 
 
 def check(rc, what=""):

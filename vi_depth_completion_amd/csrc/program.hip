@@ -3,6 +3,9 @@
 // a captured hipGraph.  This is what replaces the reference's ~1500 Python-dispatched ATen calls per frame
 // (SURVEY.md §2.2): the Python host crosses the C ABI once per frame, not once per layer.
 #include "common.h"
+#include <tuple>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 struct vidc_program {
@@ -18,76 +21,110 @@ struct vidc_program {
 
 namespace {
 
+// ---- ops: kind -> entry point, and the slots of vidc_generic_args as a function of the entry's declaration (include/vidc.h) ----------
+struct Cursor { int p = 0, i = 0, f = 0; };      // the next free slot of each class
+
+// One parameter type: its class char, the slots it takes, and how it is read.  No primary definition: an entry with a parameter of any
+// other type does not compile.
+template <class T> struct Arg;
+template <class T> struct Arg<T*> {
+    static constexpr char cls = 'p';
+    static constexpr int np = 1, ni = 0, nf = 0;
+    static T* get(const vidc_generic_args& g, Cursor& n) { return static_cast<T*>(const_cast<void*>(g.p[n.p++])); }
+};
+template <> struct Arg<int> {
+    static constexpr char cls = 'i';
+    static constexpr int np = 0, ni = 1, nf = 0;
+    static int get(const vidc_generic_args& g, Cursor& n) { return g.i[n.i++]; }
+};
+template <> struct Arg<float> {
+    static constexpr char cls = 'f';
+    static constexpr int np = 0, ni = 0, nf = 1;
+    static float get(const vidc_generic_args& g, Cursor& n) { return g.f[n.f++]; }
+};
+template <> struct Arg<long long> {      // low word, then high word
+    static constexpr char cls = 'l';
+    static constexpr int np = 0, ni = 2, nf = 0;
+    static long long get(const vidc_generic_args& g, Cursor& n) {
+        const uint64_t lo = (uint32_t)g.i[n.i], hi = (uint32_t)g.i[n.i + 1];
+        n.i += 2;
+        return (long long)(lo | hi << 32);
+    }
+};
+
+// An entry int fn(A..., vidc_stream_t): K... indexes its parameters without the stream.
+template <class Seq, class... A> struct Entry;
+template <size_t... K, class... A> struct Entry<std::index_sequence<K...>, A...> {
+    using all = std::tuple<A...>;
+    template <size_t k> using arg = Arg<std::tuple_element_t<k, all>>;
+    static_assert(std::is_same_v<std::tuple_element_t<sizeof...(K), all>, vidc_stream_t>, "an entry's last parameter is the stream");
+    static_assert((0 + ... + arg<K>::np) <= 8 && (0 + ... + arg<K>::ni) <= 16 && (0 + ... + arg<K>::nf) <= 8,
+                  "the entry needs more slots than vidc_generic_args has");
+    static constexpr char classes[] = {arg<K>::cls..., '\0'};
+    template <int (*Fn)(A...)> static int call(const vidc_generic_args& g, vidc_stream_t s) {
+        Cursor n;
+        std::tuple<A...> args{arg<K>::get(g, n)..., s};      // a braced list: evaluated left to right, so each class's slots go in declaration order
+        return std::apply(Fn, args);
+    }
+};
+template <class... A> Entry<std::make_index_sequence<sizeof...(A) - 1>, A...> entry_of(int (*)(A...));
+
+int program_copy(const void* src, void* dst, long long bytes, vidc_stream_t s) {
+    VIDC_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, vidc::as_stream(s)));
+    return VIDC_OK;
+}
+
+struct OpRow {
+    int kind;
+    const char* name;
+    const char* classes;
+    int (*call)(const vidc_generic_args&, vidc_stream_t);
+};
+#define VIDC_OP_ROW(kind, fn) {kind, #fn, decltype(entry_of(&fn))::classes, &decltype(entry_of(&fn))::template call<&fn>}
+constexpr OpRow kOps[] = {      // row k = kind k
+    {},
+    VIDC_OP_ROW(VIDC_OP_CONV, vidc_conv2d_bn_act),      // (launched with op.u.conv, not through `call`)
+    VIDC_OP_ROW(VIDC_OP_STEM, vidc_stem_conv3x3s2),
+    VIDC_OP_ROW(VIDC_OP_MAXPOOL, vidc_maxpool3x3s2),
+    VIDC_OP_ROW(VIDC_OP_UPSAMPLE, vidc_upsample_bilinear_ac),
+    VIDC_OP_ROW(VIDC_OP_HEAD, vidc_head_conv1x1_upsample),
+    VIDC_OP_ROW(VIDC_OP_WARP_PARAMS, vidc_warp2dof_params),
+    VIDC_OP_ROW(VIDC_OP_WARP_FWD, vidc_warp2dof_fwd),
+    VIDC_OP_ROW(VIDC_OP_WARP_INV, vidc_warp2dof_inv_rot_norm),
+    VIDC_OP_ROW(VIDC_OP_COPY, program_copy),
+    VIDC_OP_ROW(VIDC_OP_SPLIT, vidc_split_bf16x3),
+    VIDC_OP_ROW(VIDC_OP_AVGPOOL, vidc_avgpool2d),
+    VIDC_OP_ROW(VIDC_OP_NORMALIZE, vidc_normalize_nchw),
+    VIDC_OP_ROW(VIDC_OP_DET_IM2COL, vidc_det_stem_im2col),
+    VIDC_OP_ROW(VIDC_OP_NEAREST2X, vidc_upsample_nearest2x),
+    {},                                                 // 15: retired
+    VIDC_OP_ROW(VIDC_OP_MASK, vidc_mask_scale),
+    VIDC_OP_ROW(VIDC_OP_WINO_IN, vidc_winograd_input_transform),
+    VIDC_OP_ROW(VIDC_OP_WINO_OUT, vidc_winograd_output_transform),
+    VIDC_OP_ROW(VIDC_OP_QUANT, vidc_quant_mxfp8),
+    VIDC_OP_ROW(VIDC_OP_CAST, vidc_cast_bf16),
+    VIDC_OP_ROW(VIDC_OP_STEM_WARPED, vidc_stem_conv3x3s2_warped),
+};
+#undef VIDC_OP_ROW
+constexpr int kOpRows = (int)(sizeof(kOps) / sizeof(kOps[0]));
+constexpr bool rows_in_kind_order() {
+    for (int k = 0; k < kOpRows; ++k)
+        if (kOps[k].name && kOps[k].kind != k) return false;
+    return true;
+}
+static_assert(kOpRows == VIDC_OP_STEM_WARPED + 1 && rows_in_kind_order(), "kOps: row k must hold kind k");
+
+const OpRow* op_row(int kind) { return kind > 0 && kind < kOpRows && kOps[kind].name ? &kOps[kind] : nullptr; }
+
 int launch_op(const vidc_op& op, hipStream_t st) {
     vidc_stream_t s = reinterpret_cast<vidc_stream_t>(st);
-    const vidc_generic_args& g = op.u.g;
-    switch (op.kind) {
-        case VIDC_OP_CONV:
-            return vidc_conv2d_bn_act(&op.u.conv, s);
-        case VIDC_OP_STEM:
-            if (g.p[4])      // input gathered through the forward warp: p[4] = warp parameter records, f = cx, cy, i[8] = align_corners
-                return vidc_stem_conv3x3s2_warped((const float*)g.p[0], (const float*)g.p[4], (const float*)g.p[1], (float*)g.p[2], g.i[0], g.i[2], g.i[3], g.i[4],
-                                                  g.i[5], g.i[6], const_cast<void*>(g.p[3]), g.i[7], g.f[0], g.f[1], g.i[8], s);
-            return vidc_stem_conv3x3s2((const float*)g.p[0], (const float*)g.p[1], (float*)g.p[2], g.i[0], g.i[1], g.i[2], g.i[3],
-                                       g.i[4], g.i[5], g.i[6], const_cast<void*>(g.p[3]), g.i[7], s);
-        case VIDC_OP_MAXPOOL:
-            return vidc_maxpool3x3s2((const float*)g.p[0], (float*)g.p[1], g.i[0], g.i[1], g.i[2], g.i[3], g.i[4], g.i[5],
-                                     const_cast<void*>(g.p[2]), s);
-        case VIDC_OP_UPSAMPLE:
-            return vidc_upsample_bilinear_ac((const float*)g.p[0], (float*)g.p[1], g.i[0], g.i[1], g.i[2], g.i[3], g.i[4], g.i[5],
-                                             g.i[6], g.i[7], g.i[8], const_cast<void*>(g.p[2]), s);
-        case VIDC_OP_HEAD:
-            return vidc_head_conv1x1_upsample((const float*)g.p[0], (const float*)g.p[1], (const float*)g.p[2], (float*)g.p[3],
-                                              (float*)g.p[4], g.i[0], g.i[1], g.i[2], g.i[3], g.i[4], g.i[5], g.i[6], g.i[7],
-                                              g.i[8], g.i[9], s);
-        case VIDC_OP_WARP_PARAMS:
-            return vidc_warp2dof_params((const float*)g.p[0], (const float*)g.p[1], g.i[0], g.f[0], g.f[1], g.f[2], g.f[3],
-                                        (const float*)g.p[2], g.i[1], g.i[2], (float*)g.p[3], s);
-        case VIDC_OP_WARP_FWD:
-            return vidc_warp2dof_fwd((const float*)g.p[0], (const float*)g.p[1], (float*)g.p[2], g.i[0], g.i[1], g.i[2], g.i[3],
-                                     g.f[0], g.f[1], g.i[4], s);
-        case VIDC_OP_WARP_INV:
-            return vidc_warp2dof_inv_rot_norm((const float*)g.p[0], (const float*)g.p[1], (float*)g.p[2], g.i[0], g.i[1], g.i[2],
-                                              g.f[0], g.f[1], g.i[3], g.i[4], s);
-        case VIDC_OP_SPLIT: {  // p[0] fp32 rows -> p[1] split-bf16 image; i[0..1] = rows (lo, hi), i[2] = C, i[3] = ldx
-            long long rows = (long long)(uint32_t)g.i[0] | ((long long)(uint32_t)g.i[1] << 32);
-            return vidc_split_bf16x3((const float*)g.p[0], const_cast<void*>(g.p[1]), rows, g.i[2], g.i[3], s);
-        }
-        case VIDC_OP_AVGPOOL:   // i = B, H, W, C, ldx, kh, kw, sh, sw, ph, pw, ldy
-            return vidc_avgpool2d((const float*)g.p[0], (float*)g.p[1], g.i[0], g.i[1], g.i[2], g.i[3], g.i[4], g.i[5], g.i[6], g.i[7], g.i[8],
-                                  g.i[9], g.i[10], g.i[11], s);
-        case VIDC_OP_NORMALIZE:   // i = B, C, HW
-            return vidc_normalize_nchw((const float*)g.p[0], (float*)g.p[1], g.i[0], g.i[1], g.i[2], s);
-        case VIDC_OP_DET_IM2COL:   // i = B, H, W, Hp, Wp; f = mean (b, g, r)
-            return vidc_det_stem_im2col((const float*)g.p[0], (float*)g.p[1], g.i[0], g.i[1], g.i[2], g.i[3], g.i[4], g.f[0], g.f[1], g.f[2], s);
-        case VIDC_OP_NEAREST2X:    // i = B, h, w, C, ldx, ldy
-            return vidc_upsample_nearest2x((const float*)g.p[0], (float*)g.p[1], g.i[0], g.i[1], g.i[2], g.i[3], g.i[4], g.i[5], s);
-        case VIDC_OP_MASK:
-            return vidc_mask_scale((const float*)g.p[0], (const float*)g.p[1], (float*)g.p[2], g.i[0], g.i[1], g.i[2], g.i[3], g.i[4], g.i[5], g.i[6], g.i[7], s);
-        case VIDC_OP_WINO_IN:
-            return vidc_winograd_input_transform((const float*)g.p[0], const_cast<void*>(g.p[1]), g.i[0], g.i[1], g.i[2], g.i[3], g.i[4], g.i[5], g.i[6],
-                                                 g.i[7], g.i[8], s);
-        case VIDC_OP_WINO_OUT:
-            return vidc_winograd_output_transform((const float*)g.p[0], (float*)g.p[1], const_cast<void*>(g.p[2]), (const float*)g.p[3],
-                                                  (const float*)g.p[4], (const float*)g.p[5], (const float*)g.p[6], g.i[0], g.i[1], g.i[2], g.i[3],
-                                                  g.i[4], g.i[5], g.i[6], g.i[7], g.i[8], s);
-        case VIDC_OP_QUANT: {  // p[0] fp32 rows -> p[1] MXFP8 image; i[0..1] = rows (lo, hi), i[2] = C, i[3] = ldx, i[4] = groups
-            long long rows = (long long)(uint32_t)g.i[0] | ((long long)(uint32_t)g.i[1] << 32);
-            return vidc_quant_mxfp8((const float*)g.p[0], const_cast<void*>(g.p[1]), rows, g.i[2], g.i[3], g.i[4], s);
-        }
-        case VIDC_OP_CAST: {   // p[0] fp32 rows -> p[1] dense bf16 rows; i[0..1] = rows (lo, hi), i[2] = C, i[3] = ldx
-            long long rows = (long long)(uint32_t)g.i[0] | ((long long)(uint32_t)g.i[1] << 32);
-            return vidc_cast_bf16((const float*)g.p[0], const_cast<void*>(g.p[1]), rows, g.i[2], g.i[3], s);
-        }
-        case VIDC_OP_COPY: {   // p[0] -> p[1], i[0..1] = byte count (lo, hi)
-            size_t bytes = (size_t)(uint32_t)g.i[0] | ((size_t)(uint32_t)g.i[1] << 32);
-            VIDC_HIP(hipMemcpyAsync(const_cast<void*>(g.p[1]), g.p[0], bytes, hipMemcpyDeviceToDevice, st));
-            return VIDC_OK;
-        }
-        default:
-            vidc::set_error("program: unknown op kind %d", op.kind);
-            return VIDC_ERR_SHAPE;
+    if (op.kind == VIDC_OP_CONV) return vidc_conv2d_bn_act(&op.u.conv, s);
+    const OpRow* row = op_row(op.kind);
+    if (!row) {
+        vidc::set_error("program: unknown op kind %d", op.kind);
+        return VIDC_ERR_SHAPE;
     }
+    return row->call(op.u.g, s);
 }
 
 // Issues every op; ops with stream_id k>0 go to the program's side stream k.  Dependencies across stream ids are
@@ -129,6 +166,15 @@ int issue(vidc_program* p, hipStream_t main, bool timing, size_t begin = 0, size
 }
 
 }  // namespace
+
+extern "C" int vidc_op_info(int kind, vidc_op_entry* out) {
+    VIDC_REQUIRE(out, VIDC_ERR_NULL, "vidc_op_info: null pointer");
+    const OpRow* row = op_row(kind);
+    VIDC_REQUIRE(row, VIDC_ERR_SHAPE, "vidc_op_info: unknown op kind %d", kind);
+    out->name = row->name;
+    out->classes = row->classes;
+    return VIDC_OK;
+}
 
 extern "C" int vidc_program_create(const vidc_op* ops, int n_ops, vidc_program** out) {
     VIDC_REQUIRE(ops && out, VIDC_ERR_NULL, "vidc_program_create: null pointer");

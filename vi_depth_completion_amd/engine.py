@@ -319,13 +319,6 @@ OP_KINDS = dict({"conv": L.OP_CONV, "stem": L.OP_STEM, "maxpool": L.OP_MAXPOOL, 
 MODE_LAYERS = {"mxfp8": (mxfp8_layer, L.PREC_MXFP8), "bf16": (bf16_layer, L.PREC_BF16)}
 
 
-def _args(g, p=(), i=(), f=()):
-    """Fills the leading pointer / int / float arguments of a generic op (vidc_generic_args); the rest stay zero."""
-    for arr, vals in ((g.p, p), (g.i, i), (g.f, f)):
-        for j, v in enumerate(vals):
-            arr[j] = v
-
-
 class Program:
     """Records ops symbolically (buffers are integers), then `finalize()` plans memory and builds the C program."""
 
@@ -873,107 +866,111 @@ class Program:
                 free.append((storage[b].numel(), storage[b]))
         return storage
 
-    # ---- lowering: _lower_<kind>(g, kw) fills the generic arguments g of the recorded op kw and returns its display name ---------------
+    # ---- lowering: _lower_<kind>(kw) returns the display name of the recorded op kw and the arguments of its entry point in the header's
+    # declaration order, without the stream (L.pack_op puts them into slots) -- and the vidc_op_kind where it is not OP_KINDS[kind].
+    # The lowerers of the ops that Program.variant_ops restricts take a window (g_lo, g_hi) of the groups of a grouped tensor: group g sits
+    # at channel g * (channels per group) of every row, so a window moves the base addresses and shrinks the channel count.
     def _addr(self, t, extra=0):
         """Device address of the program tensor t (+ `extra` of its channels); 0 for no tensor."""
         return 0 if t is None else self.storage[t.buf].data_ptr() + t.esz * (t.ch_off + extra)
 
-    def _lower_image(self, g, kw, fmt):
+    def _lower(self, op, kind, kw, window=None):
+        """Packs the recorded non-conv op kw into op.kind / op.u.g and returns its display name."""
+        if kind in IMAGE_FORMATS:
+            lowered = self._lower_image(kw, IMAGE_FORMATS[kind])
+        else:
+            lowered = getattr(self, "_lower_" + kind)(kw, *(() if window is None else (window,)))
+        L.pack_op(op, lowered[2] if len(lowered) > 2 else OP_KINDS[kind], lowered[1])
+        return lowered[0]
+
+    def _lower_image(self, kw, fmt):
         """split / quant / cast: 64-bit row count, the channels of a row, the row stride of x, and the groups of a format that keeps them as planes."""
         x = kw["x"]
         rows, dims = x.B * x.H * x.W, ((x.C * x.G,) if fmt.folded else (x.C, x.G))
-        _args(g, (self._addr(x), self._addr(kw["y"])), (rows & 0xFFFFFFFF, rows >> 32, dims[0], x.ld) + dims[1:])
-        return "%s:%s" % (fmt.kind, "x".join("%d" % v for v in (rows,) + dims))
+        return "%s:%s" % (fmt.kind, "x".join("%d" % v for v in (rows,) + dims)), (self._addr(x), self._addr(kw["y"]), rows, dims[0], x.ld) + dims[1:]
 
-    def _lower_stem(self, g, kw):
+    def _lower_stem(self, kw):
         x, y, wf = kw["x"], kw["y"], kw.get("warp")
         w = self.ws.raw(kw["key"] + ".weight").contiguous()
         self._keep.append(w)
-        _args(g, (self._addr(x), w.data_ptr(), 0 if kw.get("no_f32") else self._addr(y, kw["g"] * y.C), self._addr(kw.get("split_out"))),
-              (x.B, x.C, x.H, x.W, y.C, y.ld, int(kw["relu"]), kw["g"] * y.C))
-        if wf is not None:             # the input is gathered through the forward warp: x = the unwarped image, p[4] = the parameter records
-            g.p[0], g.p[4] = self._addr(wf["x"]), self._addr(wf["p"])
-            g.f[0], g.f[1], g.i[8] = wf["intr"].cx, wf["intr"].cy, wf["ac"]
-        return "stem:" + kw["key"] + ("+warp" if wf is not None else "")
+        out = (0 if kw.get("no_f32") else self._addr(y, kw["g"] * y.C), x.B, x.C, x.H, x.W, y.C, y.ld, int(kw["relu"]), self._addr(kw.get("split_out")), kw["g"] * y.C)
+        if wf is None:
+            return "stem:" + kw["key"], (self._addr(x), w.data_ptr()) + out
+        # the input is gathered through the forward warp: the unwarped image and the parameter records in place of x; three channels, so no Cin
+        return ("stem:" + kw["key"] + "+warp", (self._addr(wf["x"]), self._addr(wf["p"]), w.data_ptr(), out[0], out[1]) + out[3:] +
+                (wf["intr"].cx, wf["intr"].cy, wf["ac"]), L.OP_STEM_WARPED)
 
-    def _lower_maxpool(self, g, kw):
+    def _lower_maxpool(self, kw, window=None):
         x, y = kw["x"], kw["y"]
-        _args(g, (self._addr(x), 0 if kw.get("no_f32") else self._addr(y), self._addr(kw.get("split_out"))), (x.B, x.H, x.W, x.C * x.G, x.ld, y.ld))
-        return "maxpool"
+        g_lo, g_hi = window or (0, x.G)
+        return "maxpool", (self._addr(x, g_lo * x.C), 0 if kw.get("no_f32") else self._addr(y, g_lo * x.C), x.B, x.H, x.W, x.C * (g_hi - g_lo), x.ld, y.ld,
+                           self._addr(kw.get("split_out"), g_lo * x.C))
 
-    def _lower_upsample(self, g, kw):
+    def _lower_upsample(self, kw):
         x, y = kw["x"], kw["y"]
-        _args(g, (self._addr(x), self._addr(y), self._addr(kw.get("split_out"))),
-              (x.B, x.H, x.W, (x.C if kw.get("sum_groups") else x.C * x.G), x.ld, y.H, y.W, y.ld, kw["flags"]))
-        return "upsample:%dx%dx%d->%dx%d" % (x.H, x.W, x.C * x.G, y.H, y.W)
+        return "upsample:%dx%dx%d->%dx%d" % (x.H, x.W, x.C * x.G, y.H, y.W), (
+            self._addr(x), self._addr(y), x.B, x.H, x.W, (x.C if kw.get("sum_groups") else x.C * x.G), x.ld, y.H, y.W, y.ld, kw["flags"], self._addr(kw.get("split_out")))
 
-    def _lower_head(self, g, kw):
+    def _lower_head(self, kw):
         x, low, y = kw["x"], kw["low"], kw["y"]
         w = self.ws.raw(kw["key"] + ".weight").reshape(y.C, -1).contiguous()
         b = self.ws.raw(kw["key"] + ".bias").contiguous()
         self._keep += [w, b]
-        _args(g, (self._addr(x), w.data_ptr(), b.data_ptr(), self._addr(low), self._addr(y)),
-              (x.B, x.H, x.W, x.C * x.G, x.ld, y.C, kw["pad"], y.H, y.W, int(kw["relu"])))
-        return "head:" + kw["key"]
+        return "head:" + kw["key"], (self._addr(x), w.data_ptr(), b.data_ptr(), self._addr(low), self._addr(y),
+                                     x.B, x.H, x.W, x.C * x.G, x.ld, y.C, kw["pad"], y.H, y.W, int(kw["relu"]))
 
-    def _lower_warp_params(self, g, kw):
+    def _lower_warp_params(self, kw):
         it = kw["intr"]
-        _args(g, [self._addr(kw[k]) for k in ("g", "a", "kinv", "p")], (self.B, it.W, it.H), (it.fx, it.fy, it.cx, it.cy))
-        return "warp_params"
+        return "warp_params", (self._addr(kw["g"]), self._addr(kw["a"]), self.B, it.fx, it.fy, it.cx, it.cy, self._addr(kw["kinv"]), it.W, it.H, self._addr(kw["p"]))
 
-    def _lower_warp_fwd(self, g, kw):
+    def _lower_warp_fwd(self, kw):
         x, it = kw["x"], kw["intr"]
-        _args(g, (self._addr(x), self._addr(kw["p"]), self._addr(kw["y"])), (x.B, x.C, x.H, x.W, kw["ac"]), (it.cx, it.cy))
-        return "warp_fwd"
+        return "warp_fwd", (self._addr(x), self._addr(kw["p"]), self._addr(kw["y"]), x.B, x.C, x.H, x.W, it.cx, it.cy, kw["ac"])
 
-    def _lower_warp_inv(self, g, kw):
+    def _lower_warp_inv(self, kw):
         x, it = kw["x"], kw["intr"]
-        _args(g, (self._addr(x), self._addr(kw["p"]), self._addr(kw["y"])), (x.B, x.H, x.W, kw["ac"], kw["norm"]), (it.cx, it.cy))
-        return "warp_inv_rot_norm"
+        return "warp_inv_rot_norm", (self._addr(x), self._addr(kw["p"]), self._addr(kw["y"]), x.B, x.H, x.W, it.cx, it.cy, kw["ac"], kw["norm"])
 
-    def _lower_avgpool(self, g, kw):
+    def _lower_avgpool(self, kw):
         x, y = kw["x"], kw["y"]
-        _args(g, (self._addr(x), self._addr(y)), (x.B, x.H, x.W, x.C * x.G, x.ld) + tuple(kw["geom"]) + (y.ld,))
-        return "avgpool"
+        return "avgpool", (self._addr(x), self._addr(y), x.B, x.H, x.W, x.C * x.G, x.ld) + tuple(kw["geom"]) + (y.ld,)
 
-    def _lower_normalize(self, g, kw):
+    def _lower_normalize(self, kw):
         x = kw["x"]
-        _args(g, (self._addr(x), self._addr(kw["y"])), (x.B, x.C, x.H * x.W))
-        return "normalize"
+        return "normalize", (self._addr(x), self._addr(kw["y"]), x.B, x.C, x.H * x.W)
 
-    def _lower_det_im2col(self, g, kw):
-        _args(g, (self._addr(kw["x"]), self._addr(kw["y"])), (kw["x"].B,) + tuple(kw["geom"]), kw["mean"])
-        return "det_im2col"
+    def _lower_det_im2col(self, kw):
+        return "det_im2col", (self._addr(kw["x"]), self._addr(kw["y"]), kw["x"].B) + tuple(kw["geom"]) + tuple(kw["mean"])
 
-    def _lower_mask(self, g, kw):
+    def _lower_mask(self, kw):
         x, y, im = kw["x"], kw["y"], kw["image"]
-        _args(g, (self._addr(x), self._addr(im), self._addr(y)), (x.B, x.H, x.W, x.C * x.G, x.ld, y.ld, im.H, im.W))
-        return "mask_scale"
+        return "mask_scale", (self._addr(x), self._addr(im), self._addr(y), x.B, x.H, x.W, x.C * x.G, x.ld, y.ld, im.H, im.W)
 
-    def _lower_wino_in(self, g, kw):
-        x, v = kw["x"], kw["v"]
-        _args(g, (self._addr(x), self._addr(v)), (x.B, x.H, x.W, x.C * x.G, x.ld, kw["cin"], kw["m"], kw["split"], v.ld))
-        return "wino_in:F%d:%dx%dx%d" % (kw["m"], x.H, x.W, x.C * x.G)
+    def _lower_wino_in(self, kw, window=None):
+        x, v, cin, a2 = kw["x"], kw["v"], kw["cin"], (kw["m"] + 2) ** 2      # V rows: [group][position][cin] (row stride explicit)
+        g_lo, C = (0, x.C * x.G) if window is None else (window[0], cin * (window[1] - window[0]))
+        return "wino_in:F%d:%dx%dx%d" % (kw["m"], x.H, x.W, x.C * x.G), (
+            self._addr(x, g_lo * cin), self._addr(v, g_lo * a2 * cin), x.B, x.H, x.W, C, x.ld, cin, kw["m"], kw["split"], v.ld)
 
-    def _lower_wino_out(self, g, kw):
-        mm, y, keys = kw["mm"], kw["y"], kw["keys"]
+    def _lower_wino_out(self, kw, window=None):
+        mm, y, keys, co, a2 = kw["mm"], kw["y"], kw["keys"], kw["cout"], (kw["m"] + 2) ** 2
         s1, b1 = self.ws.affine(list(keys), list(kw["bn"]) if kw["bn"] is not None else None)
         s2, b2 = self.ws.affine([None] * len(keys), list(kw["bn2"])) if kw["bn2"] is not None else (None, None)
-        self._keep += [t for t in (s1, b1, s2, b2) if t is not None]
-        _args(g, (self._addr(mm), 0 if kw["flags"] & L.NO_F32_OUT else self._addr(y), self._addr(kw.get("split_out")), s1.data_ptr(), b1.data_ptr(),
-                  L.ptr(s2) or 0, L.ptr(b2) or 0), (y.B, y.H, y.W, y.C * y.G, kw["cout"], y.ld, kw["m"], kw["flags"], mm.ld))
-        return "wino_out:F%d:%dx%dx%d" % (kw["m"], y.H, y.W, y.C * y.G)
+        if window is None:
+            self._keep += [t for t in (s1, b1, s2, b2) if t is not None]
+        g_lo, C = (0, y.C * y.G) if window is None else (window[0], co * (window[1] - window[0]))
+        # M rows: [group][position][cout]; y, its split image and the scale / shift arrays: group g at element g * cout
+        return "wino_out:F%d:%dx%dx%d" % (kw["m"], y.H, y.W, y.C * y.G), (
+            self._addr(mm, g_lo * a2 * co), 0 if kw["flags"] & L.NO_F32_OUT else self._addr(y, g_lo * co), self._addr(kw.get("split_out"), g_lo * co)) + tuple(
+            0 if t is None else t.data_ptr() + 4 * g_lo * co for t in (s1, b1, s2, b2)) + (y.B, y.H, y.W, C, co, y.ld, kw["m"], kw["flags"], mm.ld)
 
-    def _lower_nearest2x(self, g, kw):
+    def _lower_nearest2x(self, kw):
         x, y = kw["x"], kw["y"]
-        _args(g, (self._addr(x), self._addr(y)), (x.B, x.H, x.W, x.C * x.G, x.ld, y.ld))
-        return "nearest2x"
+        return "nearest2x", (self._addr(x), self._addr(y), x.B, x.H, x.W, x.C * x.G, x.ld, y.ld)
 
-    def _lower_copy(self, g, kw):
+    def _lower_copy(self, kw):
         src, dst = kw["src"], kw["dst"]
-        nbytes = min(self.buf_elems[src.buf], self.buf_elems[dst.buf]) * 4
-        _args(g, (self._addr(src), self._addr(dst)), (nbytes & 0xFFFFFFFF, nbytes >> 32))
-        return "copy"
+        return "copy", (self._addr(src), self._addr(dst), min(self.buf_elems[src.buf], self.buf_elems[dst.buf]) * 4)
 
     def finalize(self, dry_run=False):
         """Plans buffers and builds the C op array.  dry_run=True stops before any HIP call (host-logic tests on CPU)."""
@@ -995,17 +992,16 @@ class Program:
         for op, (kind, _r, _w, kw) in zip(ops, self.ops):
             if kind not in OP_KINDS:
                 raise ValueError(kind)
-            op.kind, op.stream_id, op.wait_mask = OP_KINDS[kind], kw["stream_id"], kw["wait_mask"]
+            op.stream_id, op.wait_mask = kw["stream_id"], kw["wait_mask"]
             if kind == "conv":
+                op.kind = L.OP_CONV
                 op.u.conv, name = self._conv_desc(kw, dry_run)
                 need = lib.vidc_conv2d_workspace_bytes(C.byref(op.u.conv))
                 if need:
                     ws_need[op.stream_id] = max(ws_need.get(op.stream_id, 0), need)
                     ws_ops.append(op)
-            elif kind in IMAGE_FORMATS:
-                name = self._lower_image(op.u.g, kw, IMAGE_FORMATS[kind])
             else:
-                name = getattr(self, "_lower_" + kind)(op.u.g, kw)
+                name = self._lower(op, kind, kw)
             self.op_names.append(name)
         # split-K workspaces (one per stream id so concurrent convs never share partials); zeroed once: their heads hold the
         # per-tile ticket counters of the fused split-K reduction, which every launch leaves at zero (include/vidc.h)
@@ -1073,24 +1069,39 @@ class Program:
         (csrc/conv_mfma.hip: `a.x + g * a.x_gs` ...), while tile, split-K partition and K order -- which fix the fp32 summation order --
         are copied from the grouped launch.  So a frame's result is bit-identical whichever variant computed its pyramids
         (tests/test_hip_parity.py::test_run_interleaved_lanes_are_bit_identical)."""
-        assert self.handle is not None and 0 <= g_lo < g_hi <= groups
+        assert self.handle is not None
+        ops, picked = self.variant_ops(segment, g_lo, g_hi, groups, keep_ungrouped)
+        h = C.c_void_p()
+        L.check(L.lib().vidc_program_create(ops, len(ops), C.byref(h)), "program_create (variant)")
+        self._variants = getattr(self, "_variants", {})
+        self._variants[name] = {"handle": h, "ops": ops, "captured": False, "indices": picked}
+        return self._variants[name]
+
+    def variant_ops(self, segment, g_lo, g_hi, groups, keep_ungrouped):
+        """(the op array of group_variant's program, the indices of the ops of this program it was made from): needs a finalized program,
+        dry-run included."""
+        assert 0 <= g_lo < g_hi <= groups
         b, e = self.segments()[segment]
         picked = []
+
+        def grouped(kind, kw):
+            return (kind in ("conv", "wino_out") and len(kw["keys"]) == groups) or (kind in ("maxpool", "wino_in") and kw["x"].G == groups)
         for i in range(b, e):
             kind, _r, _w, kw = self.ops[i]
             if kind == "stem":
                 if g_lo <= kw["g"] < g_hi:
                     picked.append(i)
                 continue
-            grouped = (kind in ("conv", "wino_out") and len(kw["keys"]) == groups) or (kind in ("maxpool", "wino_in") and kw["x"].G == groups)
             # (a split launch of its own -- VIDC_FUSE_SPLIT=0 -- over a grouped tensor has no row stride for its image: it runs whole in every variant)
-            if grouped or keep_ungrouped or (kind in IMAGE_FORMATS and kw["x"].G == groups):
+            if grouped(kind, kw) or keep_ungrouped or (kind in IMAGE_FORMATS and kw["x"].G == groups):
                 picked.append(i)
         ops = (L.Op * len(picked))()
         for j, i in enumerate(picked):
             C.memmove(C.byref(ops[j]), C.byref(self.c_ops[i]), C.sizeof(L.Op))
             kind, _r, _w, kw = self.ops[i]
-            if kind == "conv" and len(kw["keys"]) == groups:
+            if not grouped(kind, kw):
+                continue
+            if kind == "conv":
                 d = ops[j].u.conv
                 a2 = (kw["wino"] + 2) ** 2 if kw.get("wino") else 1        # Winograd GEMMs: (m+2)^2 launch groups per group of the layer
                 strides = [("x", d.x_gs, 4), ("w", d.w_gs, 4), ("y", d.y_gs, 4), ("scale1", d.p_gs, 4), ("shift1", d.p_gs, 4), ("scale2", d.p_gs, 4),
@@ -1101,31 +1112,9 @@ class Program:
                     if v:
                         setattr(d, field, v + esz * g_lo * gs * a2)
                 d.groups = (g_hi - g_lo) * a2
-            elif kind == "wino_in" and kw["x"].G == groups:        # x: group at channel g * cin; V rows: [gg][pos][cin] (row stride explicit)
-                g = ops[j].u.g
-                cin, a2 = kw["cin"], (kw["m"] + 2) ** 2
-                g.p[0], g.p[1] = g.p[0] + 4 * g_lo * cin, g.p[1] + 4 * g_lo * a2 * cin
-                g.i[3] = cin * (g_hi - g_lo)
-            elif kind == "wino_out" and len(kw["keys"]) == groups:
-                g = ops[j].u.g
-                co, a2 = kw["cout"], (kw["m"] + 2) ** 2
-                g.p[0] = g.p[0] + 4 * g_lo * a2 * co
-                for k in (1, 2, 3, 4, 5, 6):                       # y, split image, scale / shift arrays: group g at element g * cout
-                    if g.p[k]:
-                        g.p[k] = g.p[k] + 4 * g_lo * co
-                g.i[3] = co * (g_hi - g_lo)
-            elif kind == "maxpool" and kw["x"].G == groups:
-                g = ops[j].u.g
-                cg = kw["x"].C
-                for k in range(3):                            # x, y, split image: group g sits at channel offset g * C of every pixel row
-                    if g.p[k]:
-                        g.p[k] = g.p[k] + 4 * g_lo * cg
-                g.i[3] = cg * (g_hi - g_lo)
-        h = C.c_void_p()
-        L.check(L.lib().vidc_program_create(ops, len(ops), C.byref(h)), "program_create (variant)")
-        self._variants = getattr(self, "_variants", {})
-        self._variants[name] = {"handle": h, "ops": ops, "captured": False, "indices": picked}
-        return self._variants[name]
+            else:                # max-pool, wino_in, wino_out: lowered again with the window (stream id and wait mask are the copied ones)
+                self._lower(ops[j], kind, kw, (g_lo, g_hi))
+        return ops, picked
 
     def has_variant(self, name):
         return name in getattr(self, "_variants", {})
