@@ -854,7 +854,8 @@ int vidc_wgrad_permute(const float* tmp, float* dw_oihw, int Cout, int Cin, int 
 /* The epilogue of vidc_conv2d_bn_act, y = relu?(c * scale + shift) on NHWC rows, transposed in one pass (Conv2d + eval BatchNorm2d + ReLU
  * differentiated behind the raw conv output c): dc = mask(dy) * scale, dshift[ch] = sum mask(dy), dscale[ch] = sum mask(dy) * c with
  * c = (y - shift) / scale; channels with scale == 0 read c from c_raw (row stride |ldc|; may be NULL when there is no such channel),
- * and with ldc < 0 every channel does (for a forward whose y is not an fp32-accurate image of c: bf16x3, Winograd).
+ * and with ldc < 0 every channel does (for a forward whose y is not an fp32-accurate image of c: bf16x3, Winograd).  When c_raw is given,
+ * the channels with |shift| > 4 |scale| read it as well: there the quotient loses c to the rounding of y (csrc/train.hip).
  * Sums: fp64 chunk partials reduced in a fixed order.  scratch: vidc_train_scratch_bytes(M, C).  dy, y, dc 16-byte aligned. */
 int vidc_affine_act_backward(const float* dy, const float* y, const float* c_raw, const float* scale, const float* shift, float* dc,
                              float* dscale, float* dshift, long long M, int C, int lddy, int ldy, int ldc, int lddc, int relu, void* scratch,

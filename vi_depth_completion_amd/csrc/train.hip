@@ -1680,7 +1680,15 @@ namespace {
 // of dgrad and wgrad) and the chunk sums of mask(dy) and mask(dy) * c in fp64, c = (y - shift) / scale -- where the mask is open y determines c,
 // where it is closed the term is zero.  A channel with scale == 0 reads c from `craw` (the conv re-run with an identity epilogue; the caller
 // passes it only when such a channel exists), with all_raw every channel does (a forward whose y is not an fp32-accurate image of c).
+// So does, when craw is given, an ill-conditioned channel: |shift| > kAffineIllCond * |scale|.  y = fl(c * scale + shift) carries an absolute
+// error of up to u * max(|c * scale|, |shift|), so the quotient returns c with an error of up to ~u * (|c| + |shift / scale|): at most
+// u * (|c| + kAffineIllCond) where the rule reconstructs -- for a conv output of the order of 1 that is below the rounding the fp32 conv
+// itself leaves in c (the rule reads scale and shift alone and so assumes that order) -- and without bound where it does not (scale 2^-10,
+// shift 1: dscale off by 1e-5 of its size; scale 1e-30: y == shift in every row and dscale == 0).  The threshold is a power of two, so
+// kAffineIllCond * |scale| is the same fp32 value on the host (torch_ops._conv_backward_body decides there whether the conv is re-run) and
+// here, and a channel the rule keeps is computed exactly as in a call without craw: same bits.
 // Block / grid / summation order: chan_partial_kernel's.
+constexpr float kAffineIllCond = 4.f;       // torch_ops.AFFINE_ILL_COND
 __global__ void __launch_bounds__(TT)
 affine_act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ craw, const float* __restrict__ scale,
                       const float* __restrict__ shift, float* __restrict__ dc, long long M, int C, int lddy, int ldy, int ldc, int lddc, int relu,
@@ -1692,8 +1700,13 @@ affine_act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
     double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
     if (c < C) {
         float sc[4], sh[4];
+        bool raw[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { sc[k] = scale[c + k]; sh[k] = shift[c + k]; }
+        for (int k = 0; k < 4; ++k) {
+            sc[k] = scale[c + k];
+            sh[k] = shift[c + k];
+            raw[k] = all_raw || sc[k] == 0.f || (craw && fabsf(sh[k]) > kAffineIllCond * fabsf(sc[k]));
+        }
         for (long long r = r0 + rl; r < r1; r += 16) {
             const float4 gv = *reinterpret_cast<const float4*>(dy + r * lddy + c);
             const float4 yv4 = *reinterpret_cast<const float4*>(y + r * ldy + c);
@@ -1704,7 +1717,7 @@ affine_act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
             for (int k = 0; k < 4; ++k) {
                 if (relu && !(yv[k] > 0.f)) g[k] = 0.f;
                 float cv;
-                if (sc[k] != 0.f && !all_raw) cv = (yv[k] - sh[k]) / sc[k];
+                if (!raw[k]) cv = (yv[k] - sh[k]) / sc[k];
                 else cv = craw ? craw[r * ldc + c + k] : 0.f;
                 s0[k] += (double)g[k];
                 s1[k] += (double)g[k] * (double)cv;

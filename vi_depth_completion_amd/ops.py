@@ -385,7 +385,8 @@ def warp2dof_inv_rot_norm_backward(x, dz, params, cx, cy, align_corners, normali
 
 def affine_act_backward(dy, y, scale, shift, relu, c_raw=None, all_from_raw=False):
     """The conv epilogue y = relu?(c * scale + shift) transposed: (dc, dscale, dshift) from NHWC dy, y (vidc_affine_act_backward).  c_raw: the raw
-    conv output, read for the channels whose scale is 0 -- or, with all_from_raw, for every channel (ldc < 0 in the C call)."""
+    conv output, read for the channels whose scale is 0 or whose |shift| > 4 |scale| (torch_ops.affine_reads_raw) -- or, with all_from_raw, for
+    every channel (ldc < 0 in the C call)."""
     _dev(dy, y, scale, shift, c_raw)
     dy, y = dy.contiguous().float(), y.contiguous()
     Cc = y.shape[-1]

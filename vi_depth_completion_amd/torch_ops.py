@@ -397,12 +397,22 @@ def _warp_inv_backward(ctx, _grad_h, grad_z):
 torch.library.register_autograd("vidc::warp2dof_inv_rot_norm", _warp_inv_backward, setup_context=_warp_inv_setup)
 
 
+AFFINE_ILL_COND = 4.0       # kAffineIllCond of csrc/train.hip: a power of two, so the product below is exact in fp32 on either side
+
+
+def affine_reads_raw(scale, shift):
+    """Per channel: does vidc_affine_act_backward, given c_raw, read c from it instead of rebuilding it as (y - shift) / scale?  The kernel
+    evaluates the same fp32 expression (affine_act_bwd_kernel); conv2d_bn_act_backward states the rule."""
+    scale, shift = scale.float(), shift.float()
+    return (scale == 0) | (shift.abs() > AFFINE_ILL_COND * scale.abs())
+
+
 def _conv_backward_body(what, dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, stride, pad, dilation, relu, precision, need_x, need_w, need_affine,
                         recompute_c):
     """conv2d_bn_act_backward and conv2d_dilated_bn_act_backward (documented there)."""
     dil = {} if dilation == 1 else {"dilation": dilation}
     c_raw = None
-    if need_affine and (recompute_c or bool((scale == 0).any())):
+    if need_affine and (recompute_c or bool(affine_reads_raw(scale, shift).any())):
         if x_nhwc is None:
             raise RuntimeError("%s: dscale of this conv needs the conv's input" % what)
         c_raw = _ops.conv2d_bn_act(x_nhwc, _ops.pack_conv_weight(w_oihw), torch.ones_like(scale), torch.zeros_like(shift), w_oihw.shape[2],
@@ -434,6 +444,12 @@ def conv2d_bn_act_backward(dy: torch.Tensor, x_nhwc: Optional[torch.Tensor], w_o
     at precision 1 is granted 10 x fp32 and keeps the faster arithmetic.  dscale sums mask(dy) * c with c = (y - shift) / scale; with
     recompute_c (the forward ran in bf16x3 or as Winograd, whose y is not an fp32-accurate image of c), and for channels whose scale is 0, c
     is read from a re-run of the conv in the direct fp32 form with an identity epilogue, so that dscale is an fp32 result like dw and dshift.
+    The same holds for an ill-conditioned channel, |shift| > AFFINE_ILL_COND * |scale| (affine_reads_raw; a folded BatchNorm with a small
+    gamma / sigma makes such channels): y = fl(c * scale + shift) is exact to u * max(|c * scale|, |shift|) only, so the quotient gives c to
+    u * (|c| + |shift / scale|) -- at most u * (|c| + AFFINE_ILL_COND) where the rule keeps the quotient, which for a conv output of the order
+    of 1 is less than the fp32 conv's own rounding of c, and nothing where it does not (scale 1e-30, shift 1: y == shift, c == 0).  The rule
+    is evaluated here, on the host, from scale and shift alone (it assumes that order of c); the conv is re-run only if it names a channel,
+    and the kernel applies the same fp32 comparison per channel, so the channels it keeps have the bits of a call without the re-run.
     x_nhwc is read by dw and by that re-run."""
     return _conv_backward_body("conv2d_bn_act_backward", dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, stride, pad, 1, relu, precision, need_x, need_w,
                                need_affine, recompute_c)
