@@ -87,8 +87,35 @@ int vidc_warp2dof_fwd_backward(const float* dy, const float* params, float* dx, 
 int vidc_warp2dof_inv_rot_norm_backward(const float* x, const float* dz, const float* params, float* dx, int B, int H, int W,
                                         float cx, float cy, int align_corners, int normalize, vidc_stream_t stream);
 
+/* The interpolation modes of the forward warp (the `interp_mode` the reference hands to F.grid_sample, :152, :286). */
+#define VIDC_WARP_BILINEAR 0
+#define VIDC_WARP_NEAREST 1
+#define VIDC_WARP_BICUBIC 2
+
+/* warp_with_gravity_center_aligned (:108-156) with interp_mode 'bilinear' / 'nearest' / 'bicubic' (mode 0 / 1 / 2), and with rotate != 0
+ * warp_normal_image_with_gravity_center_aligned (:258-290): C == 3 and z = Cg_R_C y per pixel (:288) in the same store pass.  The sampling
+ * position is vidc_warp2dof_fwd's; zero padding.  Nearest reads the pixel at (rint ix, rint iy), ties to even as torch's nearbyint; bicubic
+ * is torch's grid_sampler_2d: A = -0.75, taps floor(ix) - 1 .. floor(ix) + 2 bounds-checked one by one, no coordinate clamping, the rows
+ * summed one fmaf chain each and then the four row sums.  mode 0 without rotate gives the bits of vidc_warp2dof_fwd.
+ * x, y: NCHW [B][C][H][W]; `params`: the record of vidc_warp2dof_params (warp_with_homography, :292-310, runs mode 0 on a record the host
+ * builds from the given homography). */
+int vidc_warp2dof_fwd_mode(const float* x, const float* params, float* y, int B, int C, int H, int W, float cx, float cy,
+                           int align_corners, int mode, int rotate, vidc_stream_t stream);
+/* dx of vidc_warp2dof_fwd_mode (:108-156 / :258-290 differentiated w.r.t. the image): with rotate dy is first multiplied by Cg_R_C^T, then
+ * the transposed gather in the form of vidc_warp2dof_fwd_backward -- a thread owns a source pixel and walks the window of output pixels that
+ * its support (one pixel either way for bilinear and nearest, two for bicubic) maps to, with the forward's own weights, in row-major order:
+ * no atomics, bit-identical from run to run.  mode 0 without rotate gives the bits of vidc_warp2dof_fwd_backward. */
+int vidc_warp2dof_fwd_mode_backward(const float* dy, const float* params, float* dx, int B, int C, int H, int W, float cx, float cy,
+                                    int align_corners, int mode, int rotate, vidc_stream_t stream);
+/* image_sampler_forward_inverse (:158-214) in one launch: grid / inv_grid (B,H,W,2) are the normalised sampling coordinates of the forward
+ * warp (:196-202) and of the inverse warp (:204-211) -- the expressions, and so the bits, that the gather kernels sample at -- and c_r_cg
+ * (B,3,3) is Cg_R_C^T.  A sample whose projected corner box has w_max / h_max below 0.8 or above 2.2 (:178-187; recomputed from the
+ * record's Cg_H_C) gets the identity grids 1/(W/2) (X - cx), 1/(H/2) (Y - cy) in both outputs and the identity matrix. */
+int vidc_warp2dof_grids(const float* params, float* grid, float* inv_grid, float* c_r_cg, int B, int H, int W, float cx, float cy,
+                        vidc_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
- * conv + BN + ReLU stacks           (networks/surface_normal.py:10-145, networks/depth_completion.py:16-147)
+ * conv + BN + ReLU stacks          (networks/surface_normal.py:10-145, networks/depth_completion.py:16-147)
  * ---------------------------------------------------------------------------------------------- */
 
 /* OIHW -> packed [Cout][Cin/32][KH][KW][32] (K-contiguous rows for the implicit GEMM; channel-unit major, tap minor so

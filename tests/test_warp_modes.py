@@ -1,0 +1,434 @@
+"""Warping2DOFAlignment beyond the bilinear warp (csrc/warp.hip: vidc_warp2dof_fwd_mode, its backward, vidc_warp2dof_grids): nearest and
+bicubic interpolation, the sampler grids with the "give up" rule, the rotated forward warp, warp_with_homography, and the adjoints.
+
+Two geometries -- small (40 x 30: four full 256-pixel blocks and a tail) and native (320 x 240) --, both grid_sample conventions, alignment
+(0, 1, 0) and the gravities of GRAVITY in batches of three and one, images uniform in [0, 1) with 1, 3 and 5 channels.
+
+Geometry and interpolation are held apart.  Geometry: the grids of vidc_warp2dof_grids against the oracle's, in pixels.  Interpolation: the
+kernels against F.grid_sample on the CPU THROUGH THE DEVICE'S OWN GRID, which the gather kernels sample at bit for bit.  Bars:
+  * nearest: equal bits, except where the position is within 1e-3 px of a half-integer (torch's CPU build may fuse the un-normalisation
+    differently by an ulp and flip the tie); at most 2 % of the in-image pixels of a sample may be left out that way;
+  * bicubic, bilinear: 1e-4 for images in [0, 1] -- fp32 rounding of 16 taps with sum |w| < 2 is ~2e-6, one ulp of ix at 320 (3e-5 px)
+    times a slope of up to 1.5 / px allows 5e-5; a wrong tap or weight gives 1e-2 and more;
+  * adjoints: <y, A x> = <A^T y, x> to 1e-5 relative (sums in float64 on the host), 2e-4 max(1, max |dx_ref|) against torch's CPU autograd.
+Measured on MI355X (profiles/EXPERIMENTS.md, "Warp modes"): nearest leaves out at most 0.70 % of a sample; bicubic 7.3e-5, bilinear 5.9e-5, rotated
+8.6e-5 at 320 x 240 (an ulp of the un-normalised coordinate times the slope) and below 1e-5 at 40 x 30; transpose gap 3.8e-9; autograd a quarter of its bar.
+"""
+import functools
+import math
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import vidc_oracle as O
+from vi_depth_completion_amd import ops
+from vi_depth_completion_amd import synthetic as S
+from vi_depth_completion_amd import torch_ops as T
+from vi_depth_completion_amd.networks.warping_2dof_alignment import Warping2DOFAlignment
+
+V = torch.ops.vidc
+GEOMS = {"small": dict(fx=25.0, fy=25.0, cx=19.6, cy=14.7), "native": dict(fx=577.87061 * 0.5, fy=577.87061 * 0.5, cx=319.87654 * 0.5, cy=239.87603 * 0.5)}
+SIZES = {"small": (40, 30), "native": (320, 240)}      # W, H
+
+
+def _roll(deg):
+    return (math.sin(math.radians(deg)), math.cos(math.radians(deg)), 0.0)
+
+
+_n = math.sqrt(0.3 ** 2 + 0.8 ** 2 + 0.4 ** 2)
+GRAVITY = {"roll10": _roll(10), "roll30": _roll(30), "roll60": _roll(60), "pitch30": (0.0, math.cos(math.radians(30)), math.sin(math.radians(30))),
+           "mixed": (0.3 / _n, 0.8 / _n, 0.4 / _n), "roll90": (1.0, 0.0, 0.0)}
+TILTED = ("roll10", "roll30", "roll60", "pitch30", "mixed")
+BATCHES = {"b3a": ("roll10", "pitch30", "mixed"), "b3b": ("roll30", "roll60", "pitch30"), "b1": ("roll30",)}
+FALLBACK_BATCH = ("roll30", "roll90", "mixed")
+MODES = ("bilinear", "nearest", "bicubic")
+CHANNELS = (1, 3, 5)
+CASES = [(g, ac) for g in ("small", "native") for ac in (False, True)]
+TIE_PX, TIE_CAP = 1e-3, 0.02
+# Worst deviation of the device's grids from the oracle's over TILTED x both geometries, pixels whose oracle coordinate lies in [-W, 2W] x [-H, 2H]
+# (measured on MI355X: 1.073e-4 px, the native forward grid; 3.8e-5 px its inverse grid, 9.5e-6 / 4.5e-6 px the small pair -- profiles/EXPERIMENTS.md,
+# "warp modes"); the spread is cosf / atan2f against torch's.  The bar is 4 x that, and 5e-3 px in any case: a confused align_corners is 0.5 px,
+# swapped kw / kh more.
+GRID_WORST_PX = 1.073e-4
+GRID_BAR_PX = min(4 * GRID_WORST_PX, 5e-3)
+
+
+def _gravity(names):
+    return torch.tensor([GRAVITY[n] for n in names], dtype=torch.float32), torch.tensor([[0.0, 1.0, 0.0]] * len(names), dtype=torch.float32)
+
+
+def _pixel_pos(grid, W, H, ac):
+    """grid_sample's un-normalisation in float64: (ix, iy), each (B,H,W)."""
+    g = grid.double()
+    if ac:
+        return (g[..., 0] + 1) / 2 * (W - 1), (g[..., 1] + 1) / 2 * (H - 1)
+    return ((g[..., 0] + 1) * W - 1) / 2, ((g[..., 1] + 1) * H - 1) / 2
+
+
+def _ties(ix, iy):
+    """Positions within TIE_PX of a half-integer in x or y (where rint may go either way), and the in-image positions."""
+    near = lambda v: ((v - torch.floor(v)) - 0.5).abs() < TIE_PX
+    return near(ix) | near(iy)
+
+
+def _in_image(ix, iy, W, H):
+    return (ix >= -0.5) & (ix <= W - 0.5) & (iy >= -0.5) & (iy <= H - 0.5)
+
+
+def _image(geom, batch, C):
+    W, H = SIZES[geom]
+    return S.uniform01(41, "warp_modes.x.%s.%s.%d" % (geom, batch, C), (len(BATCHES[batch]), C, H, W))
+
+
+# ---- CPU ---------------------------------------------------------------------------------------------------------------------------------
+def test_operators_are_registered_with_shape_functions():
+    assert T.WARP_MODE_OPS == ("warp2dof_fwd_mode", "warp2dof_fwd_mode_backward", "warp2dof_grids")
+    for name in T.WARP_MODE_OPS:
+        assert hasattr(V, name) and name in T.OPS and name not in T.BACKWARD_OPS, name
+    assert len(set(T.OPS)) == len(T.OPS)
+    from torch._subclasses.fake_tensor import FakeTensorMode
+    k = GEOMS["small"]
+    intr = (k["fx"], k["fy"], k["cx"], k["cy"])
+    with FakeTensorMode(), torch.enable_grad():
+        g = torch.empty(2, 3)
+        for C in CHANNELS:
+            x = torch.empty(2, C, 30, 40, requires_grad=True)
+            for mode in (0, 1, 2):
+                h, y = V.warp2dof_fwd_mode(x, g, g, *intr, False, mode, False)
+                assert h.shape == (2, 3, 3) and y.shape == x.shape and y.dtype == torch.float32 and y.grad_fn is not None
+                assert torch.autograd.grad(y.sum(), (x,))[0].shape == x.shape
+                assert V.warp2dof_fwd_mode_backward(y.detach(), g, g, *intr, True, mode, C == 3).shape == x.shape
+        rot, grid, inv = V.warp2dof_grids(g, g, *intr, 40, 30)
+        assert rot.shape == (2, 3, 3) and grid.shape == inv.shape == (2, 30, 40, 2) and not grid.requires_grad
+        with pytest.raises(RuntimeError, match="not differentiable"):
+            V.warp2dof_fwd_mode(x, g.clone().requires_grad_(), g, *intr, False, 1, False)
+
+
+def test_interp_mode_strings_and_refusals():
+    wp = Warping2DOFAlignment(device="cpu", **GEOMS["small"])
+    x, (g, a) = torch.zeros(1, 3, 30, 40), _gravity(("roll30",))
+    for method in (wp.warp_with_gravity_center_aligned, wp.warp_normal_image_with_gravity_center_aligned):
+        with pytest.raises(ValueError, match="'bilinear', 'nearest' or 'bicubic'"):
+            method(x, g, a, interp_mode="cubic")
+        for mode in MODES:                       # CPU tensors are refused, whatever the mode: there is no CPU path
+            with pytest.raises(RuntimeError, match="GPU only"):
+                method(x, g, a, interp_mode=mode)
+    with pytest.raises(RuntimeError, match="GPU only"):
+        wp.image_sampler_forward_inverse(g, a)
+    with pytest.raises(RuntimeError, match="GPU only"):
+        wp.warp_with_homography(x, np.identity(3))
+    for bad in (torch.zeros(2, 3, 30, 40), torch.zeros(3, 30, 40)):
+        with pytest.raises(RuntimeError, match="one image"):
+            wp.warp_with_homography(bad, np.identity(3))
+    with pytest.raises((NotImplementedError, RuntimeError)):
+        V.warp2dof_fwd_mode(x, g, a, 25.0, 25.0, 19.6, 14.7, False, 1, False)
+
+
+def _cubic_weights(t):
+    """csrc/warp.hip's cubic_weights in numpy fp32: torch's cubic convolution with A = -0.75, taps floor(i) - 1 .. floor(i) + 2."""
+    f = np.float32
+    A, t = f(-0.75), f(t)
+    far = lambda x: ((A * x - f(5) * A) * x + f(8) * A) * x - f(4) * A
+    near = lambda x: ((A + f(2)) * x - (A + f(3))) * x * x + f(1)
+    return np.array([far(t + f(1)), near(t), near(f(1) - t), far((f(1) - t) + f(1))], dtype=np.float32)
+
+
+@pytest.mark.parametrize("t", [0.0, 0.25, 0.5])
+def test_bicubic_weights_are_torchs(t):
+    """A one-row image with a single 1 read by grid_sample at 3 + t (align_corners: ix = (g + 1) / 2 * 7) gives torch's weight of that tap."""
+    w = _cubic_weights(t)
+    assert abs(float(w.astype(np.float64).sum()) - 1.0) < 1e-6
+    if t == 0.0:
+        assert w.tolist() == [0.0, 1.0, 0.0, 0.0]
+    grid = torch.tensor([[[[2 * (3 + t) / 7 - 1, 0.0]]]], dtype=torch.float32)
+    for i in range(4):
+        img = torch.zeros(1, 1, 1, 8)
+        img[0, 0, 0, 2 + i] = 1.0
+        got = F.grid_sample(img, grid, mode="bicubic", padding_mode="zeros", align_corners=True).item()
+        assert abs(got - float(w[i])) < 1e-6, (t, i, got, w[i])
+
+
+@pytest.mark.parametrize("geom,ac", CASES)
+def test_tie_share_of_the_inputs_stays_under_the_cap(geom, ac):
+    """Item 4's share of left-out pixels, on the oracle's grids: pins the gravities without a GPU.  Also: roll 60 puts more than half of the
+    forward warp outside the image (the zeros-padding test needs that region)."""
+    W, H = SIZES[geom]
+    g, a = _gravity(TILTED)
+    _, _, grid = O.forward_grid(g, a, O.Intrinsics(**GEOMS[geom]))
+    ix, iy = _pixel_pos(grid, W, H, ac)
+    tie, inside = _ties(ix, iy), _in_image(ix, iy, W, H)
+    for i, name in enumerate(TILTED):
+        share = (tie[i] & inside[i]).sum().item() / inside[i].sum().item()
+        print("TIES %-6s ac=%d %-8s %.3f %% of %d in-image pixels" % (geom, ac, name, 100 * share, inside[i].sum().item()))
+        assert share <= TIE_CAP, (name, share)
+    assert inside[TILTED.index("roll60")].double().mean().item() < 0.5
+
+
+# ---- GPU: shared inputs and references (computed once) -------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _setup(geom, ac, names):
+    W, H = SIZES[geom]
+    wp = Warping2DOFAlignment(align_corners=ac, device="cuda", **GEOMS[geom])
+    assert (wp.W, wp.H) == (W, H)
+    g, a = _gravity(names)
+    gd, ad = g.cuda(), a.cuda()
+    params = wp._params(gd, ad)
+    rot, grid, inv = wp.image_sampler_forward_inverse(gd, ad)
+    grid_cpu = grid.cpu()
+    ix, iy = _pixel_pos(grid_cpu, W, H, ac)
+    return SimpleNamespace(wp=wp, W=W, H=H, ac=ac, g=g, a=a, gd=gd, ad=ad, params=params, rot=rot.cpu(), grid=grid_cpu, inv=inv.cpu(), ix=ix, iy=iy,
+                           tie=_ties(ix, iy), inside=_in_image(ix, iy, W, H), R=params[:, 9:18].reshape(-1, 3, 3).cpu(), intr=O.Intrinsics(**GEOMS[geom]))
+
+
+def _case(geom, ac, batch):
+    return _setup(geom, ac, BATCHES[batch])
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(geom, ac, batch, C, mode):
+    """F.grid_sample on the CPU through the device's grid; never modified."""
+    s = _case(geom, ac, batch)
+    with torch.no_grad():
+        return F.grid_sample(_image(geom, batch, C), s.grid, mode=mode, padding_mode="zeros", align_corners=ac)
+
+
+def _ours(geom, ac, batch, C, mode, rotate=False):
+    s = _case(geom, ac, batch)
+    with torch.no_grad():
+        return ops.warp2dof_fwd_mode(_image(geom, batch, C).cuda(), s.params, s.wp.cx, s.wp.cy, ac, ops.WARP_MODES[mode], rotate).cpu()
+
+
+# ---- 1, 2. geometry ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_grids_against_the_oracle():
+    worst = 0.0
+    for geom, ac in CASES:
+        s = _setup(geom, ac, TILTED)
+        for kind, ours, make in (("forward", s.grid, O.forward_grid), ("inverse", s.inv, O.inverse_grid)):
+            _, _, ref = make(s.g, s.a, s.intr)
+            u, v = ref[..., 0].double() * (s.W / 2) + s.intr.cx, ref[..., 1].double() * (s.H / 2) + s.intr.cy
+            use = (u >= -s.W) & (u <= 2 * s.W) & (v >= -s.H) & (v <= 2 * s.H)
+            assert use.double().mean().item() > 0.5
+            d = (ours.double() - ref.double()).abs()
+            dev = max((d[..., 0] * (s.W / 2))[use].max().item(), (d[..., 1] * (s.H / 2))[use].max().item())
+            print("GRID %-6s ac=%d %-7s worst |dg| %.3e px over %d pixels" % (geom, ac, kind, dev, use.sum().item()))
+            worst = max(worst, dev)
+    print("GRID worst %.3e px, bar %.3e px" % (worst, GRID_BAR_PX))
+    assert worst <= GRID_BAR_PX
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("geom,ac", CASES)
+def test_extreme_tilt_falls_back_to_the_identity(geom, ac):
+    s = _setup(geom, ac, FALLBACK_BATCH)
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    ys, xs = torch.meshgrid(torch.arange(s.H, dtype=torch.float32), torch.arange(s.W, dtype=torch.float32), indexing="ij")
+    gx = f32(1.0) / (f32(s.W) / f32(2.0)) * (xs - f32(s.wp.cx))
+    gy = f32(1.0) / (f32(s.H) / f32(2.0)) * (ys - f32(s.wp.cy))
+    ident = torch.stack([gx, gy], dim=-1)
+    assert torch.equal(s.grid[1], ident) and torch.equal(s.inv[1], ident) and torch.equal(s.rot[1], torch.eye(3))
+    _, R, fwd = O.forward_grid(s.g, s.a, s.intr)
+    for i in (0, 2):
+        assert (s.rot[i] - R[i].t()).abs().max().item() <= 1e-6
+        assert not torch.equal(s.grid[i], ident) and not torch.equal(s.inv[i], ident)
+        assert ((s.grid[i] - fwd[i]).abs()[..., 0] * (s.W / 2)).median().item() < 5e-3      # (the warped grid, not some other one)
+
+
+# ---- 3. bilinear through the new entry ------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("geom,ac", CASES)
+def test_mode_0_is_the_bilinear_warp_bit_for_bit(geom, ac):
+    for batch in BATCHES:
+        s = _case(geom, ac, batch)
+        for C in CHANNELS:
+            x = _image(geom, batch, C).cuda()
+            _, y = s.wp.warp_with_gravity_center_aligned(x, s.gd, s.ad)          # vidc_warp2dof_fwd
+            assert torch.equal(ops.warp2dof_fwd_mode(x, s.params, s.wp.cx, s.wp.cy, ac, 0), y), (batch, C)
+            dy = S.normal01(42, "warp_modes.dy0.%s.%s.%d" % (geom, batch, C), tuple(x.shape)).float().cuda()
+            dx = ops.warp2dof_fwd_backward(dy, s.params, s.wp.cx, s.wp.cy, ac)
+            assert dx.abs().max().item() > 0
+            assert torch.equal(ops.warp2dof_fwd_mode_backward(dy, s.params, s.wp.cx, s.wp.cy, ac, 0), dx), (batch, C)
+
+
+# ---- 4, 5. interpolation ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("geom,ac", CASES)
+def test_nearest_has_the_references_bits(geom, ac):
+    for batch in BATCHES:
+        s = _case(geom, ac, batch)
+        for i, name in enumerate(BATCHES[batch]):
+            share = (s.tie[i] & s.inside[i]).sum().item() / s.inside[i].sum().item()
+            print("NEAREST %-6s ac=%d %-8s %.3f %% of the in-image pixels left out" % (geom, ac, name, 100 * share))
+            assert share <= TIE_CAP, (name, share)
+        for C in CHANNELS:
+            ref, got = _reference(geom, ac, batch, C, "nearest"), _ours(geom, ac, batch, C, "nearest")
+            keep = ~s.tie.unsqueeze(1).expand_as(ref)
+            wrong = (got != ref) & keep
+            assert not wrong.any(), (batch, C, int(wrong.sum()), (got - ref).abs().max().item())
+            assert (got[keep] != 0).double().mean().item() > 0.2          # (it did sample something)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["bicubic", "bilinear"])
+@pytest.mark.parametrize("geom,ac", CASES)
+def test_bicubic_and_bilinear_through_the_grid(geom, ac, mode):
+    worst, lo, hi = 0.0, 0.0, 1.0
+    for batch in BATCHES:
+        for C in CHANNELS:
+            ref, got = _reference(geom, ac, batch, C, mode), _ours(geom, ac, batch, C, mode)
+            worst = max(worst, (got - ref).abs().max().item())
+            lo, hi = min(lo, got.min().item()), max(hi, got.max().item())
+    print("INTERP %-8s %-6s ac=%d max |ours - grid_sample| %.3e (bar 1e-4), range [%.4f, %.4f]" % (mode, geom, ac, worst, lo, hi))
+    assert worst <= 1e-4
+    if mode == "bicubic":         # the overshoot of the cubic kernel: a clamped or bilinear stand-in stays inside [0, 1]
+        assert lo < -1e-3 and hi > 1 + 1e-3
+
+
+# ---- 6. zeros padding -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("geom,ac", CASES)
+def test_zeros_padding_outside_the_image(geom, ac):
+    batch, i = "b3b", BATCHES["b3b"].index("roll60")
+    s = _case(geom, ac, batch)
+    ix, iy, W, H = s.ix[i], s.iy[i], s.W, s.H
+    assert s.inside[i].double().mean().item() < 0.5
+    eps = TIE_PX
+    for C in CHANNELS:
+        near, cubic = _ours(geom, ac, batch, C, "nearest")[i], _ours(geom, ac, batch, C, "bicubic")[i]
+        # nearest: rint lands outside
+        out1 = (ix < -0.5 - eps) | (ix > W - 0.5 + eps) | (iy < -0.5 - eps) | (iy > H - 0.5 + eps)
+        assert out1.sum().item() > 0.5 * W * H and (near[:, out1] == 0).all()
+        # bicubic: taps floor(i) - 1 .. floor(i) + 2 all outside in x or in y
+        out2 = (ix < -2 - eps) | (ix > W + 1 + eps) | (iy < -2 - eps) | (iy > H + 1 + eps)
+        assert out2.sum().item() > 0.25 * W * H and (cubic[:, out2] == 0).all()
+        # the rim: the position is up to one pixel outside on one side, well inside on the other axis -- some taps are in the image
+        rim_x = (((ix > -0.9) & (ix < -0.1)) | ((ix > W - 0.9) & (ix < W - 0.1))) & (iy > 1) & (iy < H - 2)
+        rim_y = (((iy > -0.9) & (iy < -0.1)) | ((iy > H - 0.9) & (iy < H - 0.1))) & (ix > 1) & (ix < W - 2)
+        rim = rim_x | rim_y
+        assert rim.sum().item() >= 4 and (cubic[:, rim] != 0).all()
+
+
+# ---- 7. the rotated forward warp ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("geom,ac", CASES)
+def test_warp_normal_image_rotates_the_gather(geom, ac):
+    for batch in BATCHES:
+        s = _case(geom, ac, batch)
+        B = len(BATCHES[batch])
+        x = _image(geom, batch, 3).cuda()
+        h0, _ = s.wp.warp_with_gravity_center_aligned(x, s.gd, s.ad)
+        for mode in MODES:
+            h, z = s.wp.warp_normal_image_with_gravity_center_aligned(x, s.gd, s.ad, interp_mode=mode)
+            assert h.shape == (B, 3, 3) and torch.equal(h, h0) and z.shape == x.shape and z.dtype == torch.float32
+            ref = s.R.bmm(_reference(geom, ac, batch, 3, mode).view(B, 3, -1)).view(B, 3, s.H, s.W)
+            d = (z.cpu() - ref).abs()
+            if mode == "nearest":
+                d = d.masked_fill(s.tie.unsqueeze(1).expand_as(d), 0.0)
+            print("ROTATE %-8s %-6s ac=%d %-3s max |z - R gather| %.3e (bar 1e-4)" % (mode, geom, ac, batch, d.max().item()))
+            assert d.max().item() <= 1e-4
+        assert torch.equal(s.wp.warp_normal_image_with_gravity_center_aligned(x, s.gd, s.ad)[1],
+                           s.wp.warp_normal_image_with_gravity_center_aligned(x, s.gd, s.ad, "bilinear")[1])
+        for mode in MODES[1:]:
+            _, y = s.wp.warp_with_gravity_center_aligned(x, s.gd, s.ad, interp_mode=mode)
+            assert torch.equal(y.cpu(), _ours(geom, ac, batch, 3, mode))
+    one = _image(geom, "b1", 1).cuda()[:, 0]            # the (B,H,W) form keeps its shape in every mode
+    s = _case(geom, ac, "b1")
+    assert s.wp.warp_with_gravity_center_aligned(one, s.gd, s.ad, interp_mode="nearest")[1].shape == one.shape
+
+
+# ---- 8. adjoints ------------------------------------------------------------------------------------------------------------------------------
+def _adjoint_cases():
+    return [(batch, C, rotate) for batch in BATCHES for C in CHANNELS for rotate in ((False, True) if C == 3 else (False,))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("geom,ac", CASES)
+def test_adjoint_is_the_exact_transpose(geom, ac, mode):
+    m = ops.WARP_MODES[mode]
+    for batch, C, rotate in _adjoint_cases():
+        s = _case(geom, ac, batch)
+        x = _image(geom, batch, C)
+        dy = S.normal01(43, "warp_modes.dy.%s.%s.%d" % (geom, batch, C), tuple(x.shape)).float()
+        y = ops.warp2dof_fwd_mode(x.cuda(), s.params, s.wp.cx, s.wp.cy, ac, m, rotate).cpu()
+        dx = ops.warp2dof_fwd_mode_backward(dy.cuda(), s.params, s.wp.cx, s.wp.cy, ac, m, rotate)
+        again = ops.warp2dof_fwd_mode_backward(dy.cuda(), s.params, s.wp.cx, s.wp.cy, ac, m, rotate)
+        assert torch.equal(dx, again), "two runs differ"                                 # (c)
+        dx = dx.cpu()
+        terms = y.double() * dy.double()                                                   # (a)
+        lhs, rhs = terms.sum().item(), (dx.double() * x.double()).sum().item()
+        gap = abs(lhs - rhs) / terms.abs().sum().item()
+        assert terms.abs().sum().item() > 0 and gap <= 1e-5, (batch, C, rotate, gap)
+        # (b) torch's CPU autograd through the reference gather; a flipped tie would move a whole dy value, so nearest gets dy = 0 at the ties
+        if mode == "nearest":
+            dy = dy.masked_fill(s.tie.unsqueeze(1).expand_as(dy), 0.0)
+            dx = ops.warp2dof_fwd_mode_backward(dy.cuda(), s.params, s.wp.cx, s.wp.cy, ac, m, rotate).cpu()
+        with torch.enable_grad():
+            leaf = x.clone().requires_grad_()
+            out = F.grid_sample(leaf, s.grid, mode=mode, padding_mode="zeros", align_corners=ac)
+            if rotate:
+                out = s.R.bmm(out.view(len(s.R), 3, -1)).view_as(out)
+            ref, = torch.autograd.grad((out * dy).sum(), leaf)
+        dev, bar = (dx - ref).abs().max().item(), 2e-4 * max(1.0, ref.abs().max().item())
+        print("ADJOINT %-8s %-6s ac=%d %-3s C=%d rot=%d transpose gap %.2e, max |dx - autograd| %.3e (bar %.3e)" % (mode, geom, ac, batch, C, rotate, gap, dev, bar))
+        assert dev <= bar, (batch, C, rotate)
+
+
+@pytest.mark.gpu
+def test_autograd_reaches_the_image_and_refuses_the_geometry():
+    geom, ac = "small", False
+    s = _case(geom, ac, "b3a")
+    k = GEOMS[geom]
+    intr = (k["fx"], k["fy"], k["cx"], k["cy"])
+    dy = S.normal01(44, "warp_modes.dy.autograd", (3, 3, s.H, s.W)).float().cuda()
+    for mode in (0, 1, 2):
+        for rotate in (False, True):
+            with torch.enable_grad():
+                x = _image(geom, "b3a", 3).cuda().requires_grad_()
+                h, y = V.warp2dof_fwd_mode(x, s.gd, s.ad, *intr, ac, mode, rotate)
+                assert h.shape == (3, 3, 3) and y.grad_fn is not None
+                (y * dy).sum().backward()
+            assert torch.equal(x.grad, ops.warp2dof_fwd_mode_backward(dy, s.params, s.wp.cx, s.wp.cy, ac, mode, rotate))
+            assert torch.equal(y.detach(), ops.warp2dof_fwd_mode(x.detach(), s.params, s.wp.cx, s.wp.cy, ac, mode, rotate))
+    with torch.enable_grad(), pytest.raises(RuntimeError, match="not differentiable"):
+        V.warp2dof_fwd_mode(x.detach(), s.gd.clone().requires_grad_(), s.ad, *intr, ac, 2, False)
+    rot, grid, inv = V.warp2dof_grids(s.gd, s.ad, *intr, s.W, s.H)
+    assert torch.equal(grid.cpu(), s.grid) and torch.equal(inv.cpu(), s.inv) and torch.equal(rot.cpu(), s.rot)
+
+
+# ---- 9. warp_with_homography ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["identity", "roll30"])
+@pytest.mark.parametrize("geom,ac", CASES)
+def test_warp_with_homography_on_a_linear_ramp(geom, ac, which):
+    """Bilinear interpolation reproduces a linear image exactly, so the warp of a ramp is the ramp at the sampling position, restated here in
+    float64 from warping_2dof_alignment.py:292-310: independent scales kw, kh from the corner box, numpy's inverse."""
+    W, H = SIZES[geom]
+    wp = Warping2DOFAlignment(align_corners=ac, device="cuda", **GEOMS[geom])
+    if which == "identity":
+        Hm = np.identity(3)
+    else:
+        Hm = O.homography(*_gravity(("roll30",)), O.Intrinsics(**GEOMS[geom]))[0][0].double().numpy()
+    ys, xs = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    ramp = lambda x, y: np.stack([x / (W - 1), y / (H - 1), 0.3 * x / (W - 1) + 0.5 * y / (H - 1) + 0.2])
+    img = torch.tensor(ramp(xs, ys)[None], dtype=torch.float32)
+    c = Hm @ np.array([[0, W - 1, 0, W - 1], [0, 0, H - 1, H - 1], [1, 1, 1, 1]], dtype=np.float64)
+    c = c / c[2]
+    kw, kh = W / (c[0].max() - c[0].min()), H / (c[1].max() - c[1].min())
+    P = np.linalg.inv(Hm) @ np.stack([(xs / kw + c[0].min()).reshape(-1), (ys / kh + c[1].min()).reshape(-1), np.ones(H * W)])
+    u, v = (P[0] / P[2]).reshape(H, W), (P[1] / P[2]).reshape(H, W)
+    gx, gy = (u - wp.cx) / (W / 2), (v - wp.cy) / (H / 2)
+    if ac:
+        ix, iy = (gx + 1) / 2 * (W - 1), (gy + 1) / 2 * (H - 1)
+    else:
+        ix, iy = ((gx + 1) * W - 1) / 2, ((gy + 1) * H - 1) / 2
+    inside = (ix >= 0) & (ix <= W - 1) & (iy >= 0) & (iy <= H - 1)
+    for arg in (Hm, torch.tensor(Hm)):
+        ret, y = wp.warp_with_homography(img.cuda(), arg)
+        assert ret is arg and y.shape == img.shape
+        dev = np.abs(y[0].cpu().numpy().astype(np.float64) - ramp(ix, iy))[:, inside].max()
+        print("HOMOGRAPHY %-8s %-6s ac=%d max deviation inside %.3e over %.1f %% of the pixels" % (which, geom, ac, dev, 100 * inside.mean()))
+        assert inside.mean() > 0.5 and dev <= 1e-4

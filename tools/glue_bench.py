@@ -29,9 +29,42 @@ def timed(fn, n=50):
     return e0.elapsed_time(e1) * 1e3 / n
 
 
+def warp_mode_rows(lib, st, B=32):
+    """The forward warp in its three interpolation modes (vidc_warp2dof_fwd_mode) and their adjoints at the native 3 x 240 x 320, beside the
+    bilinear kernels they stand next to; algorithmic bytes = the image in + the image out."""
+    wp = Warping2DOFAlignment()
+    H, W = wp.H, wp.W
+    b = S.synthetic_batch(B, H, W, 1234)
+    x = b["image"].cuda()
+    p = wp._params(b["gravity"].cuda(), b["aligned_direction"].cuda())
+    y = torch.empty_like(x)
+    nbytes = 2 * x.numel() * 4
+    rows = [("warp_fwd 3ch %dx%d" % (W, H), B, timed(lambda: lib.vidc_warp2dof_fwd(x.data_ptr(), p.data_ptr(), y.data_ptr(), B, 3, H, W, wp.cx, wp.cy, 0, st)), nbytes),
+            ("warp_fwd_backward", B, timed(lambda: lib.vidc_warp2dof_fwd_backward(x.data_ptr(), p.data_ptr(), y.data_ptr(), B, 3, H, W, wp.cx, wp.cy, 0, st)), nbytes)]
+    for mode, name in enumerate(("bilinear", "nearest", "bicubic")):
+        us = timed(lambda: lib.vidc_warp2dof_fwd_mode(x.data_ptr(), p.data_ptr(), y.data_ptr(), B, 3, H, W, wp.cx, wp.cy, 0, mode, 0, st))
+        rows.append(("warp_fwd_mode %s" % name, B, us, nbytes))
+        us = timed(lambda: lib.vidc_warp2dof_fwd_mode_backward(x.data_ptr(), p.data_ptr(), y.data_ptr(), B, 3, H, W, wp.cx, wp.cy, 0, mode, 0, st))
+        rows.append(("warp_fwd_mode_backward %s" % name, B, us, nbytes))
+    us = timed(lambda: lib.vidc_warp2dof_fwd_mode(x.data_ptr(), p.data_ptr(), y.data_ptr(), B, 3, H, W, wp.cx, wp.cy, 0, 2, 1, st))
+    rows.append(("warp_fwd_mode bicubic + rotate", B, us, nbytes))
+    grid, inv, rot = torch.empty(B, H, W, 2, device="cuda"), torch.empty(B, H, W, 2, device="cuda"), torch.empty(B, 3, 3, device="cuda")
+    us = timed(lambda: lib.vidc_warp2dof_grids(p.data_ptr(), grid.data_ptr(), inv.data_ptr(), rot.data_ptr(), B, H, W, wp.cx, wp.cy, st))
+    rows.append(("warp2dof_grids", B, us, 2 * grid.numel() * 4))
+    return rows
+
+
+def report(rows):
+    print("%-36s %5s %10s %10s %10s %8s" % ("kernel", "batch", "us", "MB", "GB/s", "of peak"))
+    for name, B, us, nbytes in rows:
+        print("%-36s %5d %10.1f %10.2f %10.1f %7.1f%%" % (name, B, us, nbytes / 1e6, nbytes / us / 1e3, 100 * nbytes / us / 1e3 / PEAK))
+
+
 def main():
     lib = L.lib()
     st = torch.cuda.current_stream().cuda_stream
+    if "--warp-modes" in sys.argv[1:]:      # only the rows of warp_mode_rows
+        return report(warp_mode_rows(lib, st))
     H, W = 256, 320
     rows = []
     for B in (1, 4, 8, 32):
@@ -75,9 +108,7 @@ def main():
         yo = torch.empty(B, 64, 80, 512, device="cuda")
         us = timed(lambda: lib.vidc_maxpool3x3s2(xi.data_ptr(), yo.data_ptr(), B, 128, 160, 512, 512, 512, None, st))
         rows.append(("maxpool 128x160x512 (4 pyramids)", B, us, (xi.numel() + yo.numel()) * 4))
-    print("%-36s %5s %10s %10s %10s %8s" % ("kernel", "batch", "us", "MB", "GB/s", "of peak"))
-    for name, B, us, nbytes in rows:
-        print("%-36s %5d %10.1f %10.2f %10.1f %7.1f%%" % (name, B, us, nbytes / 1e6, nbytes / us / 1e3, 100 * nbytes / us / 1e3 / PEAK))
+    report(rows + warp_mode_rows(lib, st))
 
 
 if __name__ == "__main__":

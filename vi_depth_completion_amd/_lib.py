@@ -161,6 +161,9 @@ SIGNATURES = {
     "vidc_warp2dof_inv_rot_norm": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _i, _vp]),
     "vidc_warp2dof_fwd_backward": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "vidc_warp2dof_inv_rot_norm_backward": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _i, _vp]),
+    "vidc_warp2dof_fwd_mode": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _i, _vp]),
+    "vidc_warp2dof_fwd_mode_backward": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _i, _vp]),
+    "vidc_warp2dof_grids": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp]),
     "vidc_affine_act_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vidc_stem_conv3x3s2_backward_data": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "vidc_pack_conv_weight": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp]),

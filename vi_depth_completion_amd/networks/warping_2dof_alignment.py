@@ -1,6 +1,10 @@
-"""Drop-in for the reference's `Warping2DOFAlignment` (networks/warping_2dof_alignment.py:5-24, 108-156, 216-255):
+"""Drop-in for the reference's `Warping2DOFAlignment` (networks/warping_2dof_alignment.py:5-24, 108-310):
 same constructor and method signatures, but each method is two HIP launches (per-sample geometry + fused
 gather) through libvidc.so instead of ~520 ATen calls.  No weights; not an nn.Module (like the reference).
+
+`warp_normal_image_with_gravity_center_aligned` is read as its sibling `warp_with_gravity_center_aligned` reads: as shipped (:259-260) the
+reference's method fails on its first line -- it unpacks two of `_build_homography`'s three values and inverts Cg_H_C with torch.inverse
+where the sibling takes the third, K R^T K^-1.  `warp_with_homography` builds its geometry record on the host (one launch).
 """
 import math
 
@@ -8,6 +12,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from .. import ops
 
 
 class Warping2DOFAlignment:
@@ -45,10 +50,16 @@ class Warping2DOFAlignment:
         if not x.is_cuda:
             raise RuntimeError("Warping2DOFAlignment runs on the GPU only (HIP path, no CPU fallback)")
 
+    @staticmethod
+    def _mode(interp_mode):
+        """F.grid_sample's `mode` string -> VIDC_WARP_*."""
+        if interp_mode not in ops.WARP_MODES:
+            raise ValueError("interp_mode must be 'bilinear', 'nearest' or 'bicubic', got %r" % (interp_mode,))
+        return ops.WARP_MODES[interp_mode]
+
     def warp_with_gravity_center_aligned(self, x, I_g, I_a, interp_mode="bilinear"):
+        mode = self._mode(interp_mode)
         self._require_device(x)
-        if interp_mode != "bilinear":
-            raise NotImplementedError("only bilinear interpolation is implemented")
         squeeze = x.dim() == 3
         if squeeze:
             x = x.view(x.shape[0], 1, x.shape[1], x.shape[2])
@@ -56,10 +67,13 @@ class Warping2DOFAlignment:
         assert tuple(x.shape[-2:]) == (self.H, self.W), "image must be %dx%d" % (self.H, self.W)
         x = x.contiguous().float()
         p = self._params(I_g, I_a)
-        y = torch.empty_like(x)
         B, Cc = x.shape[0], x.shape[1]
-        L.check(L.lib().vidc_warp2dof_fwd(L.ptr(x), L.ptr(p), L.ptr(y), B, Cc, self.H, self.W, self.cx, self.cy,
-                                          int(self.align_corners), L.current_stream()), "warp2dof_fwd")
+        if mode == 0:
+            y = torch.empty_like(x)
+            L.check(L.lib().vidc_warp2dof_fwd(L.ptr(x), L.ptr(p), L.ptr(y), B, Cc, self.H, self.W, self.cx, self.cy,
+                                              int(self.align_corners), L.current_stream()), "warp2dof_fwd")
+        else:
+            y = ops.warp2dof_fwd_mode(x, p, self.cx, self.cy, self.align_corners, mode)
         Cg_H_C = p[:, 0:9].reshape(B, 3, 3).clone()
         return (Cg_H_C, y.view(B, self.H, self.W)) if squeeze else (Cg_H_C, y)
 
@@ -75,3 +89,41 @@ class Warping2DOFAlignment:
                                                    int(self.align_corners), int(normalize), L.current_stream()),
                 "warp2dof_inv_rot_norm")
         return p[:, 0:9].reshape(B, 3, 3).clone(), z
+
+    def warp_normal_image_with_gravity_center_aligned(self, x, I_g, I_a, interp_mode="bilinear"):
+        """The forward companion of the inverse normal warp (:258-290): the gather of warp_with_gravity_center_aligned, then z = Cg_R_C y."""
+        mode = self._mode(interp_mode)
+        self._require_device(x)
+        assert x.shape[0] == I_g.shape[0] and x.shape[1] == 3
+        assert tuple(x.shape[-2:]) == (self.H, self.W)
+        p = self._params(I_g, I_a)
+        z = ops.warp2dof_fwd_mode(x, p, self.cx, self.cy, self.align_corners, mode, rotate=True)
+        return p[:, 0:9].reshape(x.shape[0], 3, 3).clone(), z
+
+    def image_sampler_forward_inverse(self, I_g, I_a):
+        """(C_R_Cg_ret, grid_sampler, inv_grid_sampler) (:158-214): the sampling grids of the two warps as F.grid_sample takes them, and
+        Cg_R_C^T; a sample tilted so far that its corner box leaves [0.8, 2.2] in w_max / h_max gets identity grids and I3 (:178-187)."""
+        self._require_device(I_g)
+        return ops.warp2dof_grids(self._params(I_g, I_a), self.H, self.W, self.cx, self.cy)
+
+    def homography_record(self, Cg_H_C):
+        """The 32-float record of vidc_warp2dof_params for a GIVEN homography (warp_with_homography, :292-310), on the host in float64 as the
+        reference computes it, cast to fp32: R = I, numpy's inverse, the corner box and kw = W / (w_max - w_min), kh = H / (h_max - h_min)
+        -- independent scales, no 4:3 rule."""
+        Hm = np.asarray(Cg_H_C.detach().cpu() if torch.is_tensor(Cg_H_C) else Cg_H_C, dtype=np.float64).reshape(3, 3)
+        corners = np.array([[0, 0, 1], [self.W - 1, 0, 1], [0, self.H - 1, 1], [self.W - 1, self.H - 1, 1]], dtype=np.float64).T
+        c = Hm @ corners
+        c = c / c[2, :]
+        h_min, h_max, w_min, w_max = c[1].min(), c[1].max(), c[0].min(), c[0].max()
+        rec = np.zeros(L.WARP_PARAMS, dtype=np.float64)
+        rec[0:9], rec[9:18], rec[18:27] = Hm.reshape(-1), np.identity(3).reshape(-1), np.linalg.inv(Hm).reshape(-1)
+        rec[27:31] = w_min, h_min, self.W / (w_max - w_min), self.H / (h_max - h_min)
+        return rec.astype(np.float32)
+
+    def warp_with_homography(self, x, Cg_H_C):
+        if x.dim() != 4 or x.shape[0] != 1:
+            raise RuntimeError("warp_with_homography takes one image (1,C,H,W), as the reference's single grid does; got %s" % (tuple(x.shape),))
+        self._require_device(x)
+        assert tuple(x.shape[-2:]) == (self.H, self.W), "image must be %dx%d" % (self.H, self.W)
+        p = torch.from_numpy(self.homography_record(Cg_H_C)).view(1, L.WARP_PARAMS).to(x.device)
+        return Cg_H_C, ops.warp2dof_fwd_mode(x, p, self.cx, self.cy, self.align_corners, 0)

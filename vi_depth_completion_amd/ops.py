@@ -383,6 +383,44 @@ def warp2dof_inv_rot_norm_backward(x, dz, params, cx, cy, align_corners, normali
     return dx
 
 
+WARP_MODES = {"bilinear": 0, "nearest": 1, "bicubic": 2}      # VIDC_WARP_BILINEAR / _NEAREST / _BICUBIC: F.grid_sample's `mode` strings
+
+
+def warp2dof_fwd_mode(x, params, cx, cy, align_corners, mode, rotate=False):
+    """vidc_warp2dof_fwd_mode: the forward warp of x (B,C,H,W) in interpolation mode 0 / 1 / 2 (WARP_MODES); rotate (C == 3): z = Cg_R_C y per
+    pixel.  params: the (B,32) record of vidc_warp2dof_params."""
+    _dev(x, params)
+    x = x.contiguous().float()
+    B, Cc, H, W = x.shape
+    y = torch.empty_like(x)
+    L.check(L.lib().vidc_warp2dof_fwd_mode(L.ptr(x), L.ptr(params), L.ptr(y), B, Cc, H, W, float(cx), float(cy), int(align_corners), int(mode),
+                                           int(rotate), L.current_stream()), "warp2dof_fwd_mode")
+    return y
+
+
+def warp2dof_fwd_mode_backward(dy, params, cx, cy, align_corners, mode, rotate=False):
+    """dx of vidc_warp2dof_fwd_mode: dy (B,C,H,W), the gradient of its output."""
+    _dev(dy, params)
+    dy = dy.contiguous().float()
+    B, Cc, H, W = dy.shape
+    dx = torch.empty_like(dy)
+    L.check(L.lib().vidc_warp2dof_fwd_mode_backward(L.ptr(dy), L.ptr(params), L.ptr(dx), B, Cc, H, W, float(cx), float(cy), int(align_corners),
+                                                    int(mode), int(rotate), L.current_stream()), "warp2dof_fwd_mode_backward")
+    return dx
+
+
+def warp2dof_grids(params, H, W, cx, cy):
+    """vidc_warp2dof_grids: (C_R_Cg (B,3,3), grid (B,H,W,2), inverse grid (B,H,W,2)) of the (B,32) records -- image_sampler_forward_inverse."""
+    _dev(params)
+    B = params.shape[0]
+    grid = torch.empty((B, H, W, 2), dtype=torch.float32, device=params.device)
+    inv_grid = torch.empty_like(grid)
+    rot = torch.empty((B, 3, 3), dtype=torch.float32, device=params.device)
+    L.check(L.lib().vidc_warp2dof_grids(L.ptr(params), L.ptr(grid), L.ptr(inv_grid), L.ptr(rot), B, int(H), int(W), float(cx), float(cy),
+                                        L.current_stream()), "warp2dof_grids")
+    return rot, grid, inv_grid
+
+
 def affine_act_backward(dy, y, scale, shift, relu, c_raw=None, all_from_raw=False):
     """The conv epilogue y = relu?(c * scale + shift) transposed: (dc, dscale, dshift) from NHWC dy, y (vidc_affine_act_backward).  c_raw: the raw
     conv output, read for the channels whose scale is 0 or whose |shift| > 4 |scale| (torch_ops.affine_reads_raw) -- or, with all_from_raw, for

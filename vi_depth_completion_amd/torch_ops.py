@@ -13,6 +13,8 @@ Inference surface (differentiable where the Autograd section says so):
 
     torch.ops.vidc.warp2dof_fwd(x, g, a, fx, fy, cx, cy, align_corners)      warping_2dof_alignment.py:108-156
     torch.ops.vidc.warp2dof_inv_rot_norm(x, g, a, fx, fy, cx, cy, align_corners, normalize)   :216-255 (+ surface_normal.py:170)
+    torch.ops.vidc.warp2dof_fwd_mode(x, g, a, fx, fy, cx, cy, align_corners, mode, rotate)    :108-156 with interp_mode (0 bilinear, 1 nearest, 2 bicubic); rotate: :258-290
+    torch.ops.vidc.warp2dof_grids(g, a, fx, fy, cx, cy, W, H) -> (C_R_Cg, grid, inv_grid)     :158-214 (not differentiable)
     torch.ops.vidc.plane_ransac_normal(normals, ids, slots, hyp_pix)          main.py:38-62 (+ the write-back of :157)
     torch.ops.vidc.plane_offset(homo, depth, slots, inlier_mask, counts, scratch)       main.py:68-101, 162-173
     torch.ops.vidc.plane_project_depth(homo, slots, inlier_mask, scratch, records, plane_depth)   main.py:110-127
@@ -395,6 +397,68 @@ def _warp_inv_backward(ctx, _grad_h, grad_z):
 
 
 torch.library.register_autograd("vidc::warp2dof_inv_rot_norm", _warp_inv_backward, setup_context=_warp_inv_setup)
+
+
+# ---- the forward warp in grid_sample's three interpolation modes (WARP_MODE_OPS) --------------------------------------------------------------
+@torch.library.custom_op("vidc::warp2dof_fwd_mode", mutates_args=(), device_types=_DEV)
+def warp2dof_fwd_mode(x: torch.Tensor, gravity: torch.Tensor, aligned: torch.Tensor, fx: float, fy: float, cx: float, cy: float,
+                      align_corners: bool, mode: int, rotate: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(Cg_H_C (B,3,3), warped x (B,C,H,W)) in interpolation mode 0 bilinear / 1 nearest / 2 bicubic -- warp_with_gravity_center_aligned(interp_mode);
+    with rotate (C == 3) the warped image is rotated by Cg_R_C per pixel -- warp_normal_image_with_gravity_center_aligned."""
+    wp = _warper(x, fx, fy, cx, cy, align_corners)
+    assert tuple(x.shape[-2:]) == (wp.H, wp.W) and x.dim() == 4
+    p = wp._params(gravity, aligned)
+    return p[:, 0:9].reshape(x.shape[0], 3, 3).clone(), _ops.warp2dof_fwd_mode(x, p, cx, cy, align_corners, mode, rotate)
+
+
+@warp2dof_fwd_mode.register_fake
+def _(x, gravity, aligned, fx, fy, cx, cy, align_corners, mode, rotate):
+    return x.new_empty((x.shape[0], 3, 3)), torch.empty_like(x)
+
+
+@torch.library.custom_op("vidc::warp2dof_fwd_mode_backward", mutates_args=(), device_types=_DEV)
+def warp2dof_fwd_mode_backward(dy: torch.Tensor, gravity: torch.Tensor, aligned: torch.Tensor, fx: float, fy: float, cx: float, cy: float,
+                               align_corners: bool, mode: int, rotate: bool) -> torch.Tensor:
+    """dx of warp2dof_fwd_mode: Cg_R_C^T with rotate, then the transposed gather of the mode (vidc_warp2dof_fwd_mode_backward)."""
+    wp = _warper(dy, fx, fy, cx, cy, align_corners)
+    assert tuple(dy.shape[-2:]) == (wp.H, wp.W)
+    return _ops.warp2dof_fwd_mode_backward(dy, wp._params(gravity, aligned), cx, cy, align_corners, mode, rotate)
+
+
+@warp2dof_fwd_mode_backward.register_fake
+def _(dy, gravity, aligned, fx, fy, cx, cy, align_corners, mode, rotate):
+    return torch.empty_like(dy)
+
+
+def _warp_mode_setup(ctx, inputs, output):
+    x, gravity, aligned, fx, fy, cx, cy, align_corners, mode, rotate = inputs
+    _no_geometry_grad(ctx, "warp2dof_fwd_mode", 1, 2)
+    ctx.save_for_backward(gravity, aligned)
+    ctx.args = (fx, fy, cx, cy, align_corners, mode, rotate)
+
+
+def _warp_mode_backward(ctx, _grad_h, grad_y):
+    gravity, aligned = ctx.saved_tensors
+    return (torch.ops.vidc.warp2dof_fwd_mode_backward(grad_y, gravity, aligned, *ctx.args),) + (None,) * 9
+
+
+torch.library.register_autograd("vidc::warp2dof_fwd_mode", _warp_mode_backward, setup_context=_warp_mode_setup)
+
+
+@torch.library.custom_op("vidc::warp2dof_grids", mutates_args=(), device_types=_DEV)
+def warp2dof_grids(gravity: torch.Tensor, aligned: torch.Tensor, fx: float, fy: float, cx: float, cy: float, W: int,
+                   H: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(C_R_Cg (B,3,3), grid (B,H,W,2), inverse grid (B,H,W,2)) -- Warping2DOFAlignment.image_sampler_forward_inverse; W, H must be the ones the
+    intrinsics give (ceil(2 cx), ceil(2 cy)).  Not differentiable (no autograd formula is registered: the geometry gets no gradient)."""
+    wp = _warper(gravity, fx, fy, cx, cy, False)
+    assert (W, H) == (wp.W, wp.H), "W, H must be ceil(2 cx), ceil(2 cy) = %d, %d" % (wp.W, wp.H)
+    return wp.image_sampler_forward_inverse(gravity, aligned)
+
+
+@warp2dof_grids.register_fake
+def _(gravity, aligned, fx, fy, cx, cy, W, H):
+    B = gravity.shape[0]
+    return gravity.new_empty((B, 3, 3)), gravity.new_empty((B, H, W, 2)), gravity.new_empty((B, H, W, 2))
 
 
 AFFINE_ILL_COND = 4.0       # kAffineIllCond of csrc/train.hip: a power of two, so the product below is exact in fp32 on either side
@@ -969,7 +1033,9 @@ TRAIN_BACKWARD_OPS = ("batch_norm_train_backward", "normalize_nchw_backward", "n
 # ModifiedFPN.forward_autograd, SurfaceNormalPrediction.forward_autograd and the depth loss; feature_mask_scale is its own backward
 NET_TRAIN_OPS = ("depth_l1_loss", "depth_l1_loss_with_grad", "feature_mask_scale", "add_rows")
 NET_TRAIN_BACKWARD_OPS = ("depth_l1_loss_backward", "add_rows_backward")
+# the forward warp in grid_sample's three interpolation modes with its backward, and the sampler grids (not differentiable)
+WARP_MODE_OPS = ("warp2dof_fwd_mode", "warp2dof_fwd_mode_backward", "warp2dof_grids")
 OPS = (("plane_ransac_normal", "plane_offset", "plane_project_depth", "plane_finalize", "enrich_scatter", "warp2dof_fwd", "warp2dof_inv_rot_norm", "conv2d_bn_act",
         "conv3x3_winograd", "stem_conv3x3s2", "maxpool3x3s2", "upsample_bilinear_ac", "head_conv1x1_upsample")
-       + BACKWARD_OPS + DORN_OPS + DORN_BACKWARD_OPS + TRAIN_OPS + TRAIN_BACKWARD_OPS + NET_TRAIN_OPS + NET_TRAIN_BACKWARD_OPS)
+       + BACKWARD_OPS + DORN_OPS + DORN_BACKWARD_OPS + TRAIN_OPS + TRAIN_BACKWARD_OPS + NET_TRAIN_OPS + NET_TRAIN_BACKWARD_OPS + WARP_MODE_OPS)
 RATIO_KEYS = ("D_1.05", "D_1.10", "D_1.25", "D_1.56", "D_1.95")      # depth_l1_loss's five ratio counts, as depth_printable_ratios names them
