@@ -66,7 +66,8 @@ int vidc_warp2dof_params(const float* gravity, const float* aligned, int B, floa
 
 /* Replaces warp_with_gravity_center_aligned (:108-156): y[b,c,Y,X] = bilinear(x[b,c], H^-1 (X/kw+px_min, Y/kh+py_min, 1)),
  * zero padding; align_corners selects grid_sample's convention (0 = what the oracle/reference do on torch>=1.3).
- * x, y: NCHW [B][C][H][W]. */
+ * x, y: NCHW [B][C][H][W].  Every entry of this section that takes an image refuses H * W >= 2^30 with VIDC_ERR_SHAPE (the kernels index
+ * pixels with int). */
 int vidc_warp2dof_fwd(const float* x, const float* params, float* y, int B, int C, int H, int W, float cx, float cy,
                       int align_corners, vidc_stream_t stream);
 
@@ -96,7 +97,7 @@ int vidc_warp2dof_inv_rot_norm_backward(const float* x, const float* dz, const f
  * warp_normal_image_with_gravity_center_aligned (:258-290): C == 3 and z = Cg_R_C y per pixel (:288) in the same store pass.  The sampling
  * position is vidc_warp2dof_fwd's; zero padding.  Nearest reads the pixel at (rint ix, rint iy), ties to even as torch's nearbyint; bicubic
  * is torch's grid_sampler_2d: A = -0.75, taps floor(ix) - 1 .. floor(ix) + 2 bounds-checked one by one, no coordinate clamping, the rows
- * summed one fmaf chain each and then the four row sums.  mode 0 without rotate gives the bits of vidc_warp2dof_fwd.
+ * summed one fmaf chain each and then the four row sums.  mode 0 without rotate is vidc_warp2dof_fwd: the same kernel through the same launcher.
  * x, y: NCHW [B][C][H][W]; `params`: the record of vidc_warp2dof_params (warp_with_homography, :292-310, runs mode 0 on a record the host
  * builds from the given homography). */
 int vidc_warp2dof_fwd_mode(const float* x, const float* params, float* y, int B, int C, int H, int W, float cx, float cy,
@@ -104,7 +105,7 @@ int vidc_warp2dof_fwd_mode(const float* x, const float* params, float* y, int B,
 /* dx of vidc_warp2dof_fwd_mode (:108-156 / :258-290 differentiated w.r.t. the image): with rotate dy is first multiplied by Cg_R_C^T, then
  * the transposed gather in the form of vidc_warp2dof_fwd_backward -- a thread owns a source pixel and walks the window of output pixels that
  * its support (one pixel either way for bilinear and nearest, two for bicubic) maps to, with the forward's own weights, in row-major order:
- * no atomics, bit-identical from run to run.  mode 0 without rotate gives the bits of vidc_warp2dof_fwd_backward. */
+ * no atomics, bit-identical from run to run.  mode 0 without rotate is vidc_warp2dof_fwd_backward: the same kernel. */
 int vidc_warp2dof_fwd_mode_backward(const float* dy, const float* params, float* dx, int B, int C, int H, int W, float cx, float cy,
                                     int align_corners, int mode, int rotate, vidc_stream_t stream);
 /* image_sampler_forward_inverse (:158-214) in one launch: grid / inv_grid (B,H,W,2) are the normalised sampling coordinates of the forward
@@ -311,8 +312,8 @@ int vidc_stem_conv3x3s2(const float* x, const float* w_oihw, float* y, int B, in
                         int relu, void* y_split, int split_ch0, vidc_stream_t stream);
 
 /* The same conv reading its input THROUGH the gravity-aligned forward warp (warp_with_gravity_center_aligned, :108-156, in front of
- * `self.resnet_pyramids(warped)`, surface_normal.py:163-164): the patch loader gathers x with the tap sets of vidc_warp2dof_fwd (same code,
- * same bits), the warped image is never stored.  x: NCHW [B][3][H][W]; warp_params: the records of vidc_warp2dof_params. */
+ * `self.resnet_pyramids(warped)`, surface_normal.py:163-164): the patch loader gathers x with the tap sets of vidc_warp2dof_fwd (one
+ * function), the warped image is never stored.  x: NCHW [B][3][H][W]; warp_params: the records of vidc_warp2dof_params. */
 int vidc_stem_conv3x3s2_warped(const float* x, const float* warp_params, const float* w_oihw, float* y, int B, int H, int W, int Cout, int ldy,
                                int relu, void* y_split, int split_ch0, float cx, float cy, int align_corners, vidc_stream_t stream);
 

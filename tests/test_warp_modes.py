@@ -432,3 +432,31 @@ def test_warp_with_homography_on_a_linear_ramp(geom, ac, which):
         dev = np.abs(y[0].cpu().numpy().astype(np.float64) - ramp(ix, iy))[:, inside].max()
         print("HOMOGRAPHY %-8s %-6s ac=%d max deviation inside %.3e over %.1f %% of the pixels" % (which, geom, ac, dev, 100 * inside.mean()))
         assert inside.mean() > 0.5 and dev <= 1e-4
+
+
+# ---- 10. image sizes past what the kernels' int pixel index holds ----------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_every_image_entry_refuses_2_to_the_30_pixels():
+    """H = W = 32768 is 2^30 pixels: every kernel indexes pixels with int, so every entry that takes an image answers VIDC_ERR_SHAPE before any
+    launch (the buffers are small and valid; nothing reads them).  vidc_warp2dof_fwd_backward is the control: it has refused this all along.
+    The refusal is all that stands between these calls and a launch over 2^30 pixels on 14 KB buffers: an entry that lost it would fault the
+    GPU here, not fail an assertion."""
+    from vi_depth_completion_amd import _lib as L
+    lib, st = L.lib(), L.current_stream()
+    big, ERR_SHAPE = 32768, -2                                      # VIDC_ERR_SHAPE (include/vidc.h)
+    buf = torch.ones(3 * 30 * 40, dtype=torch.float32, device="cuda")
+    out = torch.empty_like(buf)
+    p = _case("small", False, "b1").params
+    x, y, q = L.ptr(buf), L.ptr(out), L.ptr(p)
+    calls = {"vidc_warp2dof_fwd_backward": lambda H, W: lib.vidc_warp2dof_fwd_backward(x, q, y, 1, 3, H, W, 19.6, 14.7, 0, st),
+             "vidc_warp2dof_fwd": lambda H, W: lib.vidc_warp2dof_fwd(x, q, y, 1, 3, H, W, 19.6, 14.7, 0, st),
+             "vidc_warp2dof_inv_rot_norm": lambda H, W: lib.vidc_warp2dof_inv_rot_norm(x, q, y, 1, H, W, 19.6, 14.7, 0, 0, st)}
+    for name, call in calls.items():
+        out.fill_(-7.0)
+        assert call(big, big) == ERR_SHAPE, name
+        assert lib.vidc_last_error() == (name + ": bad shape").encode(), name
+        torch.cuda.synchronize()
+        assert (out == -7.0).all().item(), name                       # the refused call wrote nothing
+        assert call(30, 40) == 0, (name, lib.vidc_last_error())       # the same call at the buffers' own size goes through ...
+        torch.cuda.synchronize()
+        assert (out != -7.0).all().item(), name                       # ... and writes every element

@@ -110,20 +110,70 @@ struct Taps {
     float w00, w01, w10, w11;
 };
 
-__device__ inline Taps make_taps(float u, float v, float cx, float cy, int W, int H, int align_corners) {
-    float gx = (1.0f / ((float)W / 2)) * (u - cx);
-    float gy = (1.0f / ((float)H / 2)) * (v - cy);
-    float ix, iy;
-    if (align_corners) {
-        ix = ((gx + 1.f) / 2.f) * (float)(W - 1);
-        iy = ((gy + 1.f) / 2.f) * (float)(H - 1);
-    } else {
-        ix = ((gx + 1.f) * (float)W - 1.f) / 2.f;
-        iy = ((gy + 1.f) * (float)H - 1.f) / 2.f;
+// The warps' coordinate maps, each stated once; every tap set, the sampler grids and the fused stem's loader are composed from these four.
+// Forward map (warping_2dof_alignment.py:142-152): (u, v) = H^-1 (X / kw + px_min, Y / kh + py_min, 1) from the per-sample record p of
+// vidc_warp2dof_params.  The products and sums are not contracted; the divisions stand outside that block.
+__device__ inline float2 warp_fwd_uv(const float* __restrict__ p, int X, int Y) {
+    const float px_min = p[27], py_min = p[28], kw = p[29], kh = p[30];
+    float Xs, Ys, P0, P1, P2;
+    {
+#pragma clang fp contract(off)
+        Xs = (1.0f / kw) * (float)X + px_min;
+        Ys = (1.0f / kh) * (float)Y + py_min;
+        P0 = (p[18] * Xs + p[19] * Ys) + p[20];
+        P1 = (p[21] * Xs + p[22] * Ys) + p[23];
+        P2 = (p[24] * Xs + p[25] * Ys) + p[26];
     }
-    // keep NaN/inf and far-out coordinates harmless: they sample nothing
-    if (!(ix > -2.0f && ix < (float)W + 1.0f)) ix = -2.0f;
-    if (!(iy > -2.0f && iy < (float)H + 1.0f)) iy = -2.0f;
+    return make_float2(P0 / P2, P1 / P2);
+}
+
+// Inverse map (:236-247): (u, v) = (kw, kh) * (H (X, Y, 1) - bbox origin), all of it uncontracted.
+__device__ inline float2 warp_inv_uv(const float* __restrict__ p, int X, int Y) {
+#pragma clang fp contract(off)
+    const float px_min = p[27], py_min = p[28], kw = p[29], kh = p[30];
+    float P0 = (p[0] * (float)X + p[1] * (float)Y) + p[2];
+    float P1 = (p[3] * (float)X + p[4] * (float)Y) + p[5];
+    float P2 = (p[6] * (float)X + p[7] * (float)Y) + p[8];
+    return make_float2(kw * (P0 / P2 - px_min), kh * (P1 / P2 - py_min));
+}
+
+// (u, v) -> F.grid_sample's normalised pair
+__device__ inline float2 warp_grid_xy(float2 uv, float cx, float cy, int W, int H) {
+    float gx = (1.0f / ((float)W / 2)) * (uv.x - cx);
+    float gy = (1.0f / ((float)H / 2)) * (uv.y - cy);
+    return make_float2(gx, gy);
+}
+
+// ... -> the pixel position it samples at.  NaN / inf and far-out coordinates are put at `far`, where they sample nothing: -2 for the bilinear and
+// nearest taps, -3 for bicubic, whose taps floor(i) - 1 .. floor(i) + 2 would reach pixel 0 from -2 (with weight 0: harmless but for a non-finite
+// pixel).  Positions inside (-2, N + 1) keep their value: below -2 or from N + 1 on, no tap of any mode is inside the image.
+// The bits the warps have had since their goldens were recorded fuse g.x + 1 with the product behind g.x (warp_grid_xy) into one fma and keep
+// g.y + 1 a sum of its own: the compiler used to hoist the first sum out of the two branches below to its product and to leave the second in
+// them, an accident of how the branches' instructions lined up.  y1 is pinned here by a contract(off) block that the code did not have before (a
+// deliberate addition).  x1 is not pinned: it relies on this function and warp_grid_xy being inlined into one block under the build's
+// -ffp-contract=fast; tests/test_warp_modes.py and the stem's parity test hold the result to the bits.
+__device__ inline float2 grid_to_pixel(float2 g, int W, int H, int align_corners, float far) {
+    const float x1 = g.x + 1.f;
+    float y1, ix, iy;
+    {
+#pragma clang fp contract(off)
+        y1 = g.y + 1.f;
+    }
+    if (align_corners) {
+        ix = (x1 / 2.f) * (float)(W - 1);
+        iy = (y1 / 2.f) * (float)(H - 1);
+    } else {
+        ix = (x1 * (float)W - 1.f) / 2.f;
+        iy = (y1 * (float)H - 1.f) / 2.f;
+    }
+    if (!(ix > -2.0f && ix < (float)W + 1.0f)) ix = far;
+    if (!(iy > -2.0f && iy < (float)H + 1.0f)) iy = far;
+    return make_float2(ix, iy);
+}
+
+__device__ inline Taps make_taps(float u, float v, float cx, float cy, int W, int H, int align_corners) {
+    const float2 pos = grid_to_pixel(warp_grid_xy(make_float2(u, v), cx, cy, W, H), W, H, align_corners, -2.0f);
+    const float ix = pos.x, iy = pos.y;
     float fx0 = floorf(ix), fy0 = floorf(iy);
     int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
     float wx1 = ix - fx0, wx0 = (fx0 + 1.f) - ix;
@@ -153,21 +203,15 @@ __device__ inline float sample_nt(const float* __restrict__ plane, const Taps& t
     return fmaf(a11, t.w11, fmaf(a10, t.w10, fmaf(a01, t.w01, a00 * t.w00)));
 }
 
-// Tap set of output pixel (X, Y) of the gravity-aligned forward warp (warping_2dof_alignment.py:142-152): H^-1 (X / kw + px_min, Y / kh + py_min, 1)
-// from the per-sample record of vidc_warp2dof_params.  One definition for the stand-alone warp kernel (csrc/warp.hip) and for the stem conv
-// that gathers its input through the warp (csrc/pointwise.hip): the same bits either way.
+// Bilinear tap set of output pixel (X, Y) of the gravity-aligned forward warp and of the inverse warp.  One definition for the warp kernels
+// (csrc/warp.hip) and for the stem conv that gathers its input through the forward warp (csrc/pointwise.hip).
 __device__ inline Taps warp_fwd_taps(const float* __restrict__ p, int X, int Y, float cx, float cy, int W, int H, int align_corners) {
-    const float px_min = p[27], py_min = p[28], kw = p[29], kh = p[30];
-    float Xs, Ys, P0, P1, P2;
-    {
-#pragma clang fp contract(off)
-        Xs = (1.0f / kw) * (float)X + px_min;
-        Ys = (1.0f / kh) * (float)Y + py_min;
-        P0 = (p[18] * Xs + p[19] * Ys) + p[20];
-        P1 = (p[21] * Xs + p[22] * Ys) + p[23];
-        P2 = (p[24] * Xs + p[25] * Ys) + p[26];
-    }
-    return make_taps(P0 / P2, P1 / P2, cx, cy, W, H, align_corners);
+    const float2 uv = warp_fwd_uv(p, X, Y);
+    return make_taps(uv.x, uv.y, cx, cy, W, H, align_corners);
+}
+__device__ inline Taps warp_inv_taps(const float* __restrict__ p, int X, int Y, float cx, float cy, int W, int H, int align_corners) {
+    const float2 uv = warp_inv_uv(p, X, Y);
+    return make_taps(uv.x, uv.y, cx, cy, W, H, align_corners);
 }
 
 }  // namespace vidc

@@ -57,16 +57,22 @@ class Warping2DOFAlignment:
             raise ValueError("interp_mode must be 'bilinear', 'nearest' or 'bicubic', got %r" % (interp_mode,))
         return ops.WARP_MODES[interp_mode]
 
+    def _prepare(self, x, I_g, I_a, channels=None):
+        """What every gravity warp of an image starts with: the device and shape checks, then (the geometry record, the Cg_H_C it returns).
+        x is (B,C,H,W), or (B,H,W) with channels=None only: the channel check reads x.shape[1]."""
+        self._require_device(x)
+        assert x.shape[0] == I_g.shape[0] and (channels is None or x.shape[1] == channels)
+        assert tuple(x.shape[-2:]) == (self.H, self.W), "image must be %dx%d" % (self.H, self.W)
+        p = self._params(I_g, I_a)
+        return p, p[:, 0:9].reshape(x.shape[0], 3, 3).clone()
+
     def warp_with_gravity_center_aligned(self, x, I_g, I_a, interp_mode="bilinear"):
         mode = self._mode(interp_mode)
-        self._require_device(x)
+        p, Cg_H_C = self._prepare(x, I_g, I_a)
         squeeze = x.dim() == 3
         if squeeze:
             x = x.view(x.shape[0], 1, x.shape[1], x.shape[2])
-        assert x.shape[0] == I_g.shape[0]
-        assert tuple(x.shape[-2:]) == (self.H, self.W), "image must be %dx%d" % (self.H, self.W)
         x = x.contiguous().float()
-        p = self._params(I_g, I_a)
         B, Cc = x.shape[0], x.shape[1]
         if mode == 0:
             y = torch.empty_like(x)
@@ -74,31 +80,22 @@ class Warping2DOFAlignment:
                                               int(self.align_corners), L.current_stream()), "warp2dof_fwd")
         else:
             y = ops.warp2dof_fwd_mode(x, p, self.cx, self.cy, self.align_corners, mode)
-        Cg_H_C = p[:, 0:9].reshape(B, 3, 3).clone()
         return (Cg_H_C, y.view(B, self.H, self.W)) if squeeze else (Cg_H_C, y)
 
     def inverse_warp_normal_image_with_gravity_center_aligned(self, x, I_g, I_a, normalize=False):
-        self._require_device(x)
-        assert x.shape[0] == I_g.shape[0] and x.shape[1] == 3
-        assert tuple(x.shape[-2:]) == (self.H, self.W)
+        p, Cg_H_C = self._prepare(x, I_g, I_a, channels=3)
         x = x.contiguous().float()
-        p = self._params(I_g, I_a)
         z = torch.empty_like(x)
-        B = x.shape[0]
-        L.check(L.lib().vidc_warp2dof_inv_rot_norm(L.ptr(x), L.ptr(p), L.ptr(z), B, self.H, self.W, self.cx, self.cy,
+        L.check(L.lib().vidc_warp2dof_inv_rot_norm(L.ptr(x), L.ptr(p), L.ptr(z), x.shape[0], self.H, self.W, self.cx, self.cy,
                                                    int(self.align_corners), int(normalize), L.current_stream()),
                 "warp2dof_inv_rot_norm")
-        return p[:, 0:9].reshape(B, 3, 3).clone(), z
+        return Cg_H_C, z
 
     def warp_normal_image_with_gravity_center_aligned(self, x, I_g, I_a, interp_mode="bilinear"):
         """The forward companion of the inverse normal warp (:258-290): the gather of warp_with_gravity_center_aligned, then z = Cg_R_C y."""
         mode = self._mode(interp_mode)
-        self._require_device(x)
-        assert x.shape[0] == I_g.shape[0] and x.shape[1] == 3
-        assert tuple(x.shape[-2:]) == (self.H, self.W)
-        p = self._params(I_g, I_a)
-        z = ops.warp2dof_fwd_mode(x, p, self.cx, self.cy, self.align_corners, mode, rotate=True)
-        return p[:, 0:9].reshape(x.shape[0], 3, 3).clone(), z
+        p, Cg_H_C = self._prepare(x, I_g, I_a, channels=3)
+        return Cg_H_C, ops.warp2dof_fwd_mode(x, p, self.cx, self.cy, self.align_corners, mode, rotate=True)
 
     def image_sampler_forward_inverse(self, I_g, I_a):
         """(C_R_Cg_ret, grid_sampler, inv_grid_sampler) (:158-214): the sampling grids of the two warps as F.grid_sample takes them, and

@@ -361,26 +361,26 @@ def _scratch(nbytes, device):
     return torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
 
 
+def _warp_call(entry, tensors, params, tail, channels=True):
+    """One warp entry of libvidc.so on NCHW float images: entry(tensors..., params, out, B, [C,] H, W, *tail, stream).  channels=False: the entry
+    takes no C (the 3-channel inverse warp).  Returns out, shaped like the images."""
+    _dev(*tensors, params)
+    tensors = [t.contiguous().float() for t in tensors]
+    B, Cc, H, W = tensors[0].shape
+    out = torch.empty_like(tensors[0])
+    dims = (B, Cc, H, W) if channels else (B, H, W)
+    L.check(getattr(L.lib(), entry)(*[L.ptr(t) for t in tensors], L.ptr(params), L.ptr(out), *dims, *tail, L.current_stream()), entry[len("vidc_"):])
+    return out
+
+
 def warp2dof_fwd_backward(dy, params, cx, cy, align_corners):
     """dx of vidc_warp2dof_fwd: dy (B,C,H,W), params the (B,32) record of vidc_warp2dof_params."""
-    _dev(dy, params)
-    dy = dy.contiguous().float()
-    B, Cc, H, W = dy.shape
-    dx = torch.empty_like(dy)
-    L.check(L.lib().vidc_warp2dof_fwd_backward(L.ptr(dy), L.ptr(params), L.ptr(dx), B, Cc, H, W, float(cx), float(cy), int(align_corners),
-                                               L.current_stream()), "warp2dof_fwd_backward")
-    return dx
+    return _warp_call("vidc_warp2dof_fwd_backward", [dy], params, (float(cx), float(cy), int(align_corners)))
 
 
 def warp2dof_inv_rot_norm_backward(x, dz, params, cx, cy, align_corners, normalize):
     """dx of vidc_warp2dof_inv_rot_norm: x the forward's input (B,3,H,W), dz the gradient of its output."""
-    _dev(x, dz, params)
-    x, dz = x.contiguous().float(), dz.contiguous().float()
-    B, _c, H, W = x.shape
-    dx = torch.empty_like(x)
-    L.check(L.lib().vidc_warp2dof_inv_rot_norm_backward(L.ptr(x), L.ptr(dz), L.ptr(params), L.ptr(dx), B, H, W, float(cx), float(cy),
-                                                        int(align_corners), int(normalize), L.current_stream()), "warp2dof_inv_rot_norm_backward")
-    return dx
+    return _warp_call("vidc_warp2dof_inv_rot_norm_backward", [x, dz], params, (float(cx), float(cy), int(align_corners), int(normalize)), channels=False)
 
 
 WARP_MODES = {"bilinear": 0, "nearest": 1, "bicubic": 2}      # VIDC_WARP_BILINEAR / _NEAREST / _BICUBIC: F.grid_sample's `mode` strings
@@ -389,24 +389,12 @@ WARP_MODES = {"bilinear": 0, "nearest": 1, "bicubic": 2}      # VIDC_WARP_BILINE
 def warp2dof_fwd_mode(x, params, cx, cy, align_corners, mode, rotate=False):
     """vidc_warp2dof_fwd_mode: the forward warp of x (B,C,H,W) in interpolation mode 0 / 1 / 2 (WARP_MODES); rotate (C == 3): z = Cg_R_C y per
     pixel.  params: the (B,32) record of vidc_warp2dof_params."""
-    _dev(x, params)
-    x = x.contiguous().float()
-    B, Cc, H, W = x.shape
-    y = torch.empty_like(x)
-    L.check(L.lib().vidc_warp2dof_fwd_mode(L.ptr(x), L.ptr(params), L.ptr(y), B, Cc, H, W, float(cx), float(cy), int(align_corners), int(mode),
-                                           int(rotate), L.current_stream()), "warp2dof_fwd_mode")
-    return y
+    return _warp_call("vidc_warp2dof_fwd_mode", [x], params, (float(cx), float(cy), int(align_corners), int(mode), int(rotate)))
 
 
 def warp2dof_fwd_mode_backward(dy, params, cx, cy, align_corners, mode, rotate=False):
     """dx of vidc_warp2dof_fwd_mode: dy (B,C,H,W), the gradient of its output."""
-    _dev(dy, params)
-    dy = dy.contiguous().float()
-    B, Cc, H, W = dy.shape
-    dx = torch.empty_like(dy)
-    L.check(L.lib().vidc_warp2dof_fwd_mode_backward(L.ptr(dy), L.ptr(params), L.ptr(dx), B, Cc, H, W, float(cx), float(cy), int(align_corners),
-                                                    int(mode), int(rotate), L.current_stream()), "warp2dof_fwd_mode_backward")
-    return dx
+    return _warp_call("vidc_warp2dof_fwd_mode_backward", [dy], params, (float(cx), float(cy), int(align_corners), int(mode), int(rotate)))
 
 
 def warp2dof_grids(params, H, W, cx, cy):

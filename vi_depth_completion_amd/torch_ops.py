@@ -339,6 +339,29 @@ def _no_geometry_grad(ctx, what, i_gravity, i_aligned):
                            "min-max); detach them" % what)
 
 
+def _register_warp_autograd(name, backward_op, n_args, saves_x=False):
+    """The autograd formula of warp operator `name` -- (x, gravity, aligned, n_args plain arguments) -> (Cg_H_C, image): the gradient of the image
+    through torch.ops.vidc.<backward_op>(grad, gravity, aligned, *arguments), none for anything else.  saves_x: the backward operator takes x in
+    front, which is kept only if the last argument (normalize) is set -- the linear form reads no x and gets the gradient in its place."""
+    def setup(ctx, inputs, output):
+        x, gravity, aligned = inputs[:3]
+        _no_geometry_grad(ctx, name, 1, 2)
+        ctx.args = tuple(inputs[3:])
+        assert len(ctx.args) == n_args
+        saved = (gravity, aligned)
+        if saves_x:
+            saved = (x if ctx.args[-1] else x.new_empty(0),) + saved      # (the linear form reads no x)
+        ctx.save_for_backward(*saved)
+
+    def backward(ctx, _grad_h, grad):
+        *x, gravity, aligned = ctx.saved_tensors
+        if x and not x[0].numel():
+            x = [grad]
+        return (getattr(torch.ops.vidc, backward_op)(*x, grad, gravity, aligned, *ctx.args),) + (None,) * (2 + n_args)
+
+    torch.library.register_autograd("vidc::" + name, backward, setup_context=setup)
+
+
 @torch.library.custom_op("vidc::warp2dof_fwd_backward", mutates_args=(), device_types=_DEV)
 def warp2dof_fwd_backward(dy: torch.Tensor, gravity: torch.Tensor, aligned: torch.Tensor, fx: float, fy: float, cx: float, cy: float,
                           align_corners: bool) -> torch.Tensor:
@@ -353,19 +376,7 @@ def _(dy, gravity, aligned, fx, fy, cx, cy, align_corners):
     return torch.empty_like(dy)
 
 
-def _warp_fwd_setup(ctx, inputs, output):
-    x, gravity, aligned, fx, fy, cx, cy, align_corners = inputs
-    _no_geometry_grad(ctx, "warp2dof_fwd", 1, 2)
-    ctx.save_for_backward(gravity, aligned)
-    ctx.args = (fx, fy, cx, cy, align_corners)
-
-
-def _warp_fwd_backward(ctx, _grad_h, grad_y):
-    gravity, aligned = ctx.saved_tensors
-    return (torch.ops.vidc.warp2dof_fwd_backward(grad_y, gravity, aligned, *ctx.args),) + (None,) * 7
-
-
-torch.library.register_autograd("vidc::warp2dof_fwd", _warp_fwd_backward, setup_context=_warp_fwd_setup)
+_register_warp_autograd("warp2dof_fwd", "warp2dof_fwd_backward", 5)
 
 
 @torch.library.custom_op("vidc::warp2dof_inv_rot_norm_backward", mutates_args=(), device_types=_DEV)
@@ -382,21 +393,7 @@ def _(x, dz, gravity, aligned, fx, fy, cx, cy, align_corners, normalize):
     return torch.empty_like(x)
 
 
-def _warp_inv_setup(ctx, inputs, output):
-    x, gravity, aligned, fx, fy, cx, cy, align_corners, normalize = inputs
-    _no_geometry_grad(ctx, "warp2dof_inv_rot_norm", 1, 2)
-    ctx.save_for_backward(x if normalize else x.new_empty(0), gravity, aligned)      # (the linear form reads no x)
-    ctx.args = (fx, fy, cx, cy, align_corners, normalize)
-
-
-def _warp_inv_backward(ctx, _grad_h, grad_z):
-    x, gravity, aligned = ctx.saved_tensors
-    if not x.numel():
-        x = grad_z
-    return (torch.ops.vidc.warp2dof_inv_rot_norm_backward(x, grad_z, gravity, aligned, *ctx.args),) + (None,) * 8
-
-
-torch.library.register_autograd("vidc::warp2dof_inv_rot_norm", _warp_inv_backward, setup_context=_warp_inv_setup)
+_register_warp_autograd("warp2dof_inv_rot_norm", "warp2dof_inv_rot_norm_backward", 6, saves_x=True)
 
 
 # ---- the forward warp in grid_sample's three interpolation modes (WARP_MODE_OPS) --------------------------------------------------------------
@@ -430,19 +427,7 @@ def _(dy, gravity, aligned, fx, fy, cx, cy, align_corners, mode, rotate):
     return torch.empty_like(dy)
 
 
-def _warp_mode_setup(ctx, inputs, output):
-    x, gravity, aligned, fx, fy, cx, cy, align_corners, mode, rotate = inputs
-    _no_geometry_grad(ctx, "warp2dof_fwd_mode", 1, 2)
-    ctx.save_for_backward(gravity, aligned)
-    ctx.args = (fx, fy, cx, cy, align_corners, mode, rotate)
-
-
-def _warp_mode_backward(ctx, _grad_h, grad_y):
-    gravity, aligned = ctx.saved_tensors
-    return (torch.ops.vidc.warp2dof_fwd_mode_backward(grad_y, gravity, aligned, *ctx.args),) + (None,) * 9
-
-
-torch.library.register_autograd("vidc::warp2dof_fwd_mode", _warp_mode_backward, setup_context=_warp_mode_setup)
+_register_warp_autograd("warp2dof_fwd_mode", "warp2dof_fwd_mode_backward", 7)
 
 
 @torch.library.custom_op("vidc::warp2dof_grids", mutates_args=(), device_types=_DEV)
