@@ -743,6 +743,22 @@ int vidc_bn_train_backward(const float* dy, const float* x, const float* y_relu,
 int vidc_bn_train_backward_t(const float* dy, const float* x, const float* y_relu, float* dx, long long M, int C, int lddy, int ldx, int ldy,
                              int lddx, const float* gamma, const float* save_mean, const float* save_rstd, float* dgamma, float* dbeta,
                              void* dx_bf16, void* dx_bf16_t, int Mp, void* scratch, vidc_stream_t stream);
+/* nn.BatchNorm2d in eval() mode / F.batch_norm(training=False) inside a training step (a frozen BatchNorm; + the Bottleneck tail and the ReLU
+ * as above): y = relu?((x - running_mean) * rstd * gamma + beta + residual) with rstd = 1 / sqrt(running_var + eps) formed in fp64 and
+ * rounded once; the arithmetic of the train-mode apply pass (a = fl(rstd * gamma), y = x * a + (beta - running_mean * a)).  x and residual
+ * (may be NULL) may be channel slices (ldx, ldr >= C).  One launch; nothing but the C channels of each y row is written -- the running
+ * statistics are read only.  No scratch. */
+int vidc_bn_eval_forward_add(const float* x, float* y, long long M, int C, int ldx, int ldy, const float* gamma, const float* beta,
+                             const float* running_mean, const float* running_var, float eps, int relu, const float* residual, int ldr,
+                             vidc_stream_t stream);
+/* Its backward.  With g' = dy * (y_relu > 0) (y_relu: the forward output when a ReLU followed, else NULL): dx = g' * gamma * rstd,
+ * dgamma = sum g' * xh with xh = (x - running_mean) * rstd, dbeta = sum g' (fp64 chunk partials reduced in a fixed order: no atomics, the
+ * same bits on every run).  dx does not depend on the sums, so the pass that accumulates them writes it: two launches.  dgamma == dbeta ==
+ * NULL (frozen affine parameters; they come together): one elementwise launch, x and scratch may be NULL and are not read.  dx == NULL: the
+ * sums only (gamma may then be NULL).  scratch: vidc_train_scratch_bytes(M, C). */
+int vidc_bn_eval_backward(const float* dy, const float* x, const float* y_relu, float* dx, long long M, int C, int lddy, int ldx, int ldy,
+                          int lddx, const float* gamma, const float* running_mean, const float* running_var, float eps, float* dgamma,
+                          float* dbeta, void* scratch, vidc_stream_t stream);
 /* out[c] = sum over rows of dy[.][c]: the bias gradient of a convolution. */
 int vidc_colsum(const float* dy, long long M, int C, int ld, float* out, void* scratch, vidc_stream_t stream);
 /* y = a + b, ReLU optional (Bottleneck: relu(bn3(conv3(.)) + identity); decoder: z1 + z2 + z3 + z4). */

@@ -9,14 +9,21 @@ three regions of an autograd step: forward + loss, backward, Adam.
     python tools/net_train_step_bench.py --net depth --batch 8 --steps 5                          # one JSON line
     python tools/net_train_step_bench.py --net normal --batch 8 --use-mask                        # SurfaceNormalPrediction(use_mask=True): autograd only
     python tools/net_train_step_bench.py --net dorn --batch 8 --precisions 0                      # SurfaceNormalDORN, dropout_seed 1234: autograd only
+    python tools/net_train_step_bench.py --net normal --precisions 0 --no-trainer --frozen-bn all # fine-tuning with frozen BatchNorm beside the train-mode step
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o net -- python tools/net_train_step_bench.py --net depth --precisions 0 --no-trainer
     python tools/net_train_step_bench.py --kernel-stats OUT/.../net_kernel_stats.csv              # the per-kernel share table of that run (no GPU needed)
 
 The share table groups the kernels of the profiled process (warm-up steps included: they are the same steps) into what the step spends its GPU
 time on -- convs, BatchNorm passes, per-call weight packing, weight-gradient operands, the transposed conv epilogue, torch's own kernels (Adam, cat,
-zero_grad) -- and lists the kernels above 1 %."""
+zero_grad) -- and lists the kernels above 1 %.
+
+--frozen-bn backbone|all puts the BatchNorm2d modules of the ResNet backbones / of the whole network into eval() mode (fine-tuning with frozen BatchNorm:
+batch_norm_eval instead of batch_norm_train) and times that step beside the train-mode one ("none", today's step) in the same process on the same inputs,
+each with the share of the step's GPU time its BatchNorm operators take, forward and backward (HIP events around the four operators' entry points in
+`--steps` further steps, so the timed steps carry no extra events)."""
 import argparse
 import csv
+import gc
 import json
 import os
 import sys
@@ -28,7 +35,10 @@ sys.path.insert(0, ROOT)
 DTYPES = {0: "f32 (fp32 MFMA fwd / dgrad / wgrad)", 1: "f32+bf16x3 forward, fp32 dgrad / wgrad"}
 NETS = {"depth": ("ModifiedFPN", "depth_l1_loss"), "normal": ("SurfaceNormalPrediction", "normal_l1_loss"), "dorn": ("SurfaceNormalDORN", "normal_l1_loss")}
 
-GROUPS = (("BatchNorm passes", ("chan_partial_kernel", "chan_final_kernel", "bn_apply", "bn_bwd_apply")),
+BACKBONES = ("resnet_rgb.", "resnet_normal.", "resnet_depth.", "resnet_pyramids.", "feature_extractor.")
+BN_ENTRIES = ("batch_norm_train", "batch_norm_train_backward", "batch_norm_eval", "batch_norm_eval_backward")      # of vi_depth_completion_amd.ops
+
+GROUPS = (("BatchNorm passes", ("chan_partial_kernel", "chan_final_kernel", "bn_apply", "bn_bwd_apply", "bn_eval_")),
           ("per-call weight packing", ("pack_weight", "pack_batched_kernel")),
           ("weight-gradient operands / permute", ("im2col_t", "wgrad_permute_kernel", "transpose_bf16_kernel")),
           ("transposed conv epilogue", ("affine_act_bwd_kernel",)),
@@ -75,6 +85,50 @@ def timed(step, steps, warmup, events=None):
     return 1e3 * dt / steps, 1e3 * t_enq / steps, warm + [round(float(x), 6) for x in losses]
 
 
+def freeze_batch_norms(cnn, which):
+    """--frozen-bn: eval() on the BatchNorm2d modules of the backbones ("backbone") or of the whole network ("all"); the count."""
+    import torch
+    n = 0
+    for name, m in cnn.named_modules():
+        if isinstance(m, torch.nn.BatchNorm2d) and (which == "all" or name.startswith(BACKBONES)):
+            m.eval()
+            n += 1
+    return n
+
+
+def batch_norm_share(step, steps):
+    """(ms per step inside the BatchNorm operators, share of the step's GPU time): `steps` further steps with a HIP event pair around every call of the
+    BatchNorm entry points of vi_depth_completion_amd.ops (the stream is in order: a pair brackets exactly the kernels the call launched)."""
+    import torch
+    from vi_depth_completion_amd import ops
+    pairs, real = [], {n: getattr(ops, n) for n in BN_ENTRIES}
+
+    def bracket(fn):
+        def call(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = fn(*a, **k)
+            e1.record()
+            pairs.append((e0, e1))
+            return r
+        return call
+
+    ends = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for n, fn in real.items():
+        setattr(ops, n, bracket(fn))
+    try:
+        ends[0].record()
+        for _ in range(steps):
+            step(None)
+        ends[1].record()
+        torch.cuda.synchronize()
+    finally:
+        for n, fn in real.items():
+            setattr(ops, n, fn)
+    bn_ms = sum(a.elapsed_time(b) for a, b in pairs)
+    return round(bn_ms / steps, 2), round(bn_ms / ends[0].elapsed_time(ends[1]), 4), len(pairs) // steps
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--net", choices=tuple(NETS), default="depth")
@@ -83,6 +137,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--precisions", default="0,1", help="the convs' arithmetic of the autograd steps to time: 0 exact fp32, 1 bf16x3 (default: both)")
     ap.add_argument("--use-mask", action="store_true", help="--net normal: SurfaceNormalPrediction(use_mask=True), which only the autograd step trains")
+    ap.add_argument("--frozen-bn", choices=("none", "backbone", "all"), default="none",
+                    help="BatchNorm2d modules to put into eval() mode (frozen); not none: the train-mode step is timed beside it, both with their BatchNorm share")
     ap.add_argument("--no-trainer", action="store_true", help="skip the trainer's step (a profile of the autograd step alone)")
     ap.add_argument("--kernel-stats", help="a rocprofv3 --kernel-trace --stats CSV of a run of this script: print its share table and exit")
     args = ap.parse_args()
@@ -122,8 +178,10 @@ def main():
 
     result = {"metric": "%s autograd training step" % NETS[args.net][0], "unit": "ms/step", "n_gpus": 1,
               "batch_per_gpu": B, "use_mask": bool(args.use_mask), "autograd": {}}
-    for precision in [int(p) for p in args.precisions.split(",") if p != ""]:
+    settings = ["none"] if args.frozen_bn == "none" else ["none", args.frozen_bn]
+    for precision, frozen in [(int(p), f) for p in args.precisions.split(",") if p != "" for f in settings]:
         cnn = network()
+        n_frozen = freeze_batch_norms(cnn, frozen) if frozen != "none" else 0
         optimizer = torch.optim.Adam(cnn.parameters(), lr=1e-4)
         ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(args.steps)]
 
@@ -143,10 +201,18 @@ def main():
         with torch.enable_grad():
             ms, enq, losses = timed(step, args.steps, args.warmup, ev)
         region = lambda a, c: round(sum(e[a].elapsed_time(e[c]) for e in ev) / args.steps, 2)
-        result["autograd"][str(precision)] = {"ms_per_step": round(ms, 1), "frames_per_s": round(1e3 * B / ms, 1), "host_enqueue_ms_per_step": round(enq, 1),
-                                              "forward_loss_ms": region(0, 1), "backward_ms": region(1, 2), "adam_ms": region(2, 3), "dtype": DTYPES[precision],
-                                              "losses": losses, "peak_memory_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
+        key = str(precision) if frozen == "none" else "%d frozen-bn=%s" % (precision, frozen)
+        result["autograd"][key] = {"ms_per_step": round(ms, 1), "frames_per_s": round(1e3 * B / ms, 1), "host_enqueue_ms_per_step": round(enq, 1),
+                                   "forward_loss_ms": region(0, 1), "backward_ms": region(1, 2), "adam_ms": region(2, 3), "dtype": DTYPES[precision],
+                                   "losses": losses, "peak_memory_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
+        if args.frozen_bn != "none":
+            with torch.enable_grad():
+                bn_ms, share, calls = batch_norm_share(step, args.steps)
+            result["autograd"][key].update(frozen_batch_norms=n_frozen, batch_norm_ms=bn_ms, batch_norm_share=share, batch_norm_calls_per_step=calls)
+            print("%s precision %d frozen-bn=%-8s %7.1f ms/step (forward+loss %.1f, backward %.1f), BatchNorm operators %.2f ms = %.1f %% of the step's GPU time"
+                  % (NETS[args.net][0], precision, frozen, ms, region(0, 1), region(1, 2), bn_ms, 100 * share))
         del cnn, optimizer, step
+        gc.collect()                            # (the module holds reference cycles: without this the next setting's peak memory counts this network too)
         torch.cuda.empty_cache()
     if not args.no_trainer and not args.use_mask and args.net != "dorn":
         with torch.no_grad():

@@ -294,6 +294,105 @@ bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x, c
     bn_bwd_row(r, c, dy, lddy, x, ldx, y, ldy, dx, lddx, dx_bf16, C, mu, rs, gs, m1, m2, o);
 }
 
+// ---- BatchNorm in eval() mode (frozen: the running statistics are read, never written) --------------------------------------------------
+// invstd of a frozen channel: 1 / sqrt(running_var + eps) formed in fp64 and rounded once, by ONE thread per channel and workgroup (an fp64
+// sqrt and division per row quad would make these HBM-bound passes compute-bound); a workgroup then shares its 64 channels' constants in LDS.
+__device__ __forceinline__ float bn_eval_rstd(float var, float eps) { return (float)(1.0 / sqrt((double)var + (double)eps)); }
+
+// y = relu?((x - running_mean) * rstd * gamma + beta + res): bn_apply_row with alpha = fl(rstd * gamma), bb = fl(beta - fl(running_mean * alpha)),
+// the arithmetic of bn_apply_kernel on the running statistics.  64 rows x 64 channels per workgroup (16 channel quads x 16 row-lanes, 4 rows each).
+__global__ void __launch_bounds__(TT)
+bn_eval_apply_kernel(const float* __restrict__ x, float* __restrict__ y, long long M, int C, int ldx, int ldy, const float* __restrict__ running_mean,
+                     const float* __restrict__ running_var, float eps, const float* __restrict__ gamma, const float* __restrict__ beta, int relu,
+                     const float* __restrict__ res, int ldr) {
+    __shared__ float alpha_s[64], bb_s[64];
+    const int c0 = blockIdx.y * 64;
+    const long long m0 = (long long)blockIdx.x * 64;
+    if (threadIdx.x < 64 && c0 + threadIdx.x < C) {
+        const int cc = c0 + threadIdx.x;
+        const float a = bn_eval_rstd(running_var[cc], eps) * gamma[cc];
+        alpha_s[threadIdx.x] = a;
+        bb_s[threadIdx.x] = beta[cc] - running_mean[cc] * a;
+    }
+    __syncthreads();
+    const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    const int c = c0 + cq * 4;
+    if (c >= C) return;
+    float alpha[4], bb[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { alpha[k] = alpha_s[cq * 4 + k]; bb[k] = bb_s[cq * 4 + k]; }
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+        const long long r = m0 + rl + 16 * rr;
+        if (r < M) bn_apply_row(r, c, x, ldx, res, ldr, y, ldy, nullptr, C, alpha, bb, relu);
+    }
+}
+
+// The backward of the frozen form: g' = dy * (y > 0) (y != NULL), dx = g' * gs with gs = fl(gamma * rstd) -- no reduction behind it -- and, SUMS,
+// the chunk sums of dbeta = S g' and dgamma = S g' * xh in chan_partial_kernel<1>'s grid, block layout, operands (bn_bwd_operands) and summation
+// order, which chan_final_kernel<FinalParamGrad> then adds up: the pass that accumulates them writes dx (dx == NULL: sums only).  !SUMS: x is not
+// read, nothing but dx is written, and the rows are split over blockIdx.x (no chunk grid: blockIdx.y could not count the row blocks of a large map).
+template <bool SUMS>
+__global__ void __launch_bounds__(TT)
+bn_eval_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ dx, long long M, int C,
+                   int lddy, int ldx, int ldy, int lddx, const float* __restrict__ running_mean, const float* __restrict__ running_var, float eps,
+                   const float* __restrict__ gamma, int rows_per_chunk, double* __restrict__ partial) {
+    __shared__ double red[SUMS ? 2 : 1][SUMS ? 16 : 1][64];
+    __shared__ float mu_s[64], rs_s[64], gs_s[64];
+    const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    const int cblk = SUMS ? blockIdx.x : blockIdx.y, chunk = SUMS ? blockIdx.y : blockIdx.x;
+    const int c = cblk * 64 + cq * 4;
+    const long long r0 = (long long)chunk * rows_per_chunk, r1 = min(M, r0 + rows_per_chunk);
+    if (threadIdx.x < 64 && cblk * 64 + threadIdx.x < C) {
+        const int cc = cblk * 64 + threadIdx.x;
+        const float rs = bn_eval_rstd(running_var[cc], eps);
+        mu_s[threadIdx.x] = running_mean[cc];
+        rs_s[threadIdx.x] = rs;
+        gs_s[threadIdx.x] = dx ? gamma[cc] * rs : 0.f;
+    }
+    __syncthreads();
+    double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
+    if (c < C) {
+        float mu[4], rs[4], gs[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { mu[k] = mu_s[cq * 4 + k]; rs[k] = rs_s[cq * 4 + k]; gs[k] = gs_s[cq * 4 + k]; }
+        for (long long r = r0 + rl; r < r1; r += 16) {
+            float g[4];
+            load4(dy + r * lddy + c, g);
+            if (SUMS) {
+                float xh[4];
+                bn_bwd_operands(g, xh, r, c, x, ldx, y, ldy, mu, rs);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { s0[k] += (double)g[k]; s1[k] += (double)g[k] * (double)xh[k]; }
+            } else if (y) {
+                float yv[4];
+                load4(y + r * ldy + c, yv);
+                relu_mask4(g, yv);
+            }
+            if (dx) {
+                float o[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] = g[k] * gs[k];
+                store4(dx + r * lddx + c, o);
+            }
+        }
+    }
+    if constexpr (SUMS) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { red[0][rl][cq * 4 + k] = s0[k]; red[1][rl][cq * 4 + k] = s1[k]; }
+        __syncthreads();
+        if (threadIdx.x < 128) {                   // chan_partial_kernel's: 64 channels x 2 sums; row-lanes added in order 0..15
+            const int q = threadIdx.x >> 6, l = threadIdx.x & 63, cc = cblk * 64 + l;
+            if (cc < C) {
+                double t = 0.0;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) t += red[q][j][l];
+                partial[((size_t)chunk * 2 + q) * C + cc] = t;
+            }
+        }
+    }
+}
+
 // bn_bwd_row on 64 pixels x 64 channels per workgroup, which ALSO writes the transpose of dx as plain bf16 rows [C][Mp] (zero for
 // m >= M): dx of the BatchNorm behind a conv is that conv's dY, and its weight-gradient GEMM reads dY^T in exactly this format
 // (vidc_im2col_transposed(..., KH = KW = 1, split = 2) -- one launch and one pass over dY per conv that this kernel makes unnecessary).
@@ -1287,6 +1386,46 @@ extern "C" int vidc_bn_train_backward(const float* dy, const float* x, const flo
                                       int lddx, const float* gamma, const float* save_mean, const float* save_rstd, float* dgamma, float* dbeta,
                                       void* dx_bf16, void* scratch, vidc_stream_t stream) {
     return vidc_bn_train_backward_t(dy, x, y_relu, dx, M, C, lddy, ldx, ldy, lddx, gamma, save_mean, save_rstd, dgamma, dbeta, dx_bf16, nullptr, 0, scratch, stream);
+}
+
+// nn.BatchNorm2d in eval() mode inside a training step (a frozen BatchNorm): one launch, nothing but y written.
+extern "C" int vidc_bn_eval_forward_add(const float* x, float* y, long long M, int C, int ldx, int ldy, const float* gamma, const float* beta,
+                                        const float* running_mean, const float* running_var, float eps, int relu, const float* residual, int ldr,
+                                        vidc_stream_t stream) {
+    VIDC_REQUIRE(x && y && gamma && beta && running_mean && running_var, VIDC_ERR_NULL, "vidc_bn_eval_forward_add: null pointer");
+    VIDC_REQUIRE(M > 0 && M < (1ll << 36) && C > 0 && C % 4 == 0 && ldx >= C && ldy >= C && ldx % 4 == 0 && ldy % 4 == 0 &&
+                 (!residual || (ldr >= C && ldr % 4 == 0)), VIDC_ERR_SHAPE, "vidc_bn_eval_forward_add: bad shape");
+    hipLaunchKernelGGL(bn_eval_apply_kernel, dim3((unsigned)((M + 63) / 64), (C + 63) / 64), dim3(TT), 0, vidc::as_stream(stream), x, y, M, C, ldx, ldy,
+                       running_mean, running_var, eps, gamma, beta, relu, residual, ldr);
+    VIDC_CHECK_LAUNCH("bn_eval_forward");
+    return VIDC_OK;
+}
+
+// Its backward: the sums (dgamma and dbeta, both or neither) and dx are each optional; without the sums it is one elementwise launch that reads
+// neither x nor the scratch, with them the pass over the chunks writes dx as well and chan_final_kernel adds the chunk sums up (two launches).
+extern "C" int vidc_bn_eval_backward(const float* dy, const float* x, const float* y_relu, float* dx, long long M, int C, int lddy, int ldx, int ldy,
+                                     int lddx, const float* gamma, const float* running_mean, const float* running_var, float eps, float* dgamma,
+                                     float* dbeta, void* scratch, vidc_stream_t stream) {
+    const bool sums = dgamma || dbeta;
+    VIDC_REQUIRE(dy && running_mean && running_var && (!dgamma == !dbeta) && (dx || sums) && (!dx || gamma) && (!sums || (x && scratch)), VIDC_ERR_NULL,
+                 "vidc_bn_eval_backward: null pointer (dgamma and dbeta come together; x and scratch are read for them only, gamma for dx only)");
+    VIDC_REQUIRE(M > 0 && M < (1ll << 36) && C > 0 && C % 4 == 0 && lddy >= C && lddy % 4 == 0 && (!x || (ldx >= C && ldx % 4 == 0)) &&
+                 (!dx || (lddx >= C && lddx % 4 == 0)) && (!y_relu || (ldy >= C && ldy % 4 == 0)), VIDC_ERR_SHAPE, "vidc_bn_eval_backward: bad shape");
+    hipStream_t st = vidc::as_stream(stream);
+    if (!sums) {
+        hipLaunchKernelGGL(bn_eval_bwd_kernel<false>, dim3((unsigned)((M + 63) / 64), (C + 63) / 64), dim3(TT), 0, st, dy, (const float*)nullptr, y_relu, dx, M, C,
+                           lddy, 0, ldy, lddx, running_mean, running_var, eps, gamma, 64, (double*)nullptr);
+        VIDC_CHECK_LAUNCH("bn_eval_backward (dx only)");
+        return VIDC_OK;
+    }
+    const int nch = chunks_for(M, C);
+    double* partial = reinterpret_cast<double*>(scratch);
+    double* sums_d = partial + (size_t)nch * 2 * C;
+    hipLaunchKernelGGL(bn_eval_bwd_kernel<true>, dim3((C + 63) / 64, nch), dim3(TT), 0, st, dy, x, y_relu, dx, M, C, lddy, ldx, ldy, lddx, running_mean,
+                       running_var, eps, gamma, rows_for(M, C), partial);
+    hipLaunchKernelGGL(chan_final_kernel<FinalParamGrad>, dim3((C + 7) / 8), dim3(TT), 0, st, partial, nch, C, sums_d, FinalParamGrad{dgamma, dbeta});
+    VIDC_CHECK_LAUNCH("bn_eval_backward");
+    return VIDC_OK;
 }
 
 extern "C" int vidc_colsum(const float* dy, long long M, int C, int ld, float* out, void* scratch, vidc_stream_t stream) {

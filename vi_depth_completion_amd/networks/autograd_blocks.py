@@ -5,6 +5,9 @@ networks/depth_completion.py:16-65, 75-147 and networks/surface_normal_dorn.py:7
 Every conv is a conv2d_bn_act (dilated: conv2d_dilated_bn_act) with scale 1 and the conv's bias (or 0) as shift; every BatchNorm2d a batch_norm_train on
 the batch statistics that updates the module's running statistics in place; the Bottleneck tail is batch_norm_train(residual=identity, relu=True);
 z1 + z2 + z3 + z4 is add_rows.
+A BatchNorm2d that is itself in eval() mode while the network is in train() mode (the usual way to fine-tune a checkpoint with frozen BatchNorm:
+`net.train()`, then `m.eval()` on the BatchNorm modules to freeze, any subset of them) is a batch_norm_eval with the same relu / residual arguments:
+it normalises with the running statistics and leaves them and num_batches_tracked alone, as the torch module does.
 Unlike the inference program (fpn_decoder.emit_branch) nothing is reordered: a train-mode BatchNorm does not commute with the upsample in front of it.
 Activations are NHWC; the module's own parameters and buffers are read, so any torch.optim optimizer steps them.
 """
@@ -45,6 +48,8 @@ class Walk:
     def bn(self, t, m, relu, residual=None):
         if m.momentum is None or not m.track_running_stats:
             raise RuntimeError("%s.forward_autograd: BatchNorm2d with a momentum and running statistics only (the reference's)" % self.who)
+        if not m.training:                         # a frozen BatchNorm (the module itself in eval() mode): running statistics read, nothing updated
+            return self.V.batch_norm_eval(t, m.weight, m.bias, m.running_mean, m.running_var, m.eps, relu, residual)
         self._counters.append(m.num_batches_tracked)
         return self.V.batch_norm_train(t, m.weight, m.bias, m.running_mean, m.running_var, m.momentum, m.eps, relu, residual)[0]
 
@@ -94,7 +99,8 @@ class Walk:
         return z
 
     def finish(self):
-        torch._foreach_add_(self._counters, 1)                                            # every num_batches_tracked, one launch
+        if self._counters:                                                                # (none: every BatchNorm of the pass was frozen)
+            torch._foreach_add_(self._counters, 1)                                        # every num_batches_tracked, one launch
 
 
 def begin(module, tensors, precision):

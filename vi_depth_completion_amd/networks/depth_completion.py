@@ -80,8 +80,8 @@ class ModifiedFPN(_HipModule):
     # ---- training under autograd ---------------------------------------------------------------------------------------------------------
     def forward_autograd(self, image, normal, incomplete_depth, precision=0):
         """The reference's forward in train() mode (depth_completion.py:154-165) from torch.ops.vidc operators only: the three pyramids of
-        networks/autograd_blocks.py (train-mode BatchNorm: running statistics and num_batches_tracked updated as torch does; the depth pyramid's stem has one
-        input channel), combine_rgbdn as torch.cat per level in NHWC, the 3x-wide decoder branches, add_rows, feature_concat.0 with its ReLU, the
+        networks/autograd_blocks.py (train-mode BatchNorm: running statistics and num_batches_tracked updated as torch does; a BatchNorm2d module
+        that is itself in eval() mode is frozen: its running statistics are used and left alone; the depth pyramid's stem has one input channel), combine_rgbdn as torch.cat per level in NHWC, the 3x-wide decoder branches, add_rows, feature_concat.0 with its ReLU, the
         one-channel head (pad 1, ReLU).  Returns the depth (B, 1, H, W) with a grad_fn; gradients reach normal and incomplete_depth (and image) when they
         require them.  precision: the convs' (0 exact fp32, 1 bf16x3)."""
         B, _c, H, W = image.shape

@@ -149,7 +149,8 @@ class SurfaceNormalPrediction(_HipModule):
     # ---- training under autograd ---------------------------------------------------------------------------------------------------------
     def forward_autograd(self, x, gravity_tensor, alignment_tensor, precision=0):
         """The reference's forward in train() mode (surface_normal.py:147-171) from torch.ops.vidc operators only: warp2dof_fwd, the pyramid and the four
-        decoder branches of networks/autograd_blocks.py (train-mode BatchNorm: running statistics and num_batches_tracked updated as torch does), with
+        decoder branches of networks/autograd_blocks.py (train-mode BatchNorm: running statistics and num_batches_tracked updated as torch does; a BatchNorm2d module
+        that is itself in eval() mode is frozen: its running statistics are used and left alone), with
         use_mask feature_mask_scale on the four levels and on their sum (the mask is detached, as there), add_rows, feature_concat.0 with its ReLU, the
         three-channel head, warp2dof_inv_rot_norm(normalize=True).  Returns unit normals (B, 3, H, W) with a grad_fn; the gradient reaches x when it
         requires one.  gravity / aligned get no gradient.  precision: the convs' (0 exact fp32, 1 bf16x3)."""

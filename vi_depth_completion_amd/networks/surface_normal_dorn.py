@@ -138,7 +138,8 @@ class SurfaceNormalDORN(_HipModule):
     def forward_autograd(self, x, dropout_seed=None, precision=0, _keeps=None):
         """The reference's forward in train() mode (surface_normal_dorn.py:18-30, 79-89, 130-154) from torch.ops.vidc operators only -- every conv a
         conv2d_bn_act with scale 1 and its bias (or 0) as shift, every BatchNorm a batch_norm_train on the batch statistics (running statistics and
-        num_batches_tracked updated as torch does), the Bottleneck tail batch_norm_train(residual=identity, relu=True): the backbone is the pyramid walk
+        num_batches_tracked updated as torch does; a BatchNorm2d module that is itself in eval() mode is frozen: batch_norm_eval on its running
+        statistics, nothing updated), the Bottleneck tail batch_norm_train(residual=identity, relu=True): the backbone is the pyramid walk
         of networks/autograd_blocks.py, its last level feeds the scene-understanding module below -- on the module's own parameters and buffers; views,
         permutes and torch.cat are the only torch glue.  Returns unit normals (B, 3, H, W) with a grad_fn.
 

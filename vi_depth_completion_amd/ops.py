@@ -683,6 +683,67 @@ def batch_norm_train_backward(dy, x, y, gamma, save_mean, save_rstd, has_residua
     return dx, dgamma, dbeta, dres
 
 
+def _bn_eval_stats(what, Cc, gamma, beta, running_mean, running_var):
+    """The four per-channel vectors of a frozen BatchNorm as dense float32 (the running statistics are only read: a copy is harmless)."""
+    vs = [v for v in (gamma, beta, running_mean, running_var) if v is not None]
+    if any(v.numel() != Cc for v in vs):
+        raise RuntimeError("%s: %d channels, per-channel vectors of %s" % (what, Cc, " / ".join(str(v.numel()) for v in vs)))
+    return [None if v is None else v.contiguous().float() for v in (gamma, beta, running_mean, running_var)]
+
+
+def batch_norm_eval(x, gamma, beta, running_mean, running_var, eps, relu, residual=None):
+    """y = relu?(BatchNorm2d_eval(x) + residual) on NHWC rows (x, residual: dense or channel slices): nn.BatchNorm2d in eval() mode, the running
+    statistics read and left alone (vidc_bn_eval_forward_add, one launch)."""
+    _dev(x, gamma, beta, running_mean, running_var, residual)
+    x, M, Cc, ldx = _rows(x)
+    gamma, beta, running_mean, running_var = _bn_eval_stats("batch_norm_eval", Cc, gamma, beta, running_mean, running_var)
+    r, ldr = None, 0
+    if residual is not None:
+        if residual.shape != x.shape:
+            raise RuntimeError("batch_norm_eval: residual %s for x %s" % (tuple(residual.shape), tuple(x.shape)))
+        r, _m, _c, ldr = _rows(residual)
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    L.check(L.lib().vidc_bn_eval_forward_add(L.ptr(x), L.ptr(y), M, Cc, ldx, Cc, L.ptr(gamma), L.ptr(beta), L.ptr(running_mean), L.ptr(running_var), eps,
+                                             int(relu), L.ptr(r), ldr, L.current_stream()), "bn_eval_forward")
+    return y
+
+
+def batch_norm_eval_backward(dy, x, y, gamma, running_mean, running_var, eps, has_residual, need_dx, need_affine):
+    """(dx, dgamma, dbeta, dresidual) of batch_norm_eval; what nobody needs comes back empty and is not computed.  y: the forward output when a ReLU
+    followed, else None; x: the forward input, read for dgamma only (None unless need_affine).  With a residual AND a ReLU the ReLU sits behind the
+    sum: vidc_relu_backward masks dy first, the masked gradient is dresidual and what the BatchNorm part starts from.  Without a ReLU the masked
+    gradient is dy itself and dresidual comes back empty (the caller hands dy on).  vidc_bn_eval_backward: need_affine -> the pass over the chunks
+    that also writes dx, and the reduction; else one elementwise launch, no scratch."""
+    _dev(dy, x, y, gamma, running_mean, running_var)
+    dy, M, Cc, lddy = _rows(dy)
+    gamma, _b, running_mean, running_var = _bn_eval_stats("batch_norm_eval_backward", Cc, gamma, None, running_mean, running_var)
+    lib, st = L.lib(), L.current_stream()
+    empty = lambda: dy.new_empty(0)              # noqa: E731  (one per output: the outputs of a custom operator must not alias each other)
+    y_relu, ldy = None, 0
+    if y is not None:
+        y_relu, _m, _c, ldy = _rows(y)
+    dres = empty()
+    if has_residual and y_relu is not None:
+        dres = torch.empty(dy.shape, dtype=torch.float32, device=dy.device)
+        L.check(lib.vidc_relu_backward(L.ptr(dy), L.ptr(y_relu), L.ptr(dres), M, Cc, lddy, ldy, Cc, 0, st), "relu_backward")
+        dy, lddy, y_relu, ldy = dres, Cc, None, 0
+    if not (need_dx or need_affine):
+        return empty(), empty(), empty(), dres
+    xr, ldx, sc = None, 0, None
+    dgamma, dbeta = empty(), empty()
+    if need_affine:
+        if x is None or x.shape != dy.shape:
+            raise RuntimeError("batch_norm_eval_backward: dgamma needs the forward input x, shaped like dy")
+        xr, _m, _c, ldx = _rows(x)
+        dgamma, dbeta = torch.empty(Cc, dtype=torch.float32, device=dy.device), torch.empty(Cc, dtype=torch.float32, device=dy.device)
+        sc = _scratch(lib.vidc_train_scratch_bytes(M, Cc), dy.device)
+    dx = torch.empty(dy.shape, dtype=torch.float32, device=dy.device) if need_dx else empty()
+    L.check(lib.vidc_bn_eval_backward(L.ptr(dy), L.ptr(xr), L.ptr(y_relu), L.ptr(dx) if need_dx else None, M, Cc, lddy, ldx, ldy, Cc, L.ptr(gamma),
+                                      L.ptr(running_mean), L.ptr(running_var), eps, L.ptr(dgamma) if need_affine else None,
+                                      L.ptr(dbeta) if need_affine else None, L.ptr(sc), st), "bn_eval_backward")
+    return dx, dgamma, dbeta, dres
+
+
 def dropout2d_mask(B, Cc, p, seed, offset, device):
     """keep (B, C): 0 or 1 / (1 - p) per (image, channel), Philox4x32-10 at (seed, offset) (vidc_dropout2d_mask)."""
     if not 0.0 <= p < 1.0:

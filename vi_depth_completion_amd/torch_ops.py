@@ -39,6 +39,7 @@ Train-mode operators (TRAIN_OPS / TRAIN_BACKWARD_OPS, added for SurfaceNormalDOR
 SurfaceNormalPrediction):
 
     torch.ops.vidc.batch_norm_train(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual=None) -> (y, save_mean, save_rstd)
+    torch.ops.vidc.batch_norm_eval(x_nhwc, gamma, beta, running_mean, running_var, eps, relu, residual=None) -> y     a frozen BatchNorm2d (FROZEN_BN_OPS)
     torch.ops.vidc.dropout2d(x_nhwc, p, seed, offset) -> (y, keep)           nn.Dropout2d in train() mode, Philox4x32-10 per (image, channel)
     torch.ops.vidc.scale_image_channels(x_nhwc, keep)                        y = x * keep[b][c]: Dropout2d for a given keep table; its own backward
     torch.ops.vidc.normalize_nchw(x)                                         F.normalize(x, dim=1), surface_normal_dorn.py:154
@@ -46,7 +47,10 @@ SurfaceNormalPrediction):
     torch.ops.vidc.add_rows(a, b, relu)                                      z1 + z2 + z3 + z4 of both decoders
 
 batch_norm_train is nn.BatchNorm2d in train() mode (+ residual, + ReLU) on the trainers' kernels, updates the running statistics in place, and reads
-x in place when it is a channel slice.  feature_mask_scale is vidc_mask_scale and its own backward; add_rows is vidc_add_rows, its backward vidc_relu_backward.
+x in place when it is a channel slice.  batch_norm_eval is nn.BatchNorm2d in eval() mode (+ residual, + ReLU) inside a training step -- what
+forward_autograd runs for a BatchNorm module that is itself in eval() mode: the running statistics are read and never written, gradients go to x,
+gamma, beta and residual, and its backward (vidc_bn_eval_backward) launches the per-channel reduction only when gamma or beta asks for a gradient
+(x is saved only then) and writes dx only when x does.  feature_mask_scale is vidc_mask_scale and its own backward; add_rows is vidc_add_rows, its backward vidc_relu_backward.
 
 Losses (normal_l1_loss in TRAIN_OPS, depth_l1_loss in NET_TRAIN_OPS; both registered the same way, _register_l1_loss_backward):
 
@@ -768,6 +772,61 @@ def _batch_norm_train_autograd(x_nhwc, gamma, beta, running_mean, running_var, m
     return _BatchNormTrain.apply(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual)
 
 
+# batch_norm_eval is the frozen form (nn.BatchNorm2d in eval() mode inside a training step): it reads the running statistics and mutates nothing, so it
+# is a plain custom_op with a registered autograd formula.  The backward computes only what somebody needs: without a gradient for gamma / beta it is one
+# elementwise launch that reads neither x (which is then not even saved) nor any scratch; without one for x no dx is written.
+@torch.library.custom_op("vidc::batch_norm_eval", mutates_args=(), device_types=_DEV)
+def batch_norm_eval(x_nhwc: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor, running_var: torch.Tensor, eps: float,
+                    relu: bool, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = relu?(nn.BatchNorm2d in eval() mode (x) + residual) on NHWC: (x - running_mean) / sqrt(running_var + eps) * gamma + beta, the running
+    statistics read and left alone.  x and residual may be channel slices of wider tensors.  vidc_bn_eval_forward_add, one launch."""
+    return _ops.batch_norm_eval(x_nhwc, gamma, beta, running_mean, running_var, eps, relu, residual)
+
+
+@batch_norm_eval.register_fake
+def _(x_nhwc, gamma, beta, running_mean, running_var, eps, relu, residual=None):
+    return x_nhwc.new_empty(x_nhwc.shape)
+
+
+@torch.library.custom_op("vidc::batch_norm_eval_backward", mutates_args=(), device_types=_DEV)
+def batch_norm_eval_backward(dy: torch.Tensor, x_nhwc: Optional[torch.Tensor], y: Optional[torch.Tensor], gamma: torch.Tensor, running_mean: torch.Tensor,
+                             running_var: torch.Tensor, eps: float, has_residual: bool, need_dx: bool,
+                             need_affine: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dx, dgamma, dbeta, dresidual) of batch_norm_eval, each empty when not computed: dx unless need_dx, dgamma / dbeta unless need_affine (x is read
+    for them only and may be None otherwise), dresidual unless a residual sits in front of a ReLU (y given: the masked gradient, which the BatchNorm part
+    starts from; without a ReLU the masked gradient is dy itself).  vidc_bn_eval_backward."""
+    return _ops.batch_norm_eval_backward(dy, x_nhwc, y, gamma, running_mean, running_var, eps, has_residual, need_dx, need_affine)
+
+
+@batch_norm_eval_backward.register_fake
+def _(dy, x_nhwc, y, gamma, running_mean, running_var, eps, has_residual, need_dx, need_affine):
+    Cc = dy.shape[-1]
+    return (dy.new_empty(dy.shape if need_dx else (0,)), dy.new_empty((Cc if need_affine else 0,)), dy.new_empty((Cc if need_affine else 0,)),
+            dy.new_empty(dy.shape if (has_residual and y is not None) else (0,)))
+
+
+def _bn_eval_setup(ctx, inputs, output):
+    x, gamma, beta, running_mean, running_var, eps, relu, residual = inputs
+    need = ctx.needs_input_grad
+    ctx.need_affine = bool(need[1] or need[2])
+    ctx.save_for_backward(x if ctx.need_affine else None, output if relu else None, gamma, running_mean, running_var)
+    ctx.eps, ctx.has_residual, ctx.param_shape = eps, residual is not None, gamma.shape
+
+
+def _bn_eval_backward(ctx, grad_y):
+    x, y, gamma, running_mean, running_var = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    has_res = ctx.has_residual and need[7]
+    dx, dgamma, dbeta, dres = torch.ops.vidc.batch_norm_eval_backward(grad_y, x, y, gamma, running_mean, running_var, ctx.eps, has_res, need[0], ctx.need_affine)
+    if has_res and y is None:
+        dres = grad_y                                # no ReLU behind the sum: the residual's gradient is the incoming one itself
+    return (dx if need[0] else None, dgamma.reshape(ctx.param_shape) if need[1] else None, dbeta.reshape(ctx.param_shape) if need[2] else None, None, None,
+            None, None, dres if has_res else None)
+
+
+torch.library.register_autograd("vidc::batch_norm_eval", _bn_eval_backward, setup_context=_bn_eval_setup)
+
+
 @torch.library.custom_op("vidc::scale_image_channels", mutates_args=(), device_types=_DEV)
 def scale_image_channels(x_nhwc: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
     """y[b,h,w,c] = x[b,h,w,c] * keep[b][c] (vidc_scale_image_channels): Dropout2d's forward for a given keep table, and its own backward."""
@@ -1020,7 +1079,11 @@ NET_TRAIN_OPS = ("depth_l1_loss", "depth_l1_loss_with_grad", "feature_mask_scale
 NET_TRAIN_BACKWARD_OPS = ("depth_l1_loss_backward", "add_rows_backward")
 # the forward warp in grid_sample's three interpolation modes with its backward, and the sampler grids (not differentiable)
 WARP_MODE_OPS = ("warp2dof_fwd_mode", "warp2dof_fwd_mode_backward", "warp2dof_grids")
+# a BatchNorm2d in eval() mode under forward_autograd (fine-tuning with frozen BatchNorm) and its backward
+FROZEN_BN_OPS = ("batch_norm_eval",)
+FROZEN_BN_BACKWARD_OPS = ("batch_norm_eval_backward",)
 OPS = (("plane_ransac_normal", "plane_offset", "plane_project_depth", "plane_finalize", "enrich_scatter", "warp2dof_fwd", "warp2dof_inv_rot_norm", "conv2d_bn_act",
         "conv3x3_winograd", "stem_conv3x3s2", "maxpool3x3s2", "upsample_bilinear_ac", "head_conv1x1_upsample")
-       + BACKWARD_OPS + DORN_OPS + DORN_BACKWARD_OPS + TRAIN_OPS + TRAIN_BACKWARD_OPS + NET_TRAIN_OPS + NET_TRAIN_BACKWARD_OPS + WARP_MODE_OPS)
+       + BACKWARD_OPS + DORN_OPS + DORN_BACKWARD_OPS + TRAIN_OPS + TRAIN_BACKWARD_OPS + NET_TRAIN_OPS + NET_TRAIN_BACKWARD_OPS + WARP_MODE_OPS
+       + FROZEN_BN_OPS + FROZEN_BN_BACKWARD_OPS)
 RATIO_KEYS = ("D_1.05", "D_1.10", "D_1.25", "D_1.56", "D_1.95")      # depth_l1_loss's five ratio counts, as depth_printable_ratios names them
