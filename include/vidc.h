@@ -856,6 +856,10 @@ typedef struct vidc_pack_item {
     int64_t block_begin;
 } vidc_pack_item;
 long long vidc_pack_item_blocks(int Cout, int Cin, int KH, int KW, int kind);
+/* One item of vidc_pack_conv_weights_batched with its descriptor passed as a kernel argument: the same kernel body and the same bits, one launch and
+ * no descriptor table in device memory -- what an eager caller that packs a weight per call wants (the autograd data gradient at plain bf16, kind 5).
+ * VIDC_ERR_SHAPE where vidc_pack_item_blocks(...) is 0. */
+int vidc_pack_conv_weights_one(const float* w_oihw, void* packed, int Cout, int Cin, int KH, int KW, int kind, vidc_stream_t stream);
 int vidc_pack_conv_weights_batched(const vidc_pack_item* items_device, int n_items, long long total_blocks, vidc_stream_t stream);
 int vidc_zero_stuff(const float* dy, float* z, int B, int Ho, int Wo, int C, int lddy, int stride, int H, int W, vidc_stream_t stream);
 /* wgrad: dw_oihw[co][ci][kh][kw] = sum over output pixels of dy[m][co] * x[pixel(m) at the tap][ci], on v_mfma_f32_32x32x2_f32 with the
@@ -872,6 +876,16 @@ int vidc_conv_wgrad(const float* dy, const float* x, float* dw_oihw, int B, int 
 size_t vidc_conv_wgrad_dilated_scratch_bytes(int B, int Ho, int Wo, int Cout, int Cin, int KH, int KW);
 int vidc_conv_wgrad_dilated(const float* dy, const float* x, float* dw_oihw, int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout, int lddy,
                             int KH, int KW, int stride, int pad, int dilation, void* scratch, vidc_stream_t stream);
+/* vidc_conv_wgrad_dilated in bf16 (csrc/wgrad_bf16.hip): both operands are rounded to bf16 (round to nearest even, the rounding of vidc_cast_bf16 and
+ * pack kinds 4 / 5) on the way into LDS, the exact products accumulate in fp32 on v_mfma_f32_32x32x16_bf16 over the pixels of one chunk (at most 1024),
+ * and the chunk partials are summed in fp64 in chunk order and rounded once by the fp32 entries' own final kernel.  One launch plus that reduction:
+ * it replaces, for callers that hold fp32 NHWC tensors, the chain vidc_cast_bf16 / vidc_transpose_bf16 / vidc_im2col_transposed_bf16 / GEMM of the
+ * captured plain-bf16 trainers, and leaves no cast, transposed or im2col tensor in memory.  The contract of vidc_conv_wgrad_dilated (dilation = 1: a plain
+ * conv), and: Cin, Cout, ldx and lddy multiples of 4, dy and x 16-byte aligned.  No floating-point atomics, the same bits on every run.
+ * scratch: vidc_conv_wgrad_bf16_scratch_bytes (its own chunking, not that of vidc_conv_wgrad_scratch_bytes). */
+size_t vidc_conv_wgrad_bf16_scratch_bytes(int B, int Ho, int Wo, int Cout, int Cin, int KH, int KW);
+int vidc_conv_wgrad_bf16(const float* dy, const float* x, float* dw_oihw, int B, int H, int W, int Cin, int ldx, int Ho, int Wo, int Cout, int lddy,
+                         int KH, int KW, int stride, int pad, int dilation, void* scratch, vidc_stream_t stream);
 /* wgrad as a GEMM on the conv kernel: dW[co][tap][ci] = sum_m dY^T[co][m] * Xt[tap*C + ci][m] is the 1x1 case of vidc_conv2d_bn_act with
  * "activations" = the rows of dY^T and "weights" = the rows of Xt (both K-contiguous, K = pixels).  vidc_im2col_transposed writes
  * xt[(tap*C + c)][m] = x[b, oy*s - p + kh, ox*s - p + kw, c] (0 outside the image and for m >= B*Ho*Wo; rows Mp long, Mp % 32 == 0);

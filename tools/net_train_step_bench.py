@@ -10,6 +10,7 @@ three regions of an autograd step: forward + loss, backward, Adam.
     python tools/net_train_step_bench.py --net normal --batch 8 --use-mask                        # SurfaceNormalPrediction(use_mask=True): autograd only
     python tools/net_train_step_bench.py --net dorn --batch 8 --precisions 0                      # SurfaceNormalDORN, dropout_seed 1234: autograd only
     python tools/net_train_step_bench.py --net normal --precisions 0 --no-trainer --frozen-bn all # fine-tuning with frozen BatchNorm beside the train-mode step
+    python tools/net_train_step_bench.py --net depth --precisions 0 --grad-precisions 0,2         # ... and with plain-bf16 conv gradients (grad_precision=2)
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o net -- python tools/net_train_step_bench.py --net depth --precisions 0 --no-trainer
     python tools/net_train_step_bench.py --kernel-stats OUT/.../net_kernel_stats.csv              # the per-kernel share table of that run (no GPU needed)
 
@@ -33,13 +34,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 DTYPES = {0: "f32 (fp32 MFMA fwd / dgrad / wgrad)", 1: "f32+bf16x3 forward, fp32 dgrad / wgrad"}
+GRAD_DTYPES = {0: "f32 forward, bf16 dgrad / wgrad", 1: "f32+bf16x3 forward, bf16 dgrad / wgrad"}      # grad_precision 2
 NETS = {"depth": ("ModifiedFPN", "depth_l1_loss"), "normal": ("SurfaceNormalPrediction", "normal_l1_loss"), "dorn": ("SurfaceNormalDORN", "normal_l1_loss")}
 
 BACKBONES = ("resnet_rgb.", "resnet_normal.", "resnet_depth.", "resnet_pyramids.", "feature_extractor.")
 BN_ENTRIES = ("batch_norm_train", "batch_norm_train_backward", "batch_norm_eval", "batch_norm_eval_backward")      # of vi_depth_completion_amd.ops
 
 GROUPS = (("BatchNorm passes", ("chan_partial_kernel", "chan_final_kernel", "bn_apply", "bn_bwd_apply", "bn_eval_")),
-          ("per-call weight packing", ("pack_weight", "pack_batched_kernel")),
+          ("per-call weight packing", ("pack_weight", "pack_batched_kernel", "pack_one_kernel")),
           ("weight-gradient operands / permute", ("im2col_t", "wgrad_permute_kernel", "transpose_bf16_kernel")),
           ("transposed conv epilogue", ("affine_act_bwd_kernel",)),
           ("ReLU mask / residual gradient", ("relu_bwd_kernel",)),
@@ -136,6 +138,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--precisions", default="0,1", help="the convs' arithmetic of the autograd steps to time: 0 exact fp32, 1 bf16x3 (default: both)")
+    ap.add_argument("--grad-precisions", default="0",
+                    help="the conv gradients' arithmetic of the autograd steps to time: 0 fp32, 2 plain bf16 (forward_autograd's grad_precision; default: 0)")
     ap.add_argument("--use-mask", action="store_true", help="--net normal: SurfaceNormalPrediction(use_mask=True), which only the autograd step trains")
     ap.add_argument("--frozen-bn", choices=("none", "backbone", "all"), default="none",
                     help="BatchNorm2d modules to put into eval() mode (frozen); not none: the train-mode step is timed beside it, both with their BatchNorm share")
@@ -179,7 +183,8 @@ def main():
     result = {"metric": "%s autograd training step" % NETS[args.net][0], "unit": "ms/step", "n_gpus": 1,
               "batch_per_gpu": B, "use_mask": bool(args.use_mask), "autograd": {}}
     settings = ["none"] if args.frozen_bn == "none" else ["none", args.frozen_bn]
-    for precision, frozen in [(int(p), f) for p in args.precisions.split(",") if p != "" for f in settings]:
+    grads = [int(g) for g in args.grad_precisions.split(",") if g != ""]
+    for precision, grad, frozen in [(int(p), g, f) for p in args.precisions.split(",") if p != "" for g in grads for f in settings]:
         cnn = network()
         n_frozen = freeze_batch_norms(cnn, frozen) if frozen != "none" else 0
         optimizer = torch.optim.Adam(cnn.parameters(), lr=1e-4)
@@ -189,7 +194,7 @@ def main():
             mark = (lambda i: marks[i].record()) if marks is not None else (lambda i: None)
             mark(0)
             optimizer.zero_grad()
-            loss = loss_of(cnn.forward_autograd(*inputs, precision=precision, **forward_args))
+            loss = loss_of(cnn.forward_autograd(*inputs, precision=precision, **forward_args, **({"grad_precision": grad} if grad else {})))
             mark(1)
             loss.backward()
             mark(2)
@@ -201,9 +206,10 @@ def main():
         with torch.enable_grad():
             ms, enq, losses = timed(step, args.steps, args.warmup, ev)
         region = lambda a, c: round(sum(e[a].elapsed_time(e[c]) for e in ev) / args.steps, 2)
-        key = str(precision) if frozen == "none" else "%d frozen-bn=%s" % (precision, frozen)
+        key = (str(precision) if frozen == "none" else "%d frozen-bn=%s" % (precision, frozen)) + (" grad=%d" % grad if grad else "")
         result["autograd"][key] = {"ms_per_step": round(ms, 1), "frames_per_s": round(1e3 * B / ms, 1), "host_enqueue_ms_per_step": round(enq, 1),
-                                   "forward_loss_ms": region(0, 1), "backward_ms": region(1, 2), "adam_ms": region(2, 3), "dtype": DTYPES[precision],
+                                   "forward_loss_ms": region(0, 1), "backward_ms": region(1, 2), "adam_ms": region(2, 3),
+                                   "dtype": (GRAD_DTYPES if grad else DTYPES)[precision],
                                    "losses": losses, "peak_memory_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
         if args.frozen_bn != "none":
             with torch.enable_grad():

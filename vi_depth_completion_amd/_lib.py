@@ -216,12 +216,15 @@ SIGNATURES = {
     "vidc_host_mt19937_permutation_prefix": (C.c_int, [_vp, _vp, C.c_longlong, _i, _vp, _vp]),
     "vidc_pack_item_blocks": (C.c_longlong, [_i, _i, _i, _i, _i]),
     "vidc_pack_conv_weights_batched": (C.c_int, [_vp, _i, C.c_longlong, _vp]),
+    "vidc_pack_conv_weights_one": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "vidc_zero_stuff": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "vidc_conv_wgrad_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
     "vidc_conv_wgrad": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vidc_im2col_transposed": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "vidc_conv_wgrad_dilated_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
     "vidc_conv_wgrad_dilated": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "vidc_conv_wgrad_bf16_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+    "vidc_conv_wgrad_bf16": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vidc_im2col_transposed_dilated": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "vidc_wgrad_permute": (C.c_int, [_vp, _vp, _i, _i, _i, _vp]),
     "vidc_transpose_bf16": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _vp]),

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "train_rows.h"
 #include "optim.h"
+#include "wgrad_final.h"
 #include <cstdint>
 #include <type_traits>
 
@@ -837,17 +838,10 @@ __device__ inline void pack_store(const vidc_pack_item& it, long long off, float
 // consecutive bf16 values and stores them at once (2-byte stores before), and a 1x1 forward copy -- the same order as the parameter --
 // skips the LDS round trip: 0.79 ms (4.7 TB/s).  Same values.  (A block -> item index instead of the search over block_begin was
 // measured too: 0.79 against 0.76 ms, nothing -- the table is cache-resident and the search overlaps other blocks' traffic.)
-__global__ void __launch_bounds__(TT) pack_batched_kernel(const vidc_pack_item* __restrict__ items, int n) {
-    __shared__ float tile[64 * (kPackCi * 9 + 1)];          // 64 channels x (8 x 9 + 1) floats = 18.25 KB; also holds 8 units x 64 x 9, 64 units x 64 x 1
-    static_assert(64 * 64 <= 64 * (kPackCi * 9 + 1) && 64 * (64 + 1) <= 64 * (kPackCi * 9 + 1), "1x1 blocks must fit the tile");
-    const long long blk = blockIdx.x;
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (items[mid].block_begin <= blk) lo = mid; else hi = mid - 1;
-    }
-    const vidc_pack_item it = items[lo];
-    const int lb = (int)(blk - it.block_begin);
+constexpr int kPackTile = 64 * (kPackCi * 9 + 1);         // 64 channels x (8 x 9 + 1) floats = 18.25 KB; also holds 8 units x 64 x 9, 64 units x 64 x 1
+static_assert(64 * 64 <= kPackTile && 64 * (64 + 1) <= kPackTile, "1x1 blocks must fit the tile");
+// block lb of item `it` (both uniform per workgroup); tile: kPackTile floats of LDS.  One body for the batched launch and for pack_one_kernel.
+__device__ inline void pack_block(const vidc_pack_item& it, int lb, float* tile) {
     const int taps = it.KH * it.KW, U = (it.kind & 4) ? 64 : 32, seg = U * taps;
     const bool plain = (it.kind & 4) != 0;                  // plain bf16: U == 64
     if (!(it.kind & 1)) {
@@ -926,6 +920,22 @@ __global__ void __launch_bounds__(TT) pack_batched_kernel(const vidc_pack_item* 
             }
         }
     }
+}
+__global__ void __launch_bounds__(TT) pack_batched_kernel(const vidc_pack_item* __restrict__ items, int n) {
+    __shared__ float tile[kPackTile];
+    const long long blk = blockIdx.x;
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (items[mid].block_begin <= blk) lo = mid; else hi = mid - 1;
+    }
+    const vidc_pack_item it = items[lo];
+    pack_block(it, (int)(blk - it.block_begin), tile);
+}
+// One item, its descriptor a kernel argument: what an eager caller packs per call (no descriptor table in device memory, no upload).
+__global__ void __launch_bounds__(TT) pack_one_kernel(const vidc_pack_item it) {
+    __shared__ float tile[kPackTile];
+    pack_block(it, (int)blockIdx.x, tile);
 }
 
 // fp32 NHWC rows [rows][ldx] (C channels used) -> dense bf16 rows [rows][C] (round to nearest even); one thread per 8 channels
@@ -1640,6 +1650,21 @@ extern "C" int vidc_pack_conv_weights_batched(const vidc_pack_item* items_device
     return VIDC_OK;
 }
 
+extern "C" int vidc_pack_conv_weights_one(const float* w_oihw, void* packed, int Cout, int Cin, int KH, int KW, int kind, vidc_stream_t stream) {
+    VIDC_REQUIRE(w_oihw && packed, VIDC_ERR_NULL, "vidc_pack_conv_weights_one: null pointer");
+    const long long nb = vidc_pack_item_blocks(Cout, Cin, KH, KW, kind);
+    VIDC_REQUIRE(nb > 0 && nb < (1ll << 31), VIDC_ERR_SHAPE, "vidc_pack_conv_weights_one: %dx%dx%dx%d cannot be packed as kind %d", Cout, Cin, KH, KW, kind);
+    vidc_pack_item it = {};
+    it.w = w_oihw;
+    it.packed = reinterpret_cast<float*>(packed);
+    it.Cout = Cout; it.Cin = Cin; it.KH = KH; it.KW = KW;
+    it.kind = kind;
+    it.block_begin = 0;
+    hipLaunchKernelGGL(pack_one_kernel, dim3((unsigned)nb), dim3(TT), 0, vidc::as_stream(stream), it);
+    VIDC_CHECK_LAUNCH("pack_one_kernel");
+    return VIDC_OK;
+}
+
 extern "C" int vidc_cast_bf16(const float* x, void* y, long long rows, int C, int ldx, vidc_stream_t stream) {
     VIDC_REQUIRE(x && y, VIDC_ERR_NULL, "vidc_cast_bf16: null pointer");
     VIDC_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && ldx >= C && ldx % 4 == 0, VIDC_ERR_SHAPE, "vidc_cast_bf16: C must be a multiple of 8");
@@ -1656,6 +1681,10 @@ extern "C" int vidc_zero_stuff(const float* dy, float* z, int B, int Ho, int Wo,
                        stride, H, W);
     VIDC_CHECK_LAUNCH("zero_stuff_kernel");
     return VIDC_OK;
+}
+
+void vidc::launch_wgrad_final(const float* partial, int chunks, int taps, int Cout, int Cin, float* dw_oihw, hipStream_t st) {
+    hipLaunchKernelGGL(wgrad_final_kernel, dim3(blocks((long long)taps * Cout * Cin)), dim3(TT), 0, st, partial, chunks, taps, Cout, Cin, dw_oihw);
 }
 
 namespace {
@@ -1699,7 +1728,7 @@ int conv_wgrad_launch(const char* what, const float* dy, const float* x, float* 
     float* partial = reinterpret_cast<float*>(scratch);
     hipLaunchKernelGGL(wgrad_kernel, dim3((Cout + 127) / 128, ((Cin + 127) / 128) * taps, chunks), dim3(256), 0, st, dy, x, B, H, W, Cin, ldx, Ho, Wo, Cout, lddy,
                        KH, KW, stride, pad, dilation, rows, partial);
-    hipLaunchKernelGGL(wgrad_final_kernel, dim3(blocks((long long)taps * Cout * Cin)), dim3(TT), 0, st, partial, chunks, taps, Cout, Cin, dw_oihw);
+    vidc::launch_wgrad_final(partial, chunks, taps, Cout, Cin, dw_oihw, st);
     VIDC_CHECK_LAUNCH("conv_wgrad");
     return VIDC_OK;
 }

@@ -19,12 +19,19 @@ class Walk:
     """One forward pass: the constants the convs share, and the num_batches_tracked counters its BatchNorms touched (`finish` bumps them in one
     launch, as nn.BatchNorm2d does one by one)."""
 
-    def __init__(self, who, device, precision):
+    def __init__(self, who, device, precision, grad_precision=0):
         if precision not in (0, 1):
             raise RuntimeError("%s.forward_autograd: precision 0 (exact fp32) or 1 (bf16x3); the other conv modes have no backward" % who)
-        self.who, self.device, self.precision = who, device, precision
+        if grad_precision not in (0, 2):
+            raise RuntimeError("%s.forward_autograd: grad_precision 0 (fp32 conv gradients) or 2 (plain bf16 conv gradients)" % who)
+        self.who, self.device, self.precision, self.grad_precision = who, device, precision, grad_precision
         self.V = torch.ops.vidc
         self._consts, self._counters = {}, []
+
+    def grads(self):
+        """The context every conv of the walk runs its forward in: it records the walk's gradient arithmetic for the conv's backward."""
+        from .. import torch_ops                   # (here: torch_ops imports this package)
+        return torch_ops.grad_precision(self.grad_precision)
 
     def const(self, n, v):
         if (n, v) not in self._consts:
@@ -34,16 +41,18 @@ class Walk:
     def conv(self, t, m, relu=False):
         co = m.out_channels
         shift = m.bias if m.bias is not None else self.const(co, 0.0)
-        if m.dilation[0] > 1:
-            return self.V.conv2d_dilated_bn_act(t, m.weight, self.const(co, 1.0), shift, m.padding[0], m.dilation[0], relu, self.precision)
-        return self.V.conv2d_bn_act(t, m.weight, self.const(co, 1.0), shift, m.stride[0], m.padding[0], relu, self.precision)
+        with self.grads():
+            if m.dilation[0] > 1:
+                return self.V.conv2d_dilated_bn_act(t, m.weight, self.const(co, 1.0), shift, m.padding[0], m.dilation[0], relu, self.precision)
+            return self.V.conv2d_bn_act(t, m.weight, self.const(co, 1.0), shift, m.stride[0], m.padding[0], relu, self.precision)
 
     def linear(self, t, m, relu=False):
         """nn.Linear on t (B, h, w, c) flattened as NCHW, run as a 1x1 conv: the weight's (c, h, w) columns reordered to (h, w, c), as engine.linear."""
         B, h, w, c = t.shape
         wt = m.weight.view(-1, c, h, w).permute(0, 2, 3, 1).reshape(-1, h * w * c, 1, 1)
         shift = m.bias if m.bias is not None else self.const(wt.shape[0], 0.0)
-        return self.V.conv2d_bn_act(t.reshape(B, 1, 1, -1), wt, self.const(wt.shape[0], 1.0), shift, 1, 0, relu, self.precision)
+        with self.grads():
+            return self.V.conv2d_bn_act(t.reshape(B, 1, 1, -1), wt, self.const(wt.shape[0], 1.0), shift, 1, 0, relu, self.precision)
 
     def bn(self, t, m, relu, residual=None):
         if m.momentum is None or not m.track_running_stats:
@@ -103,15 +112,16 @@ class Walk:
             torch._foreach_add_(self._counters, 1)                                        # every num_batches_tracked, one launch
 
 
-def begin(module, tensors, precision):
-    """How every forward_autograd opens, after its own shape checks: refuse CPU tensors, eval() mode and a precision without a backward, and only then
-    mark the module's folded inference weights stale and hand out the pass's Walk."""
+def begin(module, tensors, precision, grad_precision=0):
+    """How every forward_autograd opens, after its own shape checks: refuse CPU tensors, eval() mode, a precision without a backward and a
+    grad_precision other than 0 / 2, and only then mark the module's folded inference weights stale and hand out the pass's Walk, whose convs (and
+    DORN's Linear) run inside torch_ops.grad_precision(grad_precision); the stem and the heads, with backward kernels of their own, stay fp32."""
     who = type(module).__name__
     for t in tensors:
         if not t.is_cuda:
             raise RuntimeError("%s runs on the GPU only: there is no CPU/eager fallback" % who)
     if not module.training:
         raise RuntimeError("%s.forward_autograd is the train() mode forward; call .train() (eval(): forward)" % who)
-    walk = Walk(who, tensors[0].device, precision)
+    walk = Walk(who, tensors[0].device, precision, grad_precision)
     module._autograd_dirty = True
     return walk

@@ -78,17 +78,18 @@ class ModifiedFPN(_HipModule):
         return self.enqueue(image, normal, incomplete_depth).clone()
 
     # ---- training under autograd ---------------------------------------------------------------------------------------------------------
-    def forward_autograd(self, image, normal, incomplete_depth, precision=0):
+    def forward_autograd(self, image, normal, incomplete_depth, precision=0, grad_precision=0):
         """The reference's forward in train() mode (depth_completion.py:154-165) from torch.ops.vidc operators only: the three pyramids of
         networks/autograd_blocks.py (train-mode BatchNorm: running statistics and num_batches_tracked updated as torch does; a BatchNorm2d module
         that is itself in eval() mode is frozen: its running statistics are used and left alone; the depth pyramid's stem has one input channel), combine_rgbdn as torch.cat per level in NHWC, the 3x-wide decoder branches, add_rows, feature_concat.0 with its ReLU, the
         one-channel head (pad 1, ReLU).  Returns the depth (B, 1, H, W) with a grad_fn; gradients reach normal and incomplete_depth (and image) when they
-        require them.  precision: the convs' (0 exact fp32, 1 bf16x3)."""
+        require them.  precision: the convs' (0 exact fp32, 1 bf16x3).  grad_precision: the arithmetic of
+        the convs' data and weight gradients, 0 fp32 (today's backward) or 2 plain bf16 (torch_ops.grad_precision); the stem and the head stay fp32."""
         B, _c, H, W = image.shape
         if tuple(normal.shape) != (B, 3, H, W) or tuple(incomplete_depth.shape) != (B, 1, H, W) or image.shape[1] != 3:
             raise ValueError("%s: image and normal (B,3,H,W), incomplete_depth (B,1,H,W); got %s, %s, %s"
                              % (type(self).__name__, tuple(image.shape), tuple(normal.shape), tuple(incomplete_depth.shape)))
-        walk = autograd_blocks.begin(self, (image, normal, incomplete_depth), precision)
+        walk = autograd_blocks.begin(self, (image, normal, incomplete_depth), precision, grad_precision)
         V = walk.V
         pyramids = [walk.pyramid(t, rp) for t, rp in ((image, self.resnet_rgb), (normal, self.resnet_normal), (incomplete_depth, self.resnet_depth))]
         levels = [torch.cat(per_level, dim=3) for per_level in zip(*pyramids)]               # combine_rgbdn, NHWC

@@ -147,17 +147,18 @@ class SurfaceNormalPrediction(_HipModule):
         return self.enqueue(x, gravity_tensor, alignment_tensor).clone()
 
     # ---- training under autograd ---------------------------------------------------------------------------------------------------------
-    def forward_autograd(self, x, gravity_tensor, alignment_tensor, precision=0):
+    def forward_autograd(self, x, gravity_tensor, alignment_tensor, precision=0, grad_precision=0):
         """The reference's forward in train() mode (surface_normal.py:147-171) from torch.ops.vidc operators only: warp2dof_fwd, the pyramid and the four
         decoder branches of networks/autograd_blocks.py (train-mode BatchNorm: running statistics and num_batches_tracked updated as torch does; a BatchNorm2d module
         that is itself in eval() mode is frozen: its running statistics are used and left alone), with
         use_mask feature_mask_scale on the four levels and on their sum (the mask is detached, as there), add_rows, feature_concat.0 with its ReLU, the
         three-channel head, warp2dof_inv_rot_norm(normalize=True).  Returns unit normals (B, 3, H, W) with a grad_fn; the gradient reaches x when it
-        requires one.  gravity / aligned get no gradient.  precision: the convs' (0 exact fp32, 1 bf16x3)."""
+        requires one.  gravity / aligned get no gradient.  precision: the convs' (0 exact fp32, 1 bf16x3).  grad_precision: the arithmetic of
+        the convs' data and weight gradients, 0 fp32 (today's backward) or 2 plain bf16 (torch_ops.grad_precision); the stem and the head stay fp32."""
         wp = self.warp_2dof_alignment
         if tuple(x.shape[1:]) != (self.resnet_pyramids.channel, wp.H, wp.W):
             raise ValueError("%s was built for %s inputs, got %s" % (type(self).__name__, (self.resnet_pyramids.channel, wp.H, wp.W), tuple(x.shape[1:])))
-        walk = autograd_blocks.begin(self, (x, gravity_tensor, alignment_tensor), precision)
+        walk = autograd_blocks.begin(self, (x, gravity_tensor, alignment_tensor), precision, grad_precision)
         V = walk.V
         geom = (wp.fx, wp.fy, wp.cx, wp.cy, wp.align_corners)
         xw = V.warp2dof_fwd(x, gravity_tensor, alignment_tensor, *geom)[1]

@@ -135,7 +135,7 @@ class SurfaceNormalDORN(_HipModule):
         return prog.tensor(prog.outputs["normals"]).clone()
 
     # ---- training under autograd ---------------------------------------------------------------------------------------------------------
-    def forward_autograd(self, x, dropout_seed=None, precision=0, _keeps=None):
+    def forward_autograd(self, x, dropout_seed=None, precision=0, _keeps=None, grad_precision=0):
         """The reference's forward in train() mode (surface_normal_dorn.py:18-30, 79-89, 130-154) from torch.ops.vidc operators only -- every conv a
         conv2d_bn_act with scale 1 and its bias (or 0) as shift, every BatchNorm a batch_norm_train on the batch statistics (running statistics and
         num_batches_tracked updated as torch does; a BatchNorm2d module that is itself in eval() mode is frozen: batch_norm_eval on its running
@@ -144,12 +144,13 @@ class SurfaceNormalDORN(_HipModule):
         permutes and torch.cat are the only torch glue.  Returns unit normals (B, 3, H, W) with a grad_fn.
 
         dropout_seed: the 64-bit Philox key of the three Dropout2d draws (default: drawn from torch's default generator at call time); layer l of
-        call n draws at offset 4 * n + l (DROPOUT_OFFSETS, self.dropout_step).  precision: the convs' (0 exact fp32, 1 bf16x3).  _keeps (tests): the
+        call n draws at offset 4 * n + l (DROPOUT_OFFSETS, self.dropout_step).  precision: the convs' (0 exact fp32, 1 bf16x3).  grad_precision: the arithmetic of
+        the convs' data and weight gradients, 0 fp32 (today's backward) or 2 plain bf16 (torch_ops.grad_precision); the stem and the head stay fp32.  _keeps (tests): the
         three (B, C) keep tables to use instead of drawing them."""
         H, W = x.shape[2:]
         if (H, W) != tuple(self.output_size):
             raise ValueError("SurfaceNormalDORN was built for %s inputs, got %s" % (tuple(self.output_size), (H, W)))
-        walk = autograd_blocks.begin(self, (x,), precision)
+        walk = autograd_blocks.begin(self, (x,), precision, grad_precision)
         V, conv, bn = walk.V, walk.conv, walk.bn
         if dropout_seed is None:
             dropout_seed = int(torch.empty((), dtype=torch.int64).random_().item())

@@ -429,20 +429,30 @@ def affine_act_backward(dy, y, scale, shift, relu, c_raw=None, all_from_raw=Fals
 
 
 def pack_conv_weight_dgrad(w_oihw, precision=0):
-    """OIHW -> the weights of the data-gradient conv (kernel flipped, channels transposed) in the format of `precision` (0 fp32, 1 bf16x3)."""
+    """OIHW -> the weights of the data-gradient conv (kernel flipped, channels transposed) in the format of `precision` (0 fp32, 1 bf16x3,
+    2 plain bf16: a torch.bfloat16 tensor, pack kind 5 through vidc_pack_conv_weights_one -- the batched packer's kernel body with the descriptor
+    as a kernel argument: one launch, no descriptor upload)."""
     _dev(w_oihw)
     w = w_oihw.contiguous().float()
     co, ci, kh, kw = w.shape
-    out = torch.empty((ci, kh * kw * co), dtype=torch.float32, device=w.device)
+    if precision == L.PREC_BF16:
+        out = torch.empty((ci, kh * kw * co), dtype=torch.bfloat16, device=w.device)
+    else:
+        out = torch.empty((ci, kh * kw * co), dtype=torch.float32, device=w.device)
     if precision == L.PREC_FP32:
         L.check(L.lib().vidc_pack_conv_weight_dgrad(L.ptr(w), L.ptr(out), co, ci, kh, kw, L.current_stream()), "pack_conv_weight_dgrad")
         return out
-    if precision != L.PREC_BF16X3:
+    if precision not in (L.PREC_BF16X3, L.PREC_BF16):
         raise RuntimeError("pack_conv_weight_dgrad: precision %d has no data-gradient form" % precision)
-    kind = 3
+    kind = 3 if precision == L.PREC_BF16X3 else 5
     nb = L.lib().vidc_pack_item_blocks(co, ci, kh, kw, kind)
     if nb <= 0:
+        if kind == 5:
+            raise RuntimeError("conv weight %dx%dx%dx%d cannot be packed for the bf16 data gradient (Cout a multiple of 64, kernels up to 3x3)" % (co, ci, kh, kw))
         raise RuntimeError("conv weight %dx%dx%dx%d cannot be packed for the bf16x3 data gradient (Cout a multiple of 32, kernels up to 3x3)" % (co, ci, kh, kw))
+    if kind == 5:
+        L.check(L.lib().vidc_pack_conv_weights_one(L.ptr(w), L.ptr(out), co, ci, kh, kw, kind, L.current_stream()), "pack_conv_weights_one")
+        return out
     item = (L.PackItem * 1)()
     item[0].w, item[0].packed, item[0].Cout, item[0].Cin, item[0].KH, item[0].KW, item[0].kind, item[0].block_begin = L.ptr(w), L.ptr(out), co, ci, kh, kw, kind, 0
     dev = torch.frombuffer(bytearray(bytes(item)), dtype=torch.uint8).to(w.device)
@@ -450,13 +460,36 @@ def pack_conv_weight_dgrad(w_oihw, precision=0):
     return out
 
 
+def conv_backward_data_precision(w_shape, precision):
+    """The arithmetic conv_backward_data runs at `precision` for a conv of weight shape (Cout, Cin, KH, KW) -- the one statement of the rule.
+    Precision 2 (plain bf16) needs the conv kernel's bf16 operand geometry: Cout, the K side of the data-gradient conv, in whole 64-channel
+    units that pack kind 5 can write (kernels up to 3x3), and Cin, its output side, a multiple of 32.  Any other conv takes its data gradient in
+    exact fp32 (0), as at precision 0.  Precisions 0 and 1 are returned as they are."""
+    co, ci, kh, kw = w_shape
+    if precision != L.PREC_BF16:
+        return precision
+    return L.PREC_BF16 if ci % 32 == 0 and L.lib().vidc_pack_item_blocks(co, ci, kh, kw, 5) > 0 else L.PREC_FP32
+
+
+def conv_backward_weight_precision(w_shape, precision, aligned=True):
+    """The arithmetic conv_backward_weight runs at `precision` (0 or 2): 2, vidc_conv_wgrad_bf16, where Cin and Cout are multiples of 4 and
+    both tensors start on a 16-byte boundary (`aligned`: its 16-byte loads; torch's own allocations do, a view at an odd storage offset may
+    not); otherwise the fp32 kernel (0)."""
+    co, ci, _kh, _kw = w_shape
+    if precision not in (L.PREC_FP32, L.PREC_BF16):
+        raise RuntimeError("conv_backward_weight: precision must be 0 (fp32) or 2 (bf16), got %r" % (precision,))
+    return L.PREC_BF16 if precision == L.PREC_BF16 and ci % 4 == 0 and co % 4 == 0 and aligned else L.PREC_FP32
+
+
 def conv_backward_data(dc, w_oihw, H, W, stride, pad, precision=0, dilation=1):
     """dx NHWC (B,H,W,Cin) of a conv from the gradient dc of its raw output: vidc_zero_stuff (stride > 1) + the conv kernel on the
     data-gradient weights, in the arithmetic of `precision` (the sequence DepthCompletionTrainer.conv records).  dilation > 1 (stride 1 only):
-    the same conv kernel with the same dilation and pad' = dilation * (k - 1) - pad."""
+    the same conv kernel with the same dilation and pad' = dilation * (k - 1) - pad.  precision=2: the conv kernel at VIDC_PREC_BF16 on pack
+    kind 5 weights, dc cast by conv2d_bn_act -- where conv_backward_data_precision allows it, else the fp32 data gradient of precision 0."""
     _dev(dc, w_oihw)
     dc = dc.contiguous()
     co, ci, kh, kw = w_oihw.shape
+    precision = conv_backward_data_precision((co, ci, kh, kw), precision)
     B, Ho, Wo, _c = dc.shape
     if dilation != 1:
         if dilation < 1 or stride != 1 or kh != kw or dilation * (kh - 1) - pad < 0:
@@ -483,15 +516,21 @@ def conv_backward_data(dc, w_oihw, H, W, stride, pad, precision=0, dilation=1):
     return dx
 
 
-def conv_backward_weight(dc, x, w_shape, stride, pad, dilation=1):
+def conv_backward_weight(dc, x, w_shape, stride, pad, dilation=1, precision=0):
     """dw OIHW (fp32) from the gradient dc of the raw conv output and the conv's NHWC input (vidc_conv_wgrad; vidc_conv_wgrad_dilated when
-    dilation != 1)."""
+    dilation != 1).  precision=2: vidc_conv_wgrad_bf16 (both operands rounded to bf16, fp32 accumulation) where
+    conv_backward_weight_precision allows it, else the fp32 kernel."""
     _dev(dc, x)
     dc, x = dc.contiguous(), x.contiguous()
     co, ci, kh, kw = w_shape
     B, H, W, _c = x.shape
     _b, Ho, Wo, _co = dc.shape
     dw = torch.empty((co, ci, kh, kw), dtype=torch.float32, device=x.device)
+    if conv_backward_weight_precision(w_shape, precision, aligned=dc.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0) == L.PREC_BF16:
+        sc = _scratch(L.lib().vidc_conv_wgrad_bf16_scratch_bytes(B, Ho, Wo, co, ci, kh, kw), x.device)
+        L.check(L.lib().vidc_conv_wgrad_bf16(L.ptr(dc), L.ptr(x), L.ptr(dw), B, H, W, ci, ci, Ho, Wo, co, co, kh, kw, stride, pad, dilation, L.ptr(sc),
+                                             L.current_stream()), "conv_wgrad_bf16")
+        return dw
     if dilation != 1:
         sc = _scratch(L.lib().vidc_conv_wgrad_dilated_scratch_bytes(B, Ho, Wo, co, ci, kh, kw), x.device)
         L.check(L.lib().vidc_conv_wgrad_dilated(L.ptr(dc), L.ptr(x), L.ptr(dw), B, H, W, ci, ci, Ho, Wo, co, co, kh, kw, stride, pad, dilation, L.ptr(sc),

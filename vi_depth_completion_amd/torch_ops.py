@@ -67,7 +67,9 @@ itself a custom operator (`torch.ops.vidc.*_backward`, listed in the *_BACKWARD_
 the gradient (scale_image_channels, which is also dropout2d's backward, and feature_mask_scale), built from HIP kernels only -- the warp adjoints of
 csrc/warp.hip, vidc_affine_act_backward + zero-stuffing + the conv kernel on data-gradient weights + vidc_conv_wgrad for the convs (precision 0 and 1; Winograd forwards share the
 direct form's backward; the data gradient runs in exact fp32 except behind a Winograd forward at precision 1, where it runs in bf16x3 like
-the forward), the backward kernels of csrc/train.hip for the glue, batch_norm_train and normalize_nchw.  Gradients flow to images / activations, conv weights, the
+the forward; inside `grad_precision(2)` both conv gradients of every conv operator run in plain bf16 instead -- the data gradient on the conv
+kernel at precision 2, the weight gradient on vidc_conv_wgrad_bf16 -- where ops.conv_backward_data_precision / conv_backward_weight_precision
+allow it, while dc, dscale, dshift and the forward keep their arithmetic), the backward kernels of csrc/train.hip for the glue, batch_norm_train and normalize_nchw.  Gradients flow to images / activations, conv weights, the
 folded scale / shift and the head's bias; only those `ctx.needs_input_grad` asks for are computed, and nothing is saved when gradients are
 disabled.  `gravity` / `aligned` get no gradient (the warp record is built with cosf / atan2f / bbox min-max) and precision 3 (MXFP8) has no
 backward: requesting either raises.  The dilated conv's backward is the direct form's with stride 1: the data gradient is the conv kernel on
@@ -76,6 +78,8 @@ is vidc_avgpool2d_backward.  The head's backward covers up to four output channe
 one-channel planes: the depth head, surface_normal.py:143 and surface_normal_dorn.py:74-75).  A loss's backward is dpred * grad_loss.  Double backward
 is not supported.  The plane operators (`plane_*`, `enrich_scatter`) stay non-differentiable: they are RANSAC decisions and index scatters.
 """
+import contextlib
+import threading
 from typing import Optional, Tuple
 
 import torch
@@ -84,6 +88,29 @@ from . import ops as _ops
 from .networks.warping_2dof_alignment import Warping2DOFAlignment
 
 _DEV = "cuda"
+
+
+_grad_state = threading.local()
+
+
+def current_grad_precision():
+    """The arithmetic of the conv gradients that a conv forward records for its backward: 0 (fp32; the default) or 2 (plain bf16)."""
+    return getattr(_grad_state, "precision", 0)
+
+
+@contextlib.contextmanager
+def grad_precision(p):
+    """Context manager: conv operators whose FORWARD runs inside record `p` as the arithmetic of their data and weight gradients.  0: today's
+    backward (exact fp32; bf16x3 data gradient behind a Winograd forward at precision 1).  2: plain bf16 operands with fp32 accumulation
+    (conv2d_bn_act_backward).  Re-entrant; the previous value is restored on exit.  The forward's own `precision` is a separate knob."""
+    if p not in (0, 2):
+        raise RuntimeError("grad_precision: the gradient arithmetic is 0 (fp32) or 2 (plain bf16), got %r" % (p,))
+    previous = current_grad_precision()
+    _grad_state.precision = p
+    try:
+        yield
+    finally:
+        _grad_state.precision = previous
 
 
 def _warper(x, fx, fy, cx, cy, align_corners):
@@ -474,7 +501,7 @@ def _conv_backward_body(what, dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, s
     dx = _ops.conv_backward_data(dc, w_oihw, in_h, in_w, stride, pad, precision, **dil) if need_x else dy.new_empty(0)
     if need_w and x_nhwc is None:
         raise RuntimeError("%s: dw needs the conv's input" % what)
-    dw = _ops.conv_backward_weight(dc, x_nhwc, tuple(w_oihw.shape), stride, pad, **dil) if need_w else dy.new_empty(0)
+    dw = _ops.conv_backward_weight(dc, x_nhwc, tuple(w_oihw.shape), stride, pad, precision=2 if precision == 2 else 0, **dil) if need_w else dy.new_empty(0)
     return dx, dw, (dscale if need_affine else dy.new_empty(0)), (dshift if need_affine else dy.new_empty(0))
 
 
@@ -503,7 +530,10 @@ def conv2d_bn_act_backward(dy: torch.Tensor, x_nhwc: Optional[torch.Tensor], w_o
     of 1 is less than the fp32 conv's own rounding of c, and nothing where it does not (scale 1e-30, shift 1: y == shift, c == 0).  The rule
     is evaluated here, on the host, from scale and shift alone (it assumes that order of c); the conv is re-run only if it names a channel,
     and the kernel applies the same fp32 comparison per channel, so the channels it keeps have the bits of a call without the re-run.
-    x_nhwc is read by dw and by that re-run."""
+    x_nhwc is read by dw and by that re-run.
+    precision 2 (recorded inside grad_precision(2)): dx = the conv kernel at plain bf16 on pack kind 5 weights over the bf16 cast of dc, and dw =
+    vidc_conv_wgrad_bf16 (dc and x rounded to bf16, fp32 accumulation), each where ops.conv_backward_data_precision /
+    ops.conv_backward_weight_precision allow it and in fp32 otherwise; dc, dscale, dshift and the c_raw re-run stay fp32 and untouched."""
     return _conv_backward_body("conv2d_bn_act_backward", dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, stride, pad, 1, relu, precision, need_x, need_w,
                                need_affine, recompute_c)
 
@@ -520,7 +550,8 @@ def conv2d_dilated_bn_act_backward(dy: torch.Tensor, x_nhwc: Optional[torch.Tens
     """(dx, dw, dscale, dshift) of conv2d_dilated_bn_act, as conv2d_bn_act_backward with stride 1: vidc_affine_act_backward -> dc; dx = the conv kernel
     on the data-gradient weights over dc with the same dilation and pad' = dilation * (k - 1) - pad, in the arithmetic of `precision` (the
     registration passes 0: the direct form's data gradient is exact fp32); dw = vidc_conv_wgrad_dilated in fp32; dscale's re-run of the conv
-    (recompute_c, or a zero scale) is dilated as well."""
+    (recompute_c, or a zero scale) is dilated as well.  precision 2 (grad_precision(2)): dx and dw in plain bf16 as in conv2d_bn_act_backward, dw through
+    vidc_conv_wgrad_bf16 with the dilation; dc, dscale, dshift and the re-run stay fp32."""
     return _conv_backward_body("conv2d_dilated_bn_act_backward", dy, x_nhwc, w_oihw, y, scale, shift, in_h, in_w, 1, pad, dilation, relu, precision, need_x,
                                need_w, need_affine, recompute_c)
 
@@ -539,6 +570,8 @@ def _conv_setup_common(ctx, what, x, w, scale, shift, y, geometry, relu, precisi
     need_x, need_w, need_affine = needs[0], needs[1], needs[2] or needs[3]
     ctx.save_for_backward(x if (need_w or need_affine) else None, w, y, scale, shift)      # (dscale re-runs the conv where a scale is 0)
     dgrad_precision = precision if winograd else 0      # (see conv2d_bn_act_backward)
+    if current_grad_precision() == 2:                   # grad_precision(2): both conv gradients in plain bf16, whatever the forward ran in
+        dgrad_precision = 2
     ctx.args = (x.shape[1], x.shape[2]) + geometry + (relu, dgrad_precision, need_x, need_w, need_affine, bool(needs[2] and (precision == 1 or winograd)))
 
 
